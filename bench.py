@@ -13,14 +13,21 @@ scaling), each frame a row of `stride` fp32 samples = [jitter gap 0..299 | chirp
     python bench.py --gpus 1 --steps 100 --warmup 5      (the defaults: a timed region of ~0.8 s)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...      (not under torchrun: starts its own N rank processes, see launch_ranks)
+    python bench.py --full            (the headline run, then every secondary measurement listed below)
+    python bench.py --dump-outputs DIR    (also writes the last timed step's outputs as .npy files, see dump_outputs)
 
 N = 1 is BASELINE config 2 (65 536 frames); N > 1 is BASELINE config 4 (131 072 frames per GPU = 1 048 576 at
-N = 8, weak scaling), timed with the per-chunk overlapped all-gather (`value`) and again with the literal single
-all-gather of the north_star (`single_gather`).
+N = 8, weak scaling), timed with the per-chunk overlapped all-gather (`value`).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for
-the dominant kernel (demod_kernel) and `cpu_baseline` (the NumPy oracle, 1 thread, on
-a bounded sample of the same workload).
+the dominant kernel (demod_kernel).  A plain run sets up, warms up, times the steps, checks every decoded bit and
+sync offset of the last step, and prints the line.  With --full the same process then adds what takes runs of its
+own: the sustained-power probe and `roofline.power`, the secondary legs (screened sync, int16 storage, 16-QAM,
+config 5, the other symbol sizes, the config-3 stream and host ingest, the reference's Final System Test recording),
+the measured copy bandwidth, `cpu_baseline` (the NumPy oracle, 1 thread and all cores, on a bounded sample of the
+same workload and on configs 1 and 3) and, at N > 1, the literal single all-gather of the north_star
+(`single_gather`) and both forms without the collective (`no_gather`, `gather_cost`).  The --no-* options switch
+single parts of --full off.
 """
 import argparse
 import json
@@ -36,6 +43,25 @@ import torch         # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 WIN_LO = -8                    # search window = chirp-start lags [-8, window-8): jitter gaps 0..299 are interior points
+DUMP_MAX_BYTES = 60_000_000    # --dump-outputs: all files together stay below 64 MB (headers included)
+DUMP_SEED = 20261003
+
+
+def dump_outputs(out_dir, starts, bits, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what the timed path handed its caller in the last step, as .npy files that two builds of the
+    project can be compared with element for element (the inputs are seeded, so the same arguments give the same
+    frames).  starts.npy: every frame's sync offset (float64; exact, the offsets are far below 2^53).  bits.npy: the
+    packed decoded bytes (float32, 0..255) of the frames listed in bits_rows.npy (float64 frame indices): every frame
+    when they fit in `max_bytes` with the rest, else a fixed seeded sample of them in ascending order."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = starts.cpu().numpy().astype(np.float64)
+    F, B = bits.shape
+    n = int(max(1, min(F, (max_bytes - st.nbytes) // (8 + 4 * B))))
+    rows = np.arange(F) if n == F else np.sort(np.random.RandomState(DUMP_SEED).choice(F, n, replace=False))
+    sample = bits.index_select(0, torch.from_numpy(rows).to(bits.device)).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "starts.npy"), st)
+    np.save(os.path.join(out_dir, "bits_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "bits.npy"), sample)
 
 
 class PowerSampler:
@@ -725,6 +751,11 @@ def main():
     ap.add_argument("--stride", type=int, default=78720)
     ap.add_argument("--window", type=int, default=320)
     ap.add_argument("--chunks", type=int, default=8, help="N>1: pieces the batch is cut into to overlap the all-gather")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure everything else the line can carry (power, secondary legs, "
+                         "copy bandwidth, CPU baselines; N>1: the single-gather and no-collective variants)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sync offsets and decoded bits (rank 0) to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-power", action="store_true", help="skip the 2 s sustained-power probe after the timed region")
@@ -755,7 +786,7 @@ def main():
         args.frames = 65536 if args.gpus == 1 else 131072
 
     pool = cores = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu and not args.rehearse_chunked:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu and not args.rehearse_chunked:
         pool, cores = make_cpu_pool()                     # before the GPU is initialised (see make_cpu_pool)
     from gf3_audio_modem_amd import dist as gd
     rank, world, local = gd.init_from_env()
@@ -888,6 +919,8 @@ def main():
     run = Run(args.chunks)
     dt, evs = run.timed(args.warmup, args.steps)
     bit_errors, sync_ok, gather_ok = run.verify()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.starts_all, run.gathered if run.gathered is not None else run.bits)
     chunks, Fc = run.chunks, run.Fc
     step = run.step
 
@@ -919,7 +952,7 @@ def main():
         return rec, w
 
     power_w, sustained = None, None
-    if not args.no_power:
+    if args.full and not args.no_power:
         # the same step over a window a hundred times longer than a 20-step timed region: a second reading of `value`,
         # not a replacement for it
         sustained, power_w = sustained_probe(run, 2.0, dt / args.steps * 1e3)
@@ -931,7 +964,7 @@ def main():
     # rank 0's sustained package power beside its time, and the gather's cost is given per rank (max and min over ranks
     # of that rank's own seconds with the collective minus without).
     single = no_gather = gather_cost = None
-    if multi:
+    if multi and args.full:
         t_chunked_local = run.t_local
 
         def variant(chunks_v, gather):
@@ -994,7 +1027,7 @@ def main():
             traffic, pmc = None, {}
     extra = {}
     power_obj = None
-    if world == 1 and not multi:
+    if world == 1 and not multi and args.full:
         if not args.no_power:
             st_all = run.starts_all
             power_obj = power_roofline(local, lambda: eng.demod_frames(big, st_all, out_bits=run.bits), t_demod, F, lib_src16)
@@ -1063,7 +1096,7 @@ def main():
         out.update(extra)
         if "hbm_copy_measured" in out:
             add_copy_fraction(out, out["hbm_copy_measured"]["GB_per_s"])
-        if world == 1 and not multi and not args.no_cpu:
+        if world == 1 and not multi and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(cfg, big, payload, args.window, args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
             if pool is not None:

@@ -732,13 +732,13 @@ def test_integration_md_ctypes_stub_runs(capsys):
 
 
 def test_bench_json_contract(capsys, monkeypatch):
-    """bench.py's one JSON line (small batch, in-process): the contract keys, BER 0, exact sync, a roofline object
+    """bench.py --full's one JSON line (small batch, in-process): the contract keys, BER 0, exact sync, a roofline object
     whose fraction is achieved/peak, and no CPU leg when --no-cpu is given."""
     import importlib.util, json, os, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("gf3_bench", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--frames", "1024", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-power"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--frames", "1024", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-power"])
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     bench.main()
     line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1]
@@ -753,6 +753,38 @@ def test_bench_json_contract(capsys, monkeypatch):
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
     assert d["ber"] == 0.0 and d["sync_exact"] is True and "cpu_baseline" not in d
     assert abs(d["value"] - 1024 * 78720 * 2 / (d["ms_per_step"] * 2e-3)) <= 1e-6 * d["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, capsys, monkeypatch):
+    """bench.py without --full (small batch, in-process): the headline line alone -- no secondary leg, power probe or CPU
+    baseline -- over exactly --steps timed steps; --dump-outputs writes what the last timed step computed: every sync
+    offset and decoded byte equal the seeded workload's own offsets and payload, and another step count writes the same."""
+    import argparse, importlib.util, json, os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("gf3_bench_plain", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    dumps = []
+    for steps in (3, 2):
+        out_dir = tmp_path / f"steps{steps}"
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--frames", "1024", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out_dir)])
+        bench.main()
+        d = json.loads([l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["ber"] == 0.0 and d["sync_exact"] is True
+        assert abs(d["value"] - 1024 * 78720 * steps / (d["ms_per_step"] * steps * 1e-3)) <= 1e-6 * d["value"]
+        for k in ("cpu_baseline", "cpu_baseline_all_cores", "cpu_baseline_config1", "screened_sync", "pcm16_storage",
+                  "roofline_demod_16qam", "roofline_rfft", "roofline_demod_by_N", "roofline_stream_sync", "h2d",
+                  "final_system_test", "hbm_copy_measured"):
+            assert k not in d, k
+        assert d["sustained_2s"] is None and d["roofline"]["power"] is None
+        dumps.append({k: np.load(out_dir / f"{k}.npy") for k in ("starts", "bits_rows", "bits")})
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    eng, cfg, big, payload, gaps = bench.build_workload(argparse.Namespace(frames=1024, stride=78720, window=320), 0)
+    exp = torch.arange(1024, device="cuda", dtype=torch.int64) * 78720 + gaps + cfg.chirp_length
+    got = dumps[0]
+    assert np.array_equal(got["bits_rows"], np.arange(1024))
+    assert np.array_equal(got["starts"], exp.cpu().numpy().astype(np.float64))
+    assert np.array_equal(got["bits"], payload.cpu().numpy().astype(np.float32))
 
 
 @pytest.mark.parametrize("seed,tail", [(1, 500), (2, 1), (3, 4000)])

@@ -235,6 +235,36 @@ def test_bench_cpu_baseline_inputs_decode_to_their_payload():
     assert len(out["starts"]) == 4 and np.mean(out["bits"] != payload) < 0.01
 
 
+def test_bench_dump_outputs_is_exact_bounded_and_fixed(tmp_path):
+    """bench.py --dump-outputs on CPU tensors of the headline's shapes (65 536 frames of 4 090 packed bytes): float
+    files under 64 MB in all, every offset and every sampled byte exact, and the same sample on every call; a batch
+    that fits is written whole."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("gf3_bench_dump", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    gen = torch.Generator().manual_seed(7)
+    F, B = 65536, 4090
+    starts = torch.arange(F, dtype=torch.int64) * 78720 + torch.randint(0, 300, (F,), generator=gen) + 5 * 4608
+    bits = torch.randint(0, 256, (F, B), dtype=torch.uint8, generator=gen)
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), starts, bits)
+        got = {k: np.load(tmp_path / d / f"{k}.npy") for k in ("starts", "bits_rows", "bits")}
+        assert sum(os.path.getsize(tmp_path / d / f"{k}.npy") for k in got) <= 64_000_000
+        assert got["starts"].dtype == np.float64 and got["bits_rows"].dtype == np.float64 and got["bits"].dtype == np.float32
+        rows = got["bits_rows"].astype(np.int64)
+        assert 1000 < len(rows) < F and np.all(np.diff(rows) > 0) and np.array_equal(rows, got["bits_rows"])
+        assert np.array_equal(got["starts"].astype(np.int64), starts.numpy())
+        assert np.array_equal(got["bits"].astype(np.uint8), bits.numpy()[rows]) and np.array_equal(got["bits"], bits.numpy()[rows])
+        outs.append(got)
+    assert all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])
+    bench.dump_outputs(str(tmp_path / "small"), starts[:64], bits[:64])
+    assert np.array_equal(np.load(tmp_path / "small" / "bits_rows.npy"), np.arange(64))
+    assert np.array_equal(np.load(tmp_path / "small" / "bits.npy"), bits[:64].numpy())
+
+
 def test_facade_file_framing_matches_the_reference_record(tmp_path, monkeypatch, capsys):
     """save_file / load_file of the drop-in module are host-side NumPy (OFDM.py:756-794): on the reference's decoded bits
     of the real recording (g6) save_file prints, returns and writes what the unmodified reference did (recorded by

@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 for pass in 1 2; do
   for lib in "$@"; do
     name=$(basename "$lib" .so)
-    GF3_LIB="$lib" timeout -k 10 300 python bench.py --no-cpu --no-config5 --no-stream --no-power > "$OUT/$name.$pass.json" 2> "$OUT/$name.$pass.err" || { echo "FAILED $name pass $pass"; tail -5 "$OUT/$name.$pass.err"; exit 1; }
+    GF3_LIB="$lib" timeout -k 10 300 python bench.py --full --no-cpu --no-config5 --no-stream --no-power > "$OUT/$name.$pass.json" 2> "$OUT/$name.$pass.err" || { echo "FAILED $name pass $pass"; tail -5 "$OUT/$name.$pass.err"; exit 1; }
     python - "$OUT/$name.$pass.json" "$name.$pass" <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))

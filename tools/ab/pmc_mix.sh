@@ -6,8 +6,8 @@ rocprofv3 -L > $OUT/counters.txt 2>&1
 grep -o "SQ_INSTS_[A-Z0-9_]*" $OUT/counters.txt | sort -u > $OUT/sq_insts.txt
 A="SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT SQ_INSTS_SALU"
 B="SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32"
-timeout -k 10 240 rocprofv3 --pmc $A --output-format csv -d $OUT/a -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-power --no-config5 --no-stream > $OUT/a.log 2>&1; echo "a rc=$?"
-timeout -k 10 240 rocprofv3 --pmc $B --output-format csv -d $OUT/b -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu --no-power --no-config5 --no-stream > $OUT/b.log 2>&1; echo "b rc=$?"
+timeout -k 10 240 rocprofv3 --pmc $A --output-format csv -d $OUT/a -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-power --no-config5 --no-stream > $OUT/a.log 2>&1; echo "a rc=$?"
+timeout -k 10 240 rocprofv3 --pmc $B --output-format csv -d $OUT/b -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu --no-power --no-config5 --no-stream > $OUT/b.log 2>&1; echo "b rc=$?"
 python3 - "$OUT" <<'P'
 import collections, csv, glob, os, sys
 acc = collections.defaultdict(lambda: collections.defaultdict(list))

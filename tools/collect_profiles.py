@@ -3,7 +3,7 @@
 
     python tools/collect_profiles.py --tag r02
 
-Writes profiles/<tag>_kernel_stats.csv (rocprofv3 --kernel-trace of `python3 bench.py --no-cpu --no-power`: the --stats
+Writes profiles/<tag>_kernel_stats.csv (rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu --no-power`: the --stats
 summary recomputed PER (kernel, grid) from the trace, because one kernel name is launched at several sizes by the bench's
 legs and a pooled mean cannot be compared with any one leg's figure),
 profiles/<tag>_bench.json (the bench line of the same run set), profiles/<tag>_pmc.json (HBM bytes per launch from the
@@ -84,7 +84,7 @@ def instruction_mix(tag, sha16):
                     acc[f"{k} grid={int(row['Grid_Size'])}"][row["Counter_Name"]].append(float(row["Counter_Value"]))
     if not acc:
         return
-    out = {"_comment": "rocprofv3 --pmc passes (two, 8 SQ counters each) of `python3 bench.py --steps 2 --warmup 1 --no-cpu --no-power` (hot-path "
+    out = {"_comment": "rocprofv3 --pmc passes (two, 8 SQ counters each) of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-power` (hot-path "
                        "legs only): wave-instructions per launch by class, mean over the launches of the run; tools/profile_round.sh",
            "source_sha16": sha16,
            "kernels": {k: {c: sum(v) / len(v) for c, v in sorted(cs.items())} for k, cs in sorted(acc.items())}}
@@ -145,7 +145,7 @@ def main():
             ent["clock_GHz_under_pmc"] = g["GRBM_GUI_ACTIVE"][0] / 8 / (g["GRBM_GUI_ACTIVE"][1] * 1e-6) / 1e9
             ent["lds_bank_conflict_share_of_lds_cycles"] = g["SQ_LDS_BANK_CONFLICT"][0] / max(1.0, g["SQ_LDS_IDX_ACTIVE"][0])
         shares[f"{k} grid={grid}"] = ent
-    out = {"_comment": "rocprofv3 --pmc passes of `python3 bench.py --steps 2 --warmup 1 --no-cpu --no-power` (FETCH_SIZE, WRITE_SIZE: full bench; "
+    out = {"_comment": "rocprofv3 --pmc passes of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-power` (FETCH_SIZE, WRITE_SIZE: full bench; "
                        "SQ and GRBM: hot-path legs only). KB counters; FETCH_SIZE calibrated on rfft_kernel<2048,f32> over 2^28 samples in the "
                        "same run (MI355X_MICROARCH.md: gfx950 reports half of wide streaming reads); narrower access patterns "
                        "(scr_ols_kernel's 8-byte sample pairs) are corrected by the same factor and are upper bounds. Produced by tools/collect_profiles.py.",
