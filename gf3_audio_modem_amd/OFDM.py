@@ -26,6 +26,19 @@ __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 _NP2T = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32,
          np.dtype("int16"): torch.int16, np.dtype("uint8"): torch.uint8}
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "known_bits.npz")
+# channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), n = 1536
+QCLDPC_ENCODINGS = {"QCLDPC-1/2": "1/2", "QCLDPC-2/3": "2/3", "QCLDPC-3/4": "3/4", "QCLDPC-5/6": "5/6"}
+_codes = {}
+
+
+def _qcldpc_code(rate, device=None):
+    """One QCLDPC object per (rate, device), made on first use (the code tables are uploaded once)."""
+    from .ldpc import QCLDPC
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    code = _codes.get((rate, dev))
+    if code is None:
+        code = _codes[(rate, dev)] = QCLDPC(rate, dev)
+    return code
 
 
 def _load_known_sequence(count):
@@ -73,6 +86,7 @@ class CamG:
         self.data_bits_per_symbol = self.data_carriers_per_symbol * self.mu
         self.bits_per_symbol = self.K * self.mu
         self.known_sequence = _load_known_sequence(self.ofdm_symbol_size)
+        self.ldpc_max_iter = 50                 # decoder iterations at most (encodings "QCLDPC-*")
         self._engines = {}
 
     def __repr__(self):
@@ -108,6 +122,10 @@ class CamG:
         """OFDM.py:106-109 (replica built inside gf3_ctx_create)."""
         return self._engine().chirp_replica()
 
+    def _qcldpc_rate(self):
+        """Rate of a "QCLDPC-*" encoding, else None."""
+        return QCLDPC_ENCODINGS.get(self.encoding)
+
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
         pts, tb = self._tables()
@@ -133,6 +151,13 @@ class transmitter(CamG):
         if self.encoding == "LDPC":
             raise NotImplementedError("LDPC encoding is out of scope (pyldpc; marked broken in the reference, OFDM.py:21)")
         bits = np.asarray(bits)
+        rate = self._qcldpc_rate()
+        if rate is not None:
+            # QC-LDPC (not in the reference): zero padding to whole codewords, encoded on the GPU; the codewords then
+            # fill packets like uncoded bits (the coin-flip fill below)
+            code = _qcldpc_code(rate)
+            msg = np.concatenate([bits.astype(np.uint8) & 1, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
+            bits = code.encode(torch.from_numpy(msg)).cpu().numpy().reshape(-1).astype(np.int64)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
             mask = np.resize(np.asarray(self.known_sequence[:self.data_bits_per_symbol]), bits.shape)
             bits = bits ^ mask.astype(bits.dtype)
@@ -334,6 +359,14 @@ class receiver(transmitter):
     def decode(self, bits_encoded):
         if self.encoding == "LDPC":
             raise NotImplementedError("LDPC decoding is out of scope (pyldpc; marked broken in the reference, OFDM.py:21)")
+        rate = self._qcldpc_rate()
+        if rate is not None:
+            # hard-input decoding (LLR = +-1) of the whole codewords in the stream; receive() decodes from soft values
+            code = _qcldpc_code(rate)
+            b = np.asarray(bits_encoded)
+            n_cw = len(b) // code.n
+            llr = 1.0 - 2.0 * torch.as_tensor(np.asarray(b[: n_cw * code.n], dtype=np.float32))
+            return code.decode(llr, max_iter=self.ldpc_max_iter).cpu().numpy().reshape(-1).astype(np.int64)
         if self.encoding == "XOR":
             n = len(bits_encoded)
             known = torch.as_tensor(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.int64))
@@ -364,7 +397,11 @@ class receiver(transmitter):
         # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
         # stay on the one-shot path.
         chunk = getattr(self, "host_chunk_samples", None)
+        rate = self._qcldpc_rate()
         if not graph_output and (chunk or len(r) > (1 << 27)):
+            if rate is not None:
+                raise NotImplementedError(f"encoding {self.encoding!r}: the piece-wise host path of long recordings (or "
+                                          "host_chunk_samples) has no soft-decision decoding; receive shorter recordings")
             return self._receive_chunked(eng, r, int(chunk or (1 << 25)))
         x = eng._samples(r)
         peaks = eng.sync_stream(x)
@@ -372,9 +409,16 @@ class receiver(transmitter):
         self.no_packets = int(starts.numel())
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
-        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ())
+        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ("eq",) if rate is not None else ())
         o = eng.demod_frames(x, starts, want=want)
-        bits_t = self._decode_packed(eng, o["bits"])
+        if rate is not None:
+            # soft path: CSI-weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
+            code = _qcldpc_code(rate, eng.device)
+            llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
+            n_cw = llr.numel() // code.n
+            bits_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter).reshape(-1)
+        else:
+            bits_t = self._decode_packed(eng, o["bits"])
         # everything else the host needs, in ONE small copy behind the kernels: first packet's Hs / He, the slopes, and the
         # ragged-packet flag (a packet that runs past the recording: the reference's get_symbols fails on it)
         K, F = self.K, self.no_packets
@@ -386,7 +430,7 @@ class receiver(transmitter):
         if host[-1] != 0:                                       # (before anything is printed: get_symbols fails first in the reference)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
-        bits = bits_t.numpy()
+        bits = bits_t.cpu().numpy().astype(np.int64) if rate is not None else bits_t.numpy()
         h = host.numpy()
         Hest_start0, Hest_end0 = h[: 2 * K].view(np.complex128).copy(), h[2 * K: 4 * K].view(np.complex128).copy()
         self._last_slope = h[4 * K: 4 * K + F].copy()

@@ -5,8 +5,10 @@ Layout
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
   engine.py  Engine: torch-tensor front end of the ABI (device memory + streams only)
   OFDM.py    drop-in mirror of the reference's `receiver` class (same names/shapes)
+  ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)
 """
 from .engine import Engine, RxConfig, qpsk_table, square_qam_table  # noqa: F401
+from .ldpc import QCLDPC  # noqa: F401
 
 __version__ = "0.1.0"

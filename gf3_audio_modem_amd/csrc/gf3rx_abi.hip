@@ -975,3 +975,12 @@ extern "C" int gf3_soft_demap(gf3_ctx* c, const void* d_sym, int64_t n, double n
     if (!c || !d_sym || !d_llr || n < 0 || !(noise_var > 0)) return fail(c, GF3_EINVAL, "gf3_soft_demap: bad argument");
     return run_demap(c, d_sym, n, nullptr, nullptr, d_llr, noise_var, stream);
 }
+extern "C" int gf3_soft_demap_csi(gf3_ctx* c, const void* d_eq, const void* d_Hs, const void* d_He, int64_t F, float* d_llr, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_eq || !d_Hs || !d_He || !d_llr || F < 0) return fail(c, GF3_EINVAL, "gf3_soft_demap_csi: bad argument");
+    const int rc = run_demap(c, d_eq, F * c->cfg.D * c->cfg.C, nullptr, nullptr, d_llr, 1.0, stream);   // max-log, sigma^2 = 1
+    if (rc != GF3_OK) return rc;
+    HIPCHK(c, launch_csi_weight(c, d_llr, d_Hs, d_He, F, (hipStream_t)stream));
+    return GF3_OK;
+}

@@ -9,6 +9,7 @@
 //   gf3rx_fscreen.hip        corr_screen_kernel: the opt-in fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
 //   gf3rx_stamp.cpp          the build stamp (source hash), recompiled on every change
 //   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide
+//   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
 //   gf3rx_abi.hip            context, plans, the remaining entry points, demappers, zero forcing, Schmidl-Cox
 #pragma once
 #include <hip/hip_runtime.h>
@@ -287,3 +288,5 @@ hipError_t run_spec_ols(const CorrPlan& pl, OlsArgs a, int64_t nwin, int64_t nbl
 // gf3rx_screen.hip
 hipError_t launch_screen(const gf3_ctx* c, ScreenArgs a, bool general, hipStream_t st);
 hipError_t launch_refine(const gf3_ctx* c, const RefineArgs& a, int64_t cap_cells, hipStream_t st);
+// gf3rx_ldpc.hip: LLR *= |H^|^2 (gf3_soft_demap_csi, after the soft demapper)
+hipError_t launch_csi_weight(const gf3_ctx* c, float* d_llr, const void* d_Hs, const void* d_He, int64_t F, hipStream_t st);

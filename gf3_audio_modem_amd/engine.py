@@ -433,6 +433,27 @@ class Engine:
         self._check(self.lib.gf3_soft_demap(self._h, _ptr(sym), sym.numel(), float(noise_var), _ptr(llr), self._stream()))
         return llr
 
+    def soft_demap_csi(self, eq, Hs, He, out=None):
+        """Channel-state-weighted max-log LLRs (gf3_soft_demap_csi): maxlog(eq; sigma^2 = 1) * |H^_{f,l,k}|^2 with the
+        reference's magnitude model |Hs| + (|He| - |Hs|)(l + P/2)/(D + P), from demod_frames' 'eq' [F*D, C] and 'Hs' /
+        'He' [F, K].  -> float32 [F*D*C*mu] in the reference's bit order (packet -> symbol -> carrier -> bit)."""
+        cfg = self.cfg
+        eq = torch.as_tensor(eq, dtype=torch.complex128).to(self.device).contiguous()
+        Hs = torch.as_tensor(Hs, dtype=torch.complex128).to(self.device).contiguous()
+        He = torch.as_tensor(He, dtype=torch.complex128).to(self.device).contiguous()
+        F = Hs.numel() // cfg.K
+        if Hs.numel() != F * cfg.K or He.numel() != Hs.numel() or eq.numel() != F * cfg.D * cfg.C:
+            raise ValueError("soft_demap_csi: need Hs, He [F, K] and eq [F*D, C]")
+        n = F * cfg.D * cfg.C * cfg.mu
+        if out is None:
+            llr = self._new((n,), torch.float32)
+        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
+        else:
+            llr = out
+        self._check(self.lib.gf3_soft_demap_csi(self._h, _ptr(eq), _ptr(Hs), _ptr(He), F, _ptr(llr), self._stream()))
+        return llr
+
     # ------------------------------------------------------------------ host ingest (streams from host memory / longer than HBM)
     def receive_host(self, samples, chunk_samples=1 << 24, list_cap=None):
         """chirp sync + demodulation (the arithmetic of receiver.receive, OFDM.py:581-603) of a stream that lives in

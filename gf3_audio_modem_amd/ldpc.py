@@ -1,0 +1,104 @@
+"""Quasi-cyclic LDPC forward error correction on the GPU (gf3_ldpc_* of include/gf3rx.h).
+
+The code family is the project's own (tools/make_qcldpc.py -> data/qcldpc_z64.json): lifting size Z = 64, 24 block
+columns, n = 1536 coded bits, rates 1/2, 2/3, 3/4, 5/6 (k = 768, 1024, 1152, 1280), dual-diagonal parity part.
+Encoding and the layered normalised min-sum decoder run in hand-written HIP (csrc/gf3rx_ldpc.hip); there is no host
+implementation to fall back to.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import Gf3Error
+
+_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "qcldpc_z64.json")
+RATES = ("1/2", "2/3", "3/4", "5/6")
+Z = 64
+
+
+def shift_table(rate):
+    """int16 [mb, 24] shift table of one rate (-1 = zero block)."""
+    if rate not in RATES:
+        raise ValueError(f"unknown QC-LDPC rate {rate!r} (one of {', '.join(RATES)})")
+    with open(_DATA) as f:
+        return np.array(json.load(f)["rates"][rate], dtype=np.int16)
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class QCLDPC:
+    """One code of the family on one GPU.  Immutable; encode / decode are asynchronous on the current stream.
+
+    QCLDPC(rate, device=None), or QCLDPC(shifts=<int16 [mb, nb] table>) for a code of one's own (Z = 64)."""
+
+    def __init__(self, rate="1/2", device=None, shifts=None):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise Gf3Error("no GPU visible: QC-LDPC coding has no CPU fallback")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.rate = None if shifts is not None else rate
+        sh = np.ascontiguousarray(shift_table(rate) if shifts is None else shifts, dtype=np.int16)
+        if sh.ndim != 2:
+            raise ValueError("shifts must be a 2-D table [mb, nb]")
+        self.shifts = sh
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.gf3_ldpc_create(sh.shape[0], sh.shape[1], Z, sh.ctypes.data_as(C.c_void_p), C.byref(h))
+        if rc != 0:
+            msg = self.lib.gf3_last_error(None).decode()
+            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(msg)
+        self._h = h
+        self.n = int(self.lib.gf3_ldpc_n(h))
+        self.k = int(self.lib.gf3_ldpc_k(h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.gf3_ldpc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = self.lib.gf3_last_error(None).decode()
+            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(f"gf3rx error {rc}: {msg}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _rows(self, x, dtype, width, what):
+        x = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
+        if x.numel() % width:
+            raise ValueError(f"{what}: {x.numel()} values are not a whole number of rows of {width}")
+        return x.reshape(-1, width)
+
+    def encode(self, msg):
+        """[n_cw, k] (or flat n_cw*k) 0/1 message bits -> uint8 [n_cw, n] codewords on the device, systematic first."""
+        m = self._rows(msg, torch.uint8, self.k, "encode")
+        cw = torch.empty((m.shape[0], self.n), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.gf3_ldpc_encode(self._h, _ptr(m), m.shape[0], _ptr(cw), self._stream()))
+        return cw
+
+    def decode(self, llr, max_iter=50, want_app=False, want_iters=False):
+        """[n_cw, n] (or flat) float32 LLRs (> 0 <=> bit 0) -> uint8 [n_cw, k] decisions; with want_app / want_iters
+        also the float32 [n_cw, n] APP LLRs and the int32 [n_cw] iteration counts (-max_iter: not converged)."""
+        x = self._rows(llr, torch.float32, self.n, "decode")
+        F = x.shape[0]
+        bits = torch.empty((F, self.k), dtype=torch.uint8, device=self.device)
+        app = torch.empty((F, self.n), dtype=torch.float32, device=self.device) if want_app else None
+        its = torch.empty((F,), dtype=torch.int32, device=self.device) if want_iters else None
+        self._check(self.lib.gf3_ldpc_decode(self._h, _ptr(x), F, int(max_iter), _ptr(bits), _ptr(app), _ptr(its),
+                                             self._stream()))
+        if not (want_app or want_iters):
+            return bits
+        return (bits,) + ((app,) if want_app else ()) + ((its,) if want_iters else ())

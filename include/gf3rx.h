@@ -354,6 +354,50 @@ int gf3_unpack_bits(gf3_ctx *ctx, const uint8_t *d_bits_packed, int64_t F, const
 int gf3_soft_demap(gf3_ctx *ctx, const void *d_sym_c128, int64_t n,
                    double noise_var, float *d_llr_f32, void *stream);
 
+/*
+ * Channel-state-weighted soft demapping (not in the reference): the max-log LLRs of gf3_soft_demap with noise_var = 1,
+ * each multiplied by |H^_{f,l,k}|^2, the squared magnitude of the reference's per-symbol channel model
+ * |Hs| + (|He| - |Hs|) (l + P/2) / (D + P) (OFDM.py:469) -- the reliability of carrier k of data symbol l after single-tap
+ * zero forcing.  Hest is not needed: the weight comes from the pilot estimates directly.  Normalised min-sum decoding is
+ * invariant to one global LLR scale, so no noise-variance estimate enters.
+ *   d_eq_c128 [F*D, C] equalised data-carrier symbols (gf3_demod_frames' d_eq)
+ *   d_Hs_c128, d_He_c128 [F, K] start / end pilot estimates (gf3_demod_frames' d_Hs / d_He)
+ *   d_llr_f32 [F*D*C*mu] in the reference's bit order (packet -> symbol -> data carrier -> bit); LLR > 0 <=> bit 0
+ */
+int gf3_soft_demap_csi(gf3_ctx *ctx, const void *d_eq_c128, const void *d_Hs_c128, const void *d_He_c128,
+                       int64_t F, float *d_llr_f32, void *stream);
+
+/*
+ * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64; the
+ * shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, 64) for the circulant whose
+ * row z has its one in column (z + s) mod 64.  Block columns 0 .. nb-mb-1 carry the message (systematic part), the
+ * last mb the parity; codeword bit j*64 + t is bit t of block column j.  n = 64 nb, k = 64 (nb - mb).  The project's
+ * own family (rates 1/2, 2/3, 3/4, 5/6 at n = 1536) is gf3_audio_modem_amd/data/qcldpc_z64.json.
+ *   - gf3_ldpc_create validates Z == 64, 0 < mb < nb <= 32, every shift in [-1, 64) and at least two non-zero blocks
+ *     per block row, and uploads the table to the current device.  It records whether the parity part is
+ *     dual-diagonal (first parity column shifts x, 0, x at rows 0, some middle row and mb-1; every other parity
+ *     column shift 0 at rows c-1 and c): only then can gf3_ldpc_encode encode (GF3_EINVAL otherwise); any valid
+ *     code decodes.  Error text of create / encode / decode: gf3_last_error(NULL), per calling thread.
+ *   - a code object is immutable: share it across threads and streams freely.  Encode and decode are asynchronous on
+ *     `stream` and run on the device the code was created on.
+ *   - gf3_ldpc_encode: d_msg [n_cw, k] uint8 0/1 -> d_cw [n_cw, n] uint8 0/1, systematic first.
+ *   - gf3_ldpc_decode: layered normalised min-sum (alpha = 0.75; block rows in order, within a row the non-zero
+ *     blocks in column order), one wavefront per codeword, stopping after the first full iteration whose decisions
+ *     satisfy every check, or after max_iter >= 1 iterations.  d_llr [n_cw, n] f32, LLR > 0 <=> bit 0; non-finite
+ *     LLRs are outside the contract.  d_bits [n_cw, k] uint8 decisions of the systematic part (1 <=> APP < 0);
+ *     d_app [n_cw, n] f32 a-posteriori LLRs or NULL; d_iters [n_cw] int32 or NULL: iterations used, -max_iter when the
+ *     syndrome is still non-zero after max_iter.  The float32 arithmetic is fixed (no contraction): results are
+ *     bit-identical to a float32 restatement of the same schedule.
+ */
+typedef struct gf3_ldpc gf3_ldpc;
+int gf3_ldpc_create(int32_t mb, int32_t nb, int32_t Z, const int16_t *h_shifts, gf3_ldpc **out);
+void gf3_ldpc_destroy(gf3_ldpc *code);
+int32_t gf3_ldpc_n(const gf3_ldpc *code);
+int32_t gf3_ldpc_k(const gf3_ldpc *code);
+int gf3_ldpc_encode(const gf3_ldpc *code, const uint8_t *d_msg, int64_t n_cw, uint8_t *d_cw, void *stream);
+int gf3_ldpc_decode(const gf3_ldpc *code, const float *d_llr, int64_t n_cw, int32_t max_iter,
+                    uint8_t *d_bits, float *d_app_or_null, int32_t *d_iters_or_null, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
