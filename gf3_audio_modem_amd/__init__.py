@@ -4,6 +4,7 @@ Layout
   csrc/      hand-written HIP kernels + the C ABI (include/gf3rx.h) -> lib/libgf3rx.so
   _lib.py    ctypes binding of that ABI (fails loudly when the library is missing)
   engine.py  Engine: torch-tensor front end of the ABI (device memory + streams only)
+  ingest.py  Engine.receive_host: a stream in host memory, piece by piece, with the global-maximum rule kept exact
   OFDM.py    drop-in mirror of the reference's `receiver` class (same names/shapes)
   ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)

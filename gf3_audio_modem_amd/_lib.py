@@ -12,6 +12,11 @@ c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
 
 
+def ptr(t):
+    """A tensor's device (or host) address as the ABI takes it; None stays NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class Gf3Config(C.Structure):
     _fields_ = [
         ("N", C.c_int32), ("CP", C.c_int32), ("P", C.c_int32), ("D", C.c_int32), ("Lc", C.c_int32),

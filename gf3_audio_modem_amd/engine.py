@@ -15,7 +15,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ingest
+from .ingest import DIRECT_PIECE_BYTES, host_pieces  # noqa: F401  (the cut of a host stream, importable from here as before)
 
 _TORCH_DT = {_lib.DT_F64: torch.float64, _lib.DT_F32: torch.float32,
              _lib.DT_I16: torch.int16, _lib.DT_U8: torch.uint8}
@@ -105,32 +106,7 @@ class Gf3Error(RuntimeError):
     pass
 
 
-DIRECT_PIECE_BYTES = 128 << 20      # from this size on the runtime pins a pageable source on the fly (its GPU_PINNED_MIN_XFER_SIZE)
-
-
-def host_pieces(n, chunk_samples, Lc, L):
-    """How Engine.receive_host cuts a stream of n samples (chirp length Lc, packet body L = M*S samples): a list of
-    pieces, each dict(lo, hi: the NEW samples [lo, hi) it brings; base: stream index of the first sample of its device
-    buffer, which starts with the last `carry` = Lc + L + 8 samples of the previous piece; n_buf; g_lo, g_hi: the lags
-    [g_lo, g_hi) of the stream's full convolution P (length n + Lc - 1) it owns).  Every lag 1 .. n+Lc-3 -- the p1 of
-    every zeros-index of OFDM.py:360 -- is owned by exactly one piece, with its Lc taps and both neighbours inside that
-    piece's buffer (or beyond the stream's true ends, where the convolution's zero extension is the reference's own).
-    Pure arithmetic: tested on the CPU (tests/test_abi_cpu.py)."""
-    carry = Lc + L + 8
-    H = max(int(chunk_samples), 2 * carry)
-    k = -(-n // H)
-    plen = n + Lc - 1
-    out = []
-    for c in range(k):
-        lo, hi = c * H, min(n, (c + 1) * H)
-        ce = min(carry, lo)
-        out.append(dict(lo=lo, hi=hi, base=lo - ce, n_buf=ce + hi - lo, g_lo=1 if c == 0 else lo - 1,
-                        g_hi=plen - 1 if c == k - 1 else hi - 1))
-    return out, H, carry
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 class Engine:
@@ -178,7 +154,8 @@ class Engine:
         self.max_window = int(self.lib.gf3_sync_max_window(h))
 
     def close(self):
-        self._tls = threading.local()                     # (drops the calling thread's cached ingest buffers)
+        ingest.release(self)
+        self._tls = threading.local()
         if getattr(self, "_h", None):
             self.lib.gf3_ctx_destroy(self._h)
             self._h = None
@@ -481,287 +458,12 @@ class Engine:
         (raised to two packets if smaller).  Returns dict(peaks int64 [n_det] (device), bits uint8 [n_det - 1,
         bytes_per_frame] (device, packed), info).  Raises ValueError where the reference fails (fewer than two detections;
         a packet that runs past the end of the stream)."""
-        import time
-        t_start = time.perf_counter()
-        cfg = self.cfg
-        if isinstance(samples, torch.Tensor):
-            if samples.is_cuda:
-                raise ValueError("receive_host takes host memory; use sync_stream / demod_frames for device tensors")
-            x = samples.reshape(-1)
-            if x.dtype != cfg.in_dtype:
-                x = x.to(cfg.in_dtype)
-        else:
-            a = np.asarray(samples).reshape(-1)
-            want = torch.empty(0, dtype=cfg.in_dtype).numpy().dtype
-            b = np.ascontiguousarray(a if a.dtype == want else a.astype(want))
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")                    # (torch warns when it wraps a non-writable array; it is only read)
-                x = torch.from_numpy(b)
-        if x.numel() < 3:
-            raise ValueError("stream too short")
-        try:
-            return self._receive_host(x, x.is_pinned(), chunk_samples, list_cap, t_start)
-        except BaseException:
-            held = getattr(self._tls, "ingest", None) or {}
-            for fut in list(held.pop("pending", [])):              # copies still being made on a helper thread
-                try:
-                    fut.result()
-                except Exception:
-                    pass
-            torch.cuda.synchronize(self.device)                    # nothing of the call is in flight when its buffers are let go
-            raise
-
-    def _receive_host(self, x, pinned_in, chunk_samples, list_cap, t_start):
-        import time
-        cfg = self.cfg
-        n = x.numel()
-        Lc, L = cfg.chirp_length, cfg.M * cfg.S
-        # Pageable memory, a large stream: pieces of at least 128 MiB, copied by the runtime itself.  From that size on a plain
-        # copy from pageable memory is pinned by the runtime on the fly and runs at the DMA rate (55 GB/s measured; below
-        # it, it is staged at 13-15 GB/s) -- the path every large host-to-device copy of every program takes.  Such a copy
-        # blocks its caller, so a copy thread makes it while the calling thread runs the previous piece's kernels.
-        direct = False
-        if not pinned_in and n * x.element_size() >= DIRECT_PIECE_BYTES + 65536:
-            direct = True
-            min_piece = -(-(DIRECT_PIECE_BYTES + 65536) // x.element_size())
-            k = max(1, min(n // min_piece, -(-n // max(int(chunk_samples), 1))))     # equal pieces, none below the threshold,
-            chunk_samples = -(-n // k)                                                # no more of them than were asked for
-        pieces, H, carry = host_pieces(n, chunk_samples, Lc, L)  # carry: samples of the previous piece kept in front of a piece
-        nchunks = len(pieces)
-        plen = n + Lc - 1
-        dev = self.device
-        main = torch.cuda.current_stream(dev)
-        cap_list = int(list_cap or max(4096, 64 * (n // Lc + 2)))
-        cap_peaks = n // Lc + 8
-        nbuf = carry + min(H, n)
-        # Device buffers, workspace, pinned staging, the copy stream and its events are kept between calls (per host
-        # thread: two threads may ingest through one Engine at once) and reused while the sizes fit: a receiver that is
-        # fed one recording after another does not allocate per call.
-        staging = not pinned_in and not direct
-        key = (nbuf, cap_list, cap_peaks, bool(staging), bool(direct), cfg.in_dtype, min(3, nchunks))
-        res = getattr(self._tls, "ingest", None)
-        if res is None or res["key"] != key:
-            # (the copy stream is a HIGH-PRIORITY stream: the runtime multiplexes streams of one priority onto a handful of
-            #  hardware queues, and a copy stream that lands on the compute stream's queue serialises the upload of piece c+1
-            #  behind the kernels of piece c -- 3.2 instead of 2.3 ms per 128 MB piece, seen in the bench process once enough
-            #  other streams existed; queues of another priority level are never shared with it)
-            res = dict(key=key, copier=torch.cuda.Stream(dev, priority=-1),
-                       bufs=[self._new((nbuf,), cfg.in_dtype) for _ in range(min(2, nchunks))],
-                       stage=[torch.empty((min(H, n),), dtype=cfg.in_dtype).pin_memory() for _ in range(min(3, nchunks))] if staging else None,
-                       idx_all=self._new((cap_list,), torch.int64), val_all=self._new((cap_list, 3), torch.float64),
-                       work=self._new((int(self.lib.gf3_sync_chunk_workspace_bytes(self._h, nbuf)),), torch.uint8),
-                       peaks_dev=self._new((cap_peaks,), torch.int64),
-                       dwork=self._new((int(self.lib.gf3_sync_decide_workspace_bytes(self._h, cap_list)),), torch.uint8),
-                       rows=self._new((cap_peaks, self.bytes_per_frame), torch.uint8))
-            res["ev_copied"] = [torch.cuda.Event() for _ in res["bufs"]]
-            if direct:
-                from concurrent.futures import ThreadPoolExecutor
-                res["copy_thread"] = ThreadPoolExecutor(1)         # makes the blocking copies, so that the kernels of the previous piece run under them
-            if staging:
-                from concurrent.futures import ThreadPoolExecutor
-                res["pool"] = ThreadPoolExecutor(4)                # the four slices of one staging copy
-                res["stager"] = ThreadPoolExecutor(1)              # the staging copy of a piece, off the calling thread
-            self._tls.ingest = res
-        copier, bufs, stage, ev_copied = res["copier"], res["bufs"], res["stage"], res["ev_copied"]
-        idx_all, val_all, work, peaks_dev, dwork, rows = res["idx_all"], res["val_all"], res["work"], res["peaks_dev"], res["dwork"], res["rows"]
-        copier.wait_stream(main)                                  # (a previous call's consumers of these buffers are ordered before the new copies)
-        run_max = torch.full((2,), float("-inf"), dtype=torch.float64, device=dev)     # [maximum so far, the last piece's own maximum]
-        row_of, next_row = {}, 0                                  # zeros-index of a detection -> row of `rows` holding its packet's bits
-        segs, overflow = [], []                                   # per piece: (first entry, entries) of the kept list; pieces whose list did not fit
-        n_listed = 0
-        BIG = (1 << 62)
-        info = dict(chunks=nchunks, chunk_samples=H, overlap_samples=carry, pinned_input=bool(pinned_in),
-                    source="pinned" if pinned_in else ("pageable, copied by the runtime in large pieces" if direct else "pageable, staged"), h2d_bytes=0,
-                    second_look_chunks=0, second_look_packets=0, provisional_detections_dropped=0, full_list_pieces=0)
-
-        def geometry(c):
-            q = pieces[c]
-            return q["lo"], q["hi"], q["lo"] - q["base"], q["base"], q["g_lo"], q["g_hi"]
-
-        staged = {}                                               # piece -> future of its host-side staging copy
-        copies = {}                                               # piece -> future of its blocking copy (large pageable streams)
-
-        def stage_piece(c):
-            """pageable source, a small stream: piece c's new samples -> pinned staging buffer c % 3 (a host copy by
-            four threads).  Runs on the stager thread, TWO pieces ahead of the kernels -- under piece c - 2's kernels and
-            piece c - 1's DMA.  The buffer was last read by the DMA of piece c - 3, which the calling thread has seen
-            finish (it synchronised on piece c - 3's kernels, which waited for that DMA) before it submits this: a plain
-            host memcpy, no HIP call on this thread."""
-            lo_s, hi_s = c * H, min(n, (c + 1) * H)
-            src, dst, m = x[lo_s:hi_s], stage[c % 3], hi_s - lo_s
-            if m >= (1 << 22):                                     # four host threads: 24 GB/s on the GPU box against 4 GB/s for one
-                q = -(-m // 4)
-                list(res["pool"].map(lambda k: dst[k * q: min(m, (k + 1) * q)].copy_(src[k * q: min(m, (k + 1) * q)]), range(4)))
-            else:
-                dst[:m].copy_(src)
-
-        def issue_copy(c):
-            """host -> dev of piece c's new samples on the copy stream (after `ev_order` of the main stream)"""
-            b = c % 2
-            lo_s, hi_s = c * H, min(n, (c + 1) * H)
-            src = x[lo_s:hi_s]
-            if stage is not None:
-                staged.pop(c).result()                            # (staged while the previous piece's kernels ran)
-                src = stage[c % 3][: hi_s - lo_s]
-            info["h2d_bytes"] += (hi_s - lo_s) * x.element_size()
-            if direct:
-                # the source is pageable: the copy blocks its caller while the runtime pins and transfers the piece -- so it is
-                # made on the copy thread (stream order: the wait for `ev_order` was enqueued by the calling thread before this)
-                def job(b=b, src=src, m=hi_s - lo_s):
-                    with torch.cuda.stream(copier):
-                        bufs[b][carry: carry + m].copy_(src)
-                        ev_copied[b].record(copier)
-                copies[c] = res["copy_thread"].submit(job)
-                return
-            with torch.cuda.stream(copier):
-                bufs[b][carry: carry + (hi_s - lo_s)].copy_(src, non_blocking=True)
-                ev_copied[b].record(copier)
-
-        def sync_piece(buf, n_buf, lag_lo, lag_hi, base, idx_t, val_t, cap):
-            """-> (entries listed, or -(entries wanted) - 1 when they do not fit; the piece's own maximum)"""
-            cnt, pmax = C.c_int64(0), C.c_double(0.0)
-            rc = self.lib.gf3_sync_chunk(self._h, _ptr(buf), n_buf, lag_lo, lag_hi, base, _ptr(run_max), _ptr(idx_t), _ptr(val_t),
-                                         cap, C.byref(cnt), C.byref(pmax), _ptr(work), self._stream())
-            if rc == _lib.GF3_ERANGE:
-                return -int(cnt.value) - 1, pmax.value
-            self._check(rc)
-            return int(cnt.value), pmax.value
-
-        def decide(idx_t, val_t, k, nz):
-            cnt = C.c_int64(0)
-            self._check(self.lib.gf3_sync_decide(self._h, _ptr(idx_t), _ptr(val_t), k, _ptr(run_max), nz, _ptr(peaks_dev), cap_peaks,
-                                                 C.byref(cnt), _ptr(dwork), self._stream()))
-            return peaks_dev[: cnt.value].cpu().numpy()
-
-        info["setup_seconds"] = time.perf_counter() - t_start    # (pinned staging, device buffers, workspace: cached by torch after the first call)
-        for fut in list(res.pop("pending", [])):                   # (a previous call that ended in an exception may have left copies running)
-            try:
-                fut.result()
-            except Exception:
-                pass
-        if stage is not None:
-            for c0 in range(min(2, nchunks)):
-                staged[c0] = res["stager"].submit(stage_piece, c0)
-            res["pending"] = staged.values()
-        if direct:
-            res["pending"] = copies.values()
-        issue_copy(0)
-        for c in range(nchunks):
-            b = c % 2
-            lo_s, hi_s, ce, base, g_lo, g_hi = geometry(c)
-            if direct:
-                copies.pop(c).result()                             # (the copy thread has recorded ev_copied[b])
-            main.wait_event(ev_copied[b])
-            if ce:
-                # (the previous piece was a full one: its last `ce` new samples sit at the end of its buffer)
-                bufs[b][carry - ce: carry].copy_(bufs[1 - b][carry + H - ce: carry + H])
-            if c + 1 < nchunks:
-                ev_order = torch.cuda.Event()
-                ev_order.record(main)                              # the other buffer is free once this point is reached
-                copier.wait_event(ev_order)
-                issue_copy(c + 1)                                  # its DMA runs under this piece's kernels
-            if stage is not None and c + 2 < nchunks:
-                # ... and piece c + 2 is staged meanwhile, into the buffer piece c - 1 was copied from: that DMA is
-                # known to be finished (this thread synchronised on piece c - 1's kernels, which had waited for it)
-                staged[c + 2] = res["stager"].submit(stage_piece, c + 2)
-            buf = bufs[b][carry - ce: carry + (hi_s - lo_s)]
-            room = cap_list - n_listed                             # (a full list: the piece can only report that it overflows, or keep nothing)
-            info["full_list_pieces"] += int(room == 0)
-            got, pmax = sync_piece(buf, buf.numel(), g_lo - base, g_hi - base, base, idx_all[n_listed:] if room else None,
-                                   val_all[n_listed:] if room else None, room)
-            if got < 0:
-                # no positive maximum yet (leading silence), or one so small that most lags of this piece stay above 0.4 x
-                # it (leading noise): nothing is kept of the piece but its own maximum, which at the end decides whether it
-                # has to be looked at again at all
-                overflow.append((c, pmax))
-                segs.append((n_listed, 0))
-            else:
-                segs.append((n_listed, got))
-                n_listed += got
-            # provisional decision with the maximum so far (a piece that kept nothing is simply not represented: whatever
-            # that gets wrong is put right at the end), then the packets whose samples are resident
-            pk = decide(idx_all, val_all, n_listed, BIG)
-            k0 = int(np.searchsorted(pk, base - 2))                # (detections before this buffer were handled, or wait for the end)
-            ready = [int(i) for i in pk[k0:] if int(i) + 2 + L <= hi_s and int(i) not in row_of]
-            if ready:
-                if next_row + len(ready) > rows.shape[0]:           # (provisional detections that are dropped later use rows too)
-                    rows = torch.cat([rows, self._new((max(len(ready), rows.shape[0]), self.bytes_per_frame), torch.uint8)])
-                st = torch.tensor([i + 2 - base for i in ready], dtype=torch.int64, device=dev)
-                self.demod_frames(buf, st, out_bits=rows[next_row: next_row + len(ready)])
-                for k, i in enumerate(ready):
-                    row_of[i] = next_row + k
-                next_row += len(ready)
-
-        info["pieces_seconds"] = time.perf_counter() - t_start - info["setup_seconds"]
-        info["listed"] = n_listed                                 # lags kept over the pieces (a superset of what the final rule can accept)
-
-        # ---- the end of the stream: the maximum is final
-        def piece_on_device(c):
-            lo_s, hi_s, ce, base, g_lo, g_hi = geometry(c)
-            buf = bufs[0][: ce + hi_s - lo_s]
-            buf.copy_(x[base:hi_s])                                # (second look: a plain synchronous copy)
-            info["h2d_bytes"] += buf.numel() * x.element_size()
-            return buf, base, g_lo, g_hi
-
-        extra, scratch = {}, None
-        M = float(run_max[0].item())
-        for c, pmax in overflow:
-            if np.isfinite(M) and M > 0.0 and pmax < cfg.thresh * M * (1.0 - 1e-6):
-                info["overflow_pieces_below_threshold"] = info.get("overflow_pieces_below_threshold", 0) + 1
-                continue                                           # no lag of that piece can pass thresh x (final maximum): nothing to look at
-            buf, base, g_lo, g_hi = piece_on_device(c)
-            k = g_hi - g_lo
-            if scratch is None or scratch[0].numel() < k:          # one scratch pair for every piece looked at again
-                scratch = (self._new((k,), torch.int64), self._new((k, 3), torch.float64))
-            got, _ = sync_piece(buf, buf.numel(), g_lo - base, g_hi - base, base, scratch[0], scratch[1], k)
-            extra[c] = (scratch[0][:got].clone(), scratch[1][:got].clone())   # (what is kept is what was listed, not k x 32 B)
-            info["second_look_chunks"] += 1
-        if overflow:
-            parts_i, parts_v = [], []
-            for c, (s0, k) in enumerate(segs):
-                if c in extra:
-                    parts_i.append(extra[c][0]); parts_v.append(extra[c][1])
-                elif k:
-                    parts_i.append(idx_all[s0: s0 + k]); parts_v.append(val_all[s0: s0 + k])
-            fi = torch.cat(parts_i) if parts_i else idx_all[:0]
-            fv = torch.cat(parts_v).contiguous() if parts_v else val_all[:0]
-            if fi.numel() > cap_list:
-                dwork = self._new((int(self.lib.gf3_sync_decide_workspace_bytes(self._h, fi.numel())),), torch.uint8)
-        else:
-            fi, fv = idx_all[:n_listed], val_all[:n_listed]
-        peaks = decide(fi.contiguous(), fv, fi.numel(), plen - 2)
-        if len(peaks) < 2:
-            raise ValueError("need at least one array to concatenate")      # np.vstack([]) in get_symbols (OFDM.py:400)
-        det = [int(i) for i in peaks[:-1]]                            # the last detection is always dropped (OFDM.py:395)
-        missing = [i for i in det if i not in row_of]
-        for i in missing:
-            if i + 2 + L > n:
-                raise ValueError("packet runs past the end of the stream")
-        info["provisional_detections_dropped"] = len(set(row_of) - set(int(i) for i in peaks))   # (accepted with an earlier maximum, rejected by the final one)
-        for k0 in range(0, len(missing), 64):                         # second look at single packets: samples re-read from the host
-            grp = missing[k0: k0 + 64]
-            seg = torch.stack([x[i + 2: i + 2 + L] for i in grp]).to(dev)
-            info["h2d_bytes"] += seg.numel() * x.element_size()
-            if next_row + len(grp) > rows.shape[0]:
-                rows = torch.cat([rows, self._new((len(grp), self.bytes_per_frame), torch.uint8)])
-            self.demod_frames(seg.reshape(-1), torch.arange(len(grp), device=dev, dtype=torch.int64) * L,
-                              out_bits=rows[next_row: next_row + len(grp)])
-            for k, i in enumerate(grp):
-                row_of[i] = next_row + k
-            next_row += len(grp)
-            info["second_look_packets"] += len(grp)
-        order = torch.tensor([row_of[i] for i in det], dtype=torch.int64, device=dev)
-        bits = rows[order]
-        torch.cuda.synchronize(dev)
-        info["seconds"] = time.perf_counter() - t_start
-        info["max"] = M
-        return dict(peaks=torch.from_numpy(peaks).to(dev), bits=bits, info=info)
+        return ingest.receive(self, samples, chunk_samples, list_cap)
 
     def release_host_buffers(self):
         """Drop the calling thread's cached ingest resources (device buffers, workspace, pinned staging, copy stream):
         receive_host keeps them between calls so that a receiver fed one recording after another does not allocate."""
-        self._tls.ingest = None
+        ingest.release(self)
 
     # ------------------------------------------------------------------ PS + decode (OFDM.py:504-505, 541-544)
     def unpack_decode(self, packed, mask_bits=None, to_host=True):

@@ -1486,12 +1486,17 @@ def test_receive_host_list_exactly_full_and_read_only_mapping(tmp_path):
     base = eng.receive_host(r, chunk_samples=1)
     listed = base["info"]["listed"]
     assert 4 <= listed <= 400, base["info"]
+    # the calling thread's cached piece buffers and kept-lag list are large enough for every call below: the same
+    # device memory serves them all, handed out as slices
+    cached = lambda: {k: eng._tls.ingest.tensors[k].data_ptr() for k in ("buf0", "buf1", "list idx", "list val")}
+    ptrs = cached()
     full = 0
     for cap in range(1, listed + 1):
         out = eng.receive_host(r, chunk_samples=1, list_cap=cap)
         full += out["info"]["full_list_pieces"]
         assert np.array_equal(out["peaks"].cpu().numpy(), want_peaks), (cap, out["info"])
         assert torch.equal(out["bits"], base["bits"]), cap
+        assert cached() == ptrs, cap
     assert full >= 1                                                    # some capacity left a piece no room at all
     assert np.array_equal(eng.unpack_bits(base["bits"]).cpu().numpy(), ref["bits"])
     # (ii) a read-only file mapping is taken like any other pageable array (staged: host copies two pieces ahead, on a

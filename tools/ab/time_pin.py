@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How to get a PAGEABLE host array to the device fastest: staged copies (1 thread / N threads) vs pinning it in place."""
+"""How to get a PAGEABLE host array to the device fastest: staged copies (1 thread / N threads) vs the runtime's own copy."""
 import time, numpy as np, torch
 from concurrent.futures import ThreadPoolExecutor
 n = 320887424
@@ -28,9 +28,3 @@ for piece in (1 << 23, 1 << 25, 1 << 27):                       # the runtime's 
         dst[lo:lo + piece].copy_(t_a[lo:lo + piece])
     torch.cuda.synchronize(); dt = time.perf_counter() - t
     print("plain copy_ from the pageable array in pieces of %9d samples: %.1f ms = %.1f GB/s" % (piece, dt * 1e3, n * 4 / dt / 1e9), flush=True)
-rt = torch.cuda.cudart()
-t = time.perf_counter(); rc = rt.cudaHostRegister(a.ctypes.data, a.nbytes, 0); t_reg = time.perf_counter() - t
-print("cudaHostRegister rc", rc, "%.1f ms" % (t_reg * 1e3), flush=True)
-torch.cuda.synchronize(); t = time.perf_counter(); dst.copy_(t_a, non_blocking=True); torch.cuda.synchronize(); t_cp = time.perf_counter() - t
-print("copy from the registered array: %.1f ms = %.1f GB/s (is_pinned %s)" % (t_cp * 1e3, n * 4 / t_cp / 1e9, t_a.is_pinned()), flush=True)
-t = time.perf_counter(); rt.cudaHostUnregister(a.ctypes.data); print("unregister %.1f ms" % ((time.perf_counter() - t) * 1e3))
