@@ -9,19 +9,13 @@
 //   c split into Q partitions of Lp taps; each partition's contribution is a
 //   circular correlation of size N = 2NC, valid for lags < N-Lp+1.
 // ============================================================================
-#ifndef GF3_CORR_WPS
-#define GF3_CORR_WPS 2
-#endif
-#ifndef GF3_CORR_PP
-#define GF3_CORR_PP true
-#endif
 // One search window: everything corr_kernel does for window b.
 template <int NC, int DT>
 GF3_DEV void corr_window(const CorrArgs& a, const int64_t b, double2* smem) {
     constexpr int T = NC / 8;
-    constexpr bool PP = GF3_CORR_PP && FftGeom<NC>::PINGPONG;
+    constexpr bool PP = FftGeom<NC>::PINGPONG;
     cplx* lds = smem;
-    double* scratch = (double*)(smem + (PP ? FftGeom<NC>::LDS_ELEMS : FftGeom<NC>::LDS_ELEMS_INPLACE));
+    double* scratch = (double*)(smem + FftGeom<NC>::LDS_ELEMS);
     const int tid = threadIdx.x;
     const int64_t s0 = b * a.stride + a.win_lo;      // absolute sample index of lag 0 of this window
     const int W = a.W;                               // lags to resolve
@@ -156,7 +150,7 @@ GF3_DEV void corr_window(const CorrArgs& a, const int64_t b, double2* smem) {
 // workgroups are ~25 us; a persistent grid walking the list was tried -- the loop's invariants spill 4-36 registers of a
 // kernel that has none to spare).  The plain instantiation is the kernel it was.
 template <int NC, int DT, bool LISTED = false>
-__global__ __launch_bounds__(NC / 8, (NC <= 2048 ? GF3_CORR_WPS : 2)) void corr_kernel(CorrArgs a) {
+__global__ __launch_bounds__(NC / 8, 2) void corr_kernel(CorrArgs a) {
     extern __shared__ double2 smem[];
     if constexpr (!LISTED) corr_window<NC, DT>(a, blockIdx.x, smem);
     else {
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(NC / 8, 2) void ols_kernel(OlsArgs a) {
 
 hipError_t run_corr(const gf3_ctx* c, const CorrPlan& pl, const CorrArgs& a, int64_t grid, hipStream_t st, bool listed) {
     const int NCp = pl.NC;
-    const size_t lds = (GF3_CORR_PP ? fft_lds_bytes(NCp) : (size_t)(NCp + NCp / 8) * sizeof(cplx)) + 32 * sizeof(double);
+    const size_t lds = fft_lds_bytes(NCp) + 32 * sizeof(double);
     hipError_t e = hipSuccess;
 #ifdef GF3_DEV_BUILD
     if (NCp == 1024 && !listed) {

@@ -97,30 +97,19 @@ GF3_DEV double rcp_n1(double x) {
 //             (1-f)|Hs| + f|He| is positive, so X/Hest and X*conj(u*rot) have the same signs and
 //             the decision needs neither the division nor |Hs|, |He|: per-carrier state is u alone.
 enum { MODE_FULL = 0, MODE_SCAN = 1, MODE_QPSK = 2 };
-#ifndef GF3_DEMOD_WPS
-#define GF3_DEMOD_WPS 2
-#endif
-#ifndef GF3_ABL
-#define GF3_ABL 0             /* timing-only ablations of the table modes (WRONG results): 1 no magnitude reads, 2 also ping-pong buffers */
-#endif
-// lean modes at GF3_DEMOD_WPS waves/SIMD; 3 needs the single in-place FFT buffer to fit 3 workgroups of LDS
-// MODE_QPSK keeps the two ping-pong FFT buffers.  The table modes carry two more doubles of state per carrier (the
-// magnitude model a0 + da f_l), which do not fit the register file next to the transform at two workgroups per CU;
-// they live in LDS ([8][T] pairs, one conflict-free 16-byte read per carrier per symbol), and the room comes from the
-// single in-place FFT buffer (one more barrier per exchange).
+// Every mode runs at two waves per SIMD.  MODE_QPSK keeps the two ping-pong FFT buffers.  The table modes carry two more
+// doubles of state per carrier (the magnitude model a0 + da f_l), which do not fit the register file next to the
+// transform at two workgroups per CU; they live in LDS ([8][T] pairs, one conflict-free 16-byte read per carrier per
+// symbol), and the room comes from the single in-place FFT buffer (one more barrier per exchange).
 template <int NC, int MODE> struct DemodOcc {
-    static constexpr int WPS = (MODE == MODE_QPSK && NC <= 2048) ? GF3_DEMOD_WPS : 2;
+    static constexpr int WPS = 2;
     static constexpr bool MAG_LDS = (MODE != MODE_QPSK);
     // N = 8192 (NC = 4096, 512 threads): the register file allows one workgroup per CU whatever the LDS does, and two
     // 64 KB buffers fit beside the decision ring (148 KB of 160) -- one barrier per exchange instead of two, with no other
     // workgroup on the CU to run under a barrier.  Four passes end in the second buffer and the next transform starts in
     // the first, so the buffers need not be flipped (rfft_regs passes flip = 0 for the unfused sizes).
     static constexpr bool PP_SIZE = FftGeom<NC>::PINGPONG || NC == 4096;
-#if GF3_ABL >= 2
-    static constexpr bool PP = PP_SIZE && WPS <= 2;
-#else
-    static constexpr bool PP = PP_SIZE && WPS <= 2 && !MAG_LDS;
-#endif
+    static constexpr bool PP = PP_SIZE && !MAG_LDS;
     static constexpr int LDS_ELEMS = PP ? 2 * NC : FftGeom<NC>::LDS_ELEMS_INPLACE;
     static constexpr int MAG_ELEMS = MAG_LDS ? NC : 0;             // double2 (a0, da) per slot per thread: 8 * NC/8
 };
@@ -343,7 +332,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     }
     if constexpr (STAGE == STAGE_EST) return;         // Hs, He, slope are in memory: the data stage takes it from there
     GF3_STAMP(3);
-    if constexpr (DemodOcc<NC, MODE>::MAG_LDS && GF3_ABL == 0) {      // (block_sum's barriers: every thread is done with the fit-range arrays)
+    if constexpr (DemodOcc<NC, MODE>::MAG_LDS) {      // (block_sum's barriers: every thread is done with the fit-range arrays)
 #pragma unroll
         for (int s = 0; s < 8; ++s) mags[s * T + tid] = make_double2(a0[s], da[s]);
     }
@@ -480,11 +469,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
                 const cplx ep = cmul_conj(v[s], g);                        // X / g  = e * mag
                 u[s] = cmul(g, gstep[s]);                                  // ... and for the next one
                 const int ps = pos_of(s);
-#if GF3_ABL >= 1
-                const double2 md = make_double2(1.0 + 1e-3 * s, 1e-4);
-#else
                 const double2 md = mags[s * T + tid];
-#endif
                 const double mag = fma(md.y, fl, md.x);
                 // bits only: the decision needs (ep / mag - lo) inv to far less than full precision (the margin of `clear`
                 // is 1e-9), so one Newton step serves and the quotient itself is never formed; the dumps of MODE_FULL
@@ -549,12 +534,16 @@ inline int demod_ring(const gf3_ctx* c) {
     while (r < need) r <<= 1;
     return r;
 }
+// DemodOcc::PP_SIZE on the host
+constexpr bool demod_pp_size(int NC) { return NC == 1024 || NC == 2048 || NC == 4096; }
+static_assert(demod_pp_size(512) == DemodOcc<512, MODE_QPSK>::PP_SIZE && demod_pp_size(1024) == DemodOcc<1024, MODE_QPSK>::PP_SIZE &&
+              demod_pp_size(2048) == DemodOcc<2048, MODE_QPSK>::PP_SIZE && demod_pp_size(4096) == DemodOcc<4096, MODE_QPSK>::PP_SIZE,
+              "demod_pp_size restates DemodOcc::PP_SIZE");
 // lean = MODE_QPSK (ping-pong FFT buffers); the table modes use the in-place buffer and NC (a0, da) pairs.
 // Layout: [scratch 32 doubles | rotation tables | FFT buffer | decision bytes | (a0, da) pairs]; everything from the
 // FFT buffer on is overlaid by Hs, He of the fit range during the channel-estimate stage (which may need more).
 inline size_t demod_lds_bytes(const gf3_ctx* c, bool lean = false) {
-    const bool inplace = !lean || (GF3_DEMOD_WPS > 2 && c->NC <= 2048);
-    const bool pp_size = c->NC == 1024 || c->NC == 2048 || c->NC == 4096;        // == DemodOcc::PP_SIZE
+    const bool inplace = !lean, pp_size = demod_pp_size(c->NC);
     const size_t fft = (inplace || !pp_size) ? (size_t)(c->NC + c->NC / 8) * sizeof(cplx) : (size_t)2 * c->NC * sizeof(cplx);
     const size_t mags = lean ? 0 : (size_t)c->NC * sizeof(double2);
     const size_t tail = fft + (size_t)((demod_ring(c) * c->cfg.C + 15) & ~15) + mags;

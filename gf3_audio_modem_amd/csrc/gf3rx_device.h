@@ -99,10 +99,6 @@ template <int DT> struct RawPair {
     GF3_DEV void zero() { v.a = 0; v.b = 0; }
     GF3_DEV cplx get() const { return cmk((double)v.a, (double)v.b); }
 };
-template <int DT> GF3_DEV double load_sample_t(const void* p, int64_t i) {
-    return (double)((const typename RawT<DT>::E*)p)[i];
-}
-
 GF3_DEV double load_sample(const void* p, int64_t i, int dt) {
     switch (dt) {
         case DT_F64: return ((const double*)p)[i];
@@ -110,12 +106,6 @@ GF3_DEV double load_sample(const void* p, int64_t i, int dt) {
         case DT_I16: return (double)((const int16_t*)p)[i];
         default:     return (double)((const uint8_t*)p)[i];
     }
-}
-GF3_DEV cplx load_pair(const void* p, int64_t i, int dt) {
-    return cmk(load_sample(p, i, dt), load_sample(p, i + 1, dt));
-}
-GF3_DEV double load_sample_clamped(const void* p, int64_t i, int64_t n, int dt) {
-    return (i >= 0 && i < n) ? load_sample(p, i, dt) : 0.0;
 }
 
 // ---------------------------------------------------------------- butterflies
@@ -201,7 +191,8 @@ template <int NC> struct FftGeom {
 // Per-thread twiddle bases: the index k of every pass depends only on the thread,
 // so one unit twiddle per pass is loaded once per workgroup and kept in registers.
 template <int NC> struct FftTw {
-    cplx b2, b3, b4, c4;
+    cplx b2, b3, b4, c4;      // c4: step to the second butterfly of a 2-butterfly pass, or (fused sizes) the base
+                              // twiddle of the mirrored butterfly of the last pass
     // Made opaque once per transform: without it LLVM hoists every twiddle POWER
     // (w^2..w^7 of each pass, ~80 VGPRs) out of the symbol loop and keeps them live across it.
     // (in place: the empty asm "redefines" the registers it is given, no copies are made)
@@ -209,9 +200,6 @@ template <int NC> struct FftTw {
         asm volatile("" : "+v"(b2.x), "+v"(b2.y), "+v"(b3.x), "+v"(b3.y));
         asm volatile("" : "+v"(b4.x), "+v"(b4.y), "+v"(c4.x), "+v"(c4.y));
     }
-    // passes 2 and 3 only: a kernel with ~16 registers to spare lets the (few) last-pass powers be hoisted
-    GF3_DEV void refresh_inner() { asm volatile("" : "+v"(b2.x), "+v"(b2.y), "+v"(b3.x), "+v"(b3.y)); }      // c4: step to the second butterfly of a 2-butterfly pass, or (fused
-                              // sizes) the base twiddle of the mirrored butterfly of the last pass
     GF3_DEV void init(int tid, const cplx* __restrict__ tw);
 };
 
@@ -413,15 +401,6 @@ GF3_DEV void rfft_regs(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, cplx wb, in
 }
 
 // ---------------------------------------------------------------- block collectives
-GF3_DEV double wave_incl_scan(double x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
 GF3_DEV double wave_sum(double x) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
@@ -467,18 +446,6 @@ GF3_DEV int block_min_i(int x, int* scratch) {
     int s = scratch[0];
     for (int i = 1; i < nw; ++i) s = min(s, scratch[i]);
     return s;
-}
-// exclusive scan of per-thread totals (two independent scans at once)
-GF3_DEV void block_excl_scan2(double a, double b, double* scratch, double& ea, double& eb) {
-    const int wave = threadIdx.x >> 6;
-    const double ia = wave_incl_scan(a), ib = wave_incl_scan(b);
-    lds_barrier();
-    if ((threadIdx.x & 63) == 63) { scratch[wave] = ia; scratch[8 + wave] = ib; }
-    lds_barrier();
-    double oa = 0.0, ob = 0.0;
-    for (int i = 0; i < wave; ++i) { oa += scratch[i]; ob += scratch[8 + i]; }
-    ea = oa + (ia - a);
-    eb = ob + (ib - b);
 }
 
 // sin/cos by Cody-Waite reduction to [-pi/4, pi/4] (three-part pi/2, exact with fma for

@@ -17,11 +17,11 @@
 // non-finite samples) is appended to a list, and corr_kernel itself runs on the listed windows: no decision is ever taken on
 // an fp32 value that the bound does not back.
 //
-// Geometry: 2048-sample transforms (1024 complex points) held by ONE wave -- 16 points per lane, passes 16 x 16 x 4, two
-// exchanges through an 8 KB private LDS buffer and no barrier anywhere (LDS serves a wave's instructions in order); the fp64
-// kernel cannot do this (16 fp64 points + 16 accumulators do not fit the register file), fp32 can.  Partition
-// length Lp = 2048 - Wmax + 1, Q = ceil(Lc / Lp) forward transforms, the chirp partitions' spectra multiplied in and
-// accumulated in registers, one inverse transform.
+// Geometry: 2048-sample transforms (1024 complex points) held by ONE wave -- 16 points per lane, passes 16 x 16 x 4, the
+// first exchange through an 8 KB private LDS buffer, the second through cross-lane swaps, and no barrier anywhere (LDS
+// serves a wave's instructions in order); the fp64 kernel cannot do this (16 fp64 points + 16 accumulators do not fit the
+// register file), fp32 can.  Partition length Lp = 2048 - Wmax + 1, Q = ceil(Lc / Lp) forward transforms, the
+// chirp partitions' spectra multiplied in and accumulated in registers, one inverse transform.
 #pragma once
 #include "gf3rx_screen.h"
 
@@ -119,9 +119,6 @@ GF3_DEV void pf_twiddle16(pf (&v)[16], pf w) {
 GF3_DEV int fs_swz(int i) { return i ^ ((i >> 4) & 15); }          // XOR swizzle of the first exchange (8-byte elements)
 
 struct FsTw { pf tw2; pf tw3; };                                  // pass 2: exp(-2 pi i (t & 15) / 256); pass 3: exp(-2 pi i ((t & 15) + 64 (t >> 4)) / 1024)
-#ifndef GF3_FS_PERMLANE
-#define GF3_FS_PERMLANE 1     /* 1: the second exchange runs through v_permlane32_swap / v_permlane16_swap instead of LDS */
-#endif
 // swap the upper 32 lanes of a with the lower 32 lanes of b / the odd rows (of 16 lanes) of a with the even rows of b
 GF3_DEV void pf_swap32(pf& a, pf& b) {
     auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
@@ -133,15 +130,11 @@ GF3_DEV void pf_swap16(pf& a, pf& b) {
     auto ry = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
     a = pfmk(__uint_as_float(rx[0]), __uint_as_float(ry[0])); b = pfmk(__uint_as_float(rx[1]), __uint_as_float(ry[1]));
 }
-// Forward complex FFT of 1024 points in ONE wave: in v[r] = z[t + 64 r]; out (GF3_FS_PERMLANE) v[i + 4 m] =
-// Z[(t & 15) + 16 i + 64 (t >> 4) + 256 m], i, m < 4 -- fs_bin(t, s) -- else Z[t + 64 s] in v[s].
-// L: the wave's private 1024-point LDS buffer (in place: a wave's LDS instructions execute in order).
+// Forward complex FFT of 1024 points in ONE wave: in v[r] = z[t + 64 r]; out v[i + 4 m] =
+// Z[(t & 15) + 16 i + 64 (t >> 4) + 256 m], i, m < 4 -- fs_bin(t, s).
+// L: the wave's private 1024-point LDS buffer of the first exchange (in place: a wave's LDS instructions execute in order).
 GF3_DEV int fs_bin(int t, int s) {
-#if GF3_FS_PERMLANE
     return (t & 15) + 16 * (s & 3) + 64 * (t >> 4) + 256 * (s >> 2);
-#else
-    return t + 64 * s;
-#endif
 }
 GF3_DEV void fs_fft1024(pf (&v)[16], pf* L, const FsTw& tw, int t) {
     pf_dft16(v);                                                   // X[m] in v[scr_perm(m)]
@@ -156,8 +149,6 @@ GF3_DEV void fs_fft1024(pf (&v)[16], pf* L, const FsTw& tw, int t) {
     }
     pf_twiddle16(v, tw.tw2);                                       // w = exp(-2 pi i (t & 15) / 256)
     pf_dft16(v);
-    const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
-#if GF3_FS_PERMLANE
     // Second exchange WITHOUT LDS.  Lane (row rho = t >> 4, column k = t & 15) holds, as X[m] in v[scr_perm(m)], element
     // 256 rho + k + 16 m of the pass's output; the radix-4 butterflies of the last pass combine the four ROWS of one column.
     // A 4 x 4 transpose of chunks of four m across the rows -- two stages of cross-row swaps, 32 instructions -- leaves lane
@@ -187,42 +178,10 @@ GF3_DEV void fs_fft1024(pf (&v)[16], pf* L, const FsTw& tw, int t) {
 #pragma unroll
         for (int s2 = 0; s2 < 16; ++s2) v[s2] = o[s2];
     }
-#else
-    {
-        const int k = t & 15, base = (t - k) * 16 + k;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) L[base + 16 * m] = v[scr_perm(m)];
-    }
-    // last pass: radix 4, NS = 256: butterflies j = t + 64 b, inputs L[j + 256 r], twiddle exp(-2 pi i j / 1024)^r
-    {
-        pf x[16];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[4 * b + r] = L[t + 64 * b + 256 * r];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const pf w16[4] = {pfmk(1.0f, 0.0f), pfmk(c1, -s1), pfmk(h, -h), pfmk(s1, -c1)};       // exp(-2 pi i b / 16)
-            const pf w1 = b == 0 ? tw.tw3 : pf_cmul(tw.tw3, w16[b]);
-            const pf w2 = pf_cmul(w1, w1), w3 = pf_cmul(w2, w1);
-            pf a0 = x[4 * b], a1 = pf_cmul(x[4 * b + 1], w1), a2 = pf_cmul(x[4 * b + 2], w2), a3 = pf_cmul(x[4 * b + 3], w3);
-            pf_dft4(a0, a1, a2, a3);                               // outputs m = 0..3: Z[j + 256 m]
-            v[b] = a0; v[b + 4] = a1; v[b + 8] = a2; v[b + 12] = a3;   // slot q = b + 4 m
-        }
-    }
-#endif
-    (void)c1; (void)s1; (void)h;
 }
 
-#ifndef GF3_FS_WPS
-#define GF3_FS_WPS 2
-#endif
-#ifndef GF3_FS_EARLY
-#define GF3_FS_EARLY 1        /* 1: the next segment's samples are requested before this one's transform (32 registers in flight) */
-#endif
-
 template <int DT>
-__global__ __launch_bounds__(64, GF3_FS_WPS) void corr_screen_kernel(FScreenArgs a) {
+__global__ __launch_bounds__(64, 2) void corr_screen_kernel(FScreenArgs a) {
     __shared__ pf L[GF3_FS_NC];
     constexpr int NC = GF3_FS_NC;
     typedef typename RawT<DT>::E E;
@@ -287,7 +246,7 @@ __global__ __launch_bounds__(64, GF3_FS_WPS) void corr_screen_kernel(FScreenArgs
         float e2 = e2p.x + e2p.y;
         // (f64 samples: 16 raw pairs are 64 registers, which do not fit beside the transform -- the next segment is then
         //  requested after this one's multiply-adds, its latency covered by the SIMD's other wave)
-        constexpr bool EARLY = GF3_FS_EARLY && DT != DT_F64;
+        constexpr bool EARLY = DT != DT_F64;
         if (EARLY && q + 1 < a.Q) fetch(q + 1);
         // this partition's spectrum (an L2-resident table): requested BEFORE the transform, whose LDS round trips then cover
         // the L2 latency -- asked for next to the multiply-adds it sat, exposed, between the split's reads and the first fma

@@ -215,16 +215,16 @@ struct DeviceGuard {
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
 
-inline size_t fft_lds_bytes(int NC) {          // == FftGeom<NC>::LDS_ELEMS
+constexpr size_t fft_lds_bytes(int NC) {
     return (size_t)((NC == 1024 || NC == 2048) ? 2 * NC : NC + NC / 8) * sizeof(cplx);
 }
+static_assert(fft_lds_bytes(512) == FftGeom<512>::LDS_ELEMS * sizeof(cplx) && fft_lds_bytes(1024) == FftGeom<1024>::LDS_ELEMS * sizeof(cplx) &&
+              fft_lds_bytes(2048) == FftGeom<2048>::LDS_ELEMS * sizeof(cplx) && fft_lds_bytes(4096) == FftGeom<4096>::LDS_ELEMS * sizeof(cplx),
+              "fft_lds_bytes restates FftGeom<NC>::LDS_ELEMS");
 
 template <typename Kern, typename Args>
 static hipError_t launch(Kern k, int64_t grid, int threads, size_t lds, hipStream_t st, const Args& a) {
     if (grid <= 0) return hipSuccess;
-#ifdef GF3_LDS_PAD      /* diagnostic builds only: extra dynamic LDS to force a lower occupancy */
-    lds += GF3_LDS_PAD;
-#endif
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -35,12 +35,6 @@ hipError_t launch_refine(const gf3_ctx* c, const RefineArgs& a, int64_t cap_cell
     const int64_t slots = 2 * (int64_t)c->n_cu;                         // (the LDS staging allows two workgroups per CU)
     const int64_t wgs = (cap_cells + 3) / 4;                             // (a wave per cell at a time)
     const unsigned grid = (unsigned)(wgs < slots ? wgs : slots);
-#if GF3_REFINE_MFMA
-    const int64_t wg4 = 4 * slots;                                       // (no LDS staging: more resident waves, a wave per cell)
-    DISPATCH_DT(a.dt, hipLaunchKernelGGL((scr_refine_mfma_kernel<DTC>), dim3((unsigned)(wg4 < wgs ? wg4 : wgs)), dim3(SCR_REF_THREADS), 0, st, a));
-    (void)grid;
-#else
     DISPATCH_DT(a.dt, hipLaunchKernelGGL((scr_refine_kernel<DTC>), dim3(grid), dim3(SCR_REF_THREADS), 0, st, a));
-#endif
     return hipGetLastError();
 }

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 for lib in "$@"; do
   tag=$(basename "$lib" .so); OUT=$R/gpurun_out/r3/reftime_$tag; mkdir -p $OUT
   if [ "$lib" = "-" ]; then unset GF3_LIB; else export GF3_LIB=$R/$lib; fi
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/tools/ab/${GF3_AB_DRIVER:-time_config3.py} > $OUT/log.txt 2>&1 || { echo "$tag failed"; tail -5 $OUT/log.txt; exit 1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/tools/ab/time_config3.py > $OUT/log.txt 2>&1 || { echo "$tag failed"; tail -5 $OUT/log.txt; exit 1; }
   tail -1 $OUT/log.txt
   python3 - "$OUT" "$tag" <<'P'
 import csv, glob, os, sys
