@@ -87,6 +87,11 @@ class CamG:
         self.bits_per_symbol = self.K * self.mu
         self.known_sequence = _load_known_sequence(self.ofdm_symbol_size)
         self.ldpc_max_iter = 50                 # decoder iterations at most (encodings "QCLDPC-*")
+        # LLR weights of receive() on the "QCLDPC-*" encodings: "csi" = |H^|^2 (white noise assumed), "noise" = 1 / the
+        # per-carrier noise variance measured on each packet's equalised symbols (coloured noise, interferers); the
+        # latter also leaves the per-carrier SNR estimate [packets, C] in dB in `last_snr_db`
+        self.llr_weighting = "csi"
+        self.last_snr_db = None
         self._engines = {}
 
     def __repr__(self):
@@ -390,6 +395,8 @@ class receiver(transmitter):
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
+        if self.llr_weighting not in ("csi", "noise"):
+            raise ValueError(f"llr_weighting must be 'csi' or 'noise', not {self.llr_weighting!r}")
         r = _as_samples(signal)
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
@@ -412,9 +419,17 @@ class receiver(transmitter):
         want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ("eq",) if rate is not None else ())
         o = eng.demod_frames(x, starts, want=want)
         if rate is not None:
-            # soft path: CSI-weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
+            # soft path: weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
             code = _qcldpc_code(rate, eng.device)
-            llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
+            if self.llr_weighting == "noise":
+                var = eng.noise_estimate(o["eq"])
+                llr = eng.soft_demap_nw(o["eq"], var)
+                # SNR report 10 log10(Es / v') with the demapper's floor, [F, C]: rides home in the small copy below
+                pts = self._tables()[0]
+                floored = torch.maximum(var, 1e-6 * var.mean(dim=1, keepdim=True))
+                snr_t = 10.0 * torch.log10(float(np.mean(np.abs(pts) ** 2)) / floored)
+            else:
+                llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
             n_cw = llr.numel() // code.n
             bits_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter).reshape(-1)
         else:
@@ -422,8 +437,9 @@ class receiver(transmitter):
         # everything else the host needs, in ONE small copy behind the kernels: first packet's Hs / He, the slopes, and the
         # ragged-packet flag (a packet that runs past the recording: the reference's get_symbols fails on it)
         K, F = self.K, self.no_packets
-        small = torch.cat([torch.view_as_real(o["Hs"][0]).reshape(-1), torch.view_as_real(o["He"][0]).reshape(-1), o["slope"],
-                           o["status"].to(torch.float64)])
+        noise = rate is not None and self.llr_weighting == "noise"
+        small = torch.cat([torch.view_as_real(o["Hs"][0]).reshape(-1), torch.view_as_real(o["He"][0]).reshape(-1), o["slope"]]
+                          + ([snr_t.reshape(-1)] if noise else []) + [o["status"].to(torch.float64)])
         host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=True)
         host.copy_(small, non_blocking=True)
         torch.cuda.current_stream(small.device).synchronize()
@@ -434,6 +450,8 @@ class receiver(transmitter):
         h = host.numpy()
         Hest_start0, Hest_end0 = h[: 2 * K].view(np.complex128).copy(), h[2 * K: 4 * K].view(np.complex128).copy()
         self._last_slope = h[4 * K: 4 * K + F].copy()
+        if noise:
+            self.last_snr_db = h[4 * K + F: 4 * K + F + snr_t.numel()].reshape(F, -1).copy()
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())

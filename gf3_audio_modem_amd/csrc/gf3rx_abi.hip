@@ -2,6 +2,7 @@
 // but the stream sync (gf3rx_sync.hip); the small stand-alone kernels (demappers, zero forcing, Schmidl-Cox) live here too.
 // See DESIGN.md for the layout and gf3rx_host.h for the map of translation units.
 #include "gf3rx_demod.h"
+#include "gf3rx_demap.h"
 #include "gf3rx_fscreen.h"
 
 // Message of the calling thread's last failure.  One buffer per host thread, none in the context: concurrent calls
@@ -43,60 +44,24 @@ template <typename T> static hipError_t upload(T** dptr, const T* h, size_t n) {
 // standalone demappers
 // ============================================================================
 struct DemapArgs {
-    const cplx* sym; int64_t n; int M, mu;
-    const double* cre; const double* cim; const int* clab;
+    const cplx* sym; int64_t n;
+    DemapTab t;
     uint8_t* bits; float* llr; double inv_nv; uint8_t* idx;
-    SepTab sep;
 };
 __global__ void demap_hard_kernel(DemapArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
         const cplx e = a.sym[i];
-        const int best = scan_table(e, a.cre, a.cim, a.M);          // literal: this entry point is `demap` itself
-        const int lab = a.clab[best];
-        for (int b = 0; b < a.mu; ++b) a.bits[i * a.mu + b] = (lab >> (a.mu - 1 - b)) & 1;
+        const int best = scan_table(e, a.t.cre, a.t.cim, a.t.M);    // literal: this entry point is `demap` itself
+        const int lab = a.t.clab[best];
+        for (int b = 0; b < a.t.mu; ++b) a.bits[i * a.t.mu + b] = (lab >> (a.t.mu - 1 - b)) & 1;
         if (a.idx) a.idx[i] = (uint8_t)best;
     }
 }
-// max-log LLR per bit: (min over points with bit=1 of d^2 - min over points with bit=0 of d^2) / noise_var
+// max-log LLR per bit: (min over points with bit=1 of d^2 - min over points with bit=0 of d^2) / noise_var; the
+// per-symbol arithmetic is gf3rx_demap.h's
 __global__ void soft_demap_kernel(DemapArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-        const cplx e = a.sym[i];
-        double m0[8], m1[8];
-#pragma unroll
-        for (int b = 0; b < 8; ++b) m0[b] = m1[b] = INFINITY;
-        if (a.sep.nI > 0) {
-            // separable table: a bit owned by one axis sees the other axis' term cancel in the difference
-            for (int k = 0; k < a.sep.nI; ++k) {
-                const double d = (e.x - a.sep.lvI[k]) * (e.x - a.sep.lvI[k]);
-                const int lab = a.sep.labI[k];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    if (b < a.mu && ((a.sep.maskI >> (a.mu - 1 - b)) & 1)) {
-                        if ((lab >> (a.mu - 1 - b)) & 1) m1[b] = fmin(m1[b], d); else m0[b] = fmin(m0[b], d);
-                    }
-            }
-            for (int k = 0; k < a.sep.nQ; ++k) {
-                const double d = (e.y - a.sep.lvQ[k]) * (e.y - a.sep.lvQ[k]);
-                const int lab = a.sep.labQ[k];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    if (b < a.mu && !((a.sep.maskI >> (a.mu - 1 - b)) & 1)) {
-                        if ((lab >> (a.mu - 1 - b)) & 1) m1[b] = fmin(m1[b], d); else m0[b] = fmin(m0[b], d);
-                    }
-            }
-        } else {
-            for (int c = 0; c < a.M; ++c) {
-                const double dx = e.x - a.cre[c], dy = e.y - a.cim[c];
-                const double d = dx * dx + dy * dy;
-                const int lab = a.clab[c];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    if (b < a.mu) { if ((lab >> (a.mu - 1 - b)) & 1) m1[b] = fmin(m1[b], d); else m0[b] = fmin(m0[b], d); }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            if (b < a.mu) a.llr[i * a.mu + b] = (float)((m1[b] - m0[b]) * a.inv_nv);
+        maxlog_table(a.sym[i], a.t, a.inv_nv, a.llr + i * a.t.mu);
     }
 }
 
@@ -111,20 +76,17 @@ __global__ __launch_bounds__(256) void soft_demap_sep_kernel(DemapArgs a) {
     bool onI[MU];
 #pragma unroll
     for (int b = 0; b < MU; ++b) {
-        onI[b] = (a.sep.maskI >> (MU - 1 - b)) & 1;
+        onI[b] = (a.t.sep.maskI >> (MU - 1 - b)) & 1;
         ones[b] = 0;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) ones[b] |= (((onI[b] ? a.sep.labI[k] : a.sep.labQ[k]) >> (MU - 1 - b)) & 1) << k;
+        for (int k = 0; k < 8; ++k) ones[b] |= (((onI[b] ? a.t.sep.labI[k] : a.t.sep.labQ[k]) >> (MU - 1 - b)) & 1) << k;
     }
-    const int nI = a.sep.nI, nQ = a.sep.nQ;
+    const int nI = a.t.sep.nI, nQ = a.t.sep.nQ;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
         const cplx e = a.sym[i];
         double dI[8], dQ[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const double tI = e.x - a.sep.lvI[k], tQ = e.y - a.sep.lvQ[k];
-            dI[k] = tI * tI; dQ[k] = tQ * tQ;
-        }
+        axis_d2<8>(e.x, a.t.sep.lvI, dI);
+        axis_d2<8>(e.y, a.t.sep.lvQ, dQ);
         float out[MU];
 #pragma unroll
         for (int b = 0; b < MU; ++b) {
@@ -141,73 +103,29 @@ __global__ __launch_bounds__(256) void soft_demap_sep_kernel(DemapArgs a) {
             }
             out[b] = (float)((m1 - m0) * a.inv_nv);
         }
-        if constexpr (MU % 4 == 0) {                  // 16-byte aligned rows
-#pragma unroll
-            for (int b = 0; b < MU; b += 4) *(float4*)(a.llr + i * MU + b) = make_float4(out[b], out[b + 1], out[b + 2], out[b + 3]);
-        } else if constexpr (MU % 2 == 0) {           // 8-byte aligned rows
-#pragma unroll
-            for (int b = 0; b < MU; b += 2) *(float2*)(a.llr + i * MU + b) = make_float2(out[b], out[b + 1]);
-        } else {
-#pragma unroll
-            for (int b = 0; b < MU; ++b) a.llr[i * MU + b] = out[b];
-        }
+        store_llr<MU>(a.llr, i, out);
     }
 }
 
-// The same for the tables every square Gray QAM generator produces (and the reference's QPSK): 2^HI x 2^HQ grid, the
-// first HI label bits are the binary index of the I level in `lvI`, the last HQ bits that of the Q level.  Which
-// levels carry a 1 in which bit is then known at compile time, so the whole reduction is straight-line v_min_f64 --
-// no scalar bit tests, no branches (the generic kernel above spends more time steering than computing: 48 scalar
-// branches per symbol against 48 minima).
+// The same for the binary-indexed grids (sep_is_binary: every square Gray QAM generator's table and the reference's
+// QPSK): straight-line minima (maxlog_bin; the generic kernel above spends more time steering than computing: 48
+// scalar branches per symbol against 48 minima).
 template <int HI, int HQ>
 __global__ __launch_bounds__(256) void soft_demap_bin_kernel(DemapArgs a) {
     constexpr int MU = HI + HQ, NI = 1 << HI, NQ = 1 << HQ;
     double lvI[NI], lvQ[NQ];
 #pragma unroll
-    for (int k = 0; k < NI; ++k) lvI[k] = a.sep.lvI[k];
+    for (int k = 0; k < NI; ++k) lvI[k] = a.t.sep.lvI[k];
 #pragma unroll
-    for (int k = 0; k < NQ; ++k) lvQ[k] = a.sep.lvQ[k];
+    for (int k = 0; k < NQ; ++k) lvQ[k] = a.t.sep.lvQ[k];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-        const cplx e = a.sym[i];
-        double dI[NI], dQ[NQ];
-#pragma unroll
-        for (int k = 0; k < NI; ++k) { const double t = e.x - lvI[k]; dI[k] = t * t; }
-#pragma unroll
-        for (int k = 0; k < NQ; ++k) { const double t = e.y - lvQ[k]; dQ[k] = t * t; }
+        double diff[MU];
+        maxlog_bin<HI, HQ>(a.sym[i], lvI, lvQ, diff);
         float out[MU];
 #pragma unroll
-        for (int b = 0; b < HI; ++b) {                 // label bit b = bit (HI - 1 - b) of the I index
-            double m0 = INFINITY, m1 = INFINITY;
-#pragma unroll
-            for (int k = 0; k < NI; ++k) { if ((k >> (HI - 1 - b)) & 1) m1 = fmin(m1, dI[k]); else m0 = fmin(m0, dI[k]); }
-            out[b] = (float)((m1 - m0) * a.inv_nv);
-        }
-#pragma unroll
-        for (int b = 0; b < HQ; ++b) {
-            double m0 = INFINITY, m1 = INFINITY;
-#pragma unroll
-            for (int k = 0; k < NQ; ++k) { if ((k >> (HQ - 1 - b)) & 1) m1 = fmin(m1, dQ[k]); else m0 = fmin(m0, dQ[k]); }
-            out[HI + b] = (float)((m1 - m0) * a.inv_nv);
-        }
-        if constexpr (MU % 4 == 0) {
-#pragma unroll
-            for (int b = 0; b < MU; b += 4) *(float4*)(a.llr + i * MU + b) = make_float4(out[b], out[b + 1], out[b + 2], out[b + 3]);
-        } else {
-#pragma unroll
-            for (int b = 0; b < MU; b += 2) *(float2*)(a.llr + i * MU + b) = make_float2(out[b], out[b + 1]);
-        }
+        for (int b = 0; b < MU; ++b) out[b] = (float)(diff[b] * a.inv_nv);
+        store_llr<MU>(a.llr, i, out);
     }
-}
-// is the separable table of that binary-indexed kind?
-static bool sep_is_binary(const SepTab& sp, int mu, int& hI, int& hQ) {
-    hI = hQ = 0;
-    while ((1 << hI) < sp.nI) ++hI;
-    while ((1 << hQ) < sp.nQ) ++hQ;
-    if (sp.nI < 2 || sp.nQ < 2 || (1 << hI) != sp.nI || (1 << hQ) != sp.nQ || hI + hQ != mu || hI != hQ) return false;
-    if (sp.maskI != (((1 << hI) - 1) << hQ)) return false;
-    for (int k = 0; k < sp.nI; ++k) if (sp.labI[k] != (k << hQ)) return false;
-    for (int k = 0; k < sp.nQ; ++k) if (sp.labQ[k] != k) return false;
-    return true;
 }
 
 // spectra of the zero-padded chirp partitions, computed with the engine's own FFT
@@ -890,7 +808,7 @@ extern "C" int gf3_equalise_known_h(gf3_ctx* c, const void* d_in, int64_t n_in, 
 }
 
 static int run_demap(gf3_ctx* c, const void* d_sym, int64_t n, uint8_t* bits, uint8_t* idx, float* llr, double nv, void* stream) {
-    DemapArgs a{(const cplx*)d_sym, n, c->cfg.M, c->cfg.mu, c->d_cre, c->d_cim, c->d_clab, bits, llr, nv > 0 ? 1.0 / nv : 0.0, idx, c->sep};
+    DemapArgs a{(const cplx*)d_sym, n, demap_tab(c), bits, llr, nv > 0 ? 1.0 / nv : 0.0, idx};
     int64_t grid = (n + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     if (grid < 1) return GF3_OK;

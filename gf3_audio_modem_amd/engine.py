@@ -431,6 +431,42 @@ class Engine:
         self._check(self.lib.gf3_soft_demap_csi(self._h, _ptr(eq), _ptr(Hs), _ptr(He), F, _ptr(llr), self._stream()))
         return llr
 
+    def _eq_packets(self, eq, who):
+        eq = torch.as_tensor(eq, dtype=torch.complex128).to(self.device).contiguous()
+        per = self.cfg.D * self.cfg.C
+        if eq.numel() % per:
+            raise ValueError(f"{who}: need eq [F*D, C]")
+        return eq, eq.numel() // per
+
+    def noise_estimate(self, eq):
+        """Decision-directed per-carrier noise variance of each packet (gf3_noise_estimate): the mean over the packet's D
+        data symbols of |eq - nearest constellation point|^2, from demod_frames' 'eq' [F*D, C].  -> float64 [F, C];
+        summed in a fixed order, so two calls give identical bits."""
+        eq, F = self._eq_packets(eq, "noise_estimate")
+        var = self._new((F, self.cfg.C), torch.float64)
+        self._check(self.lib.gf3_noise_estimate(self._h, _ptr(eq), F, _ptr(var), self._stream()))
+        return var
+
+    def soft_demap_nw(self, eq, var, out=None):
+        """Noise-weighted max-log LLRs (gf3_soft_demap_nw): maxlog(eq; sigma^2 = 1) / max(var[f, c], 1e-6 mean_c var[f])
+        in one pass over eq [F*D, C] with var [F, C] from noise_estimate; weight 1 for a packet whose mean variance is 0
+        or not finite, LLR 0 on a carrier whose variance is not finite.  -> float32 [F*D*C*mu], order and sign as
+        soft_demap_csi."""
+        cfg = self.cfg
+        eq, F = self._eq_packets(eq, "soft_demap_nw")
+        var = torch.as_tensor(var, dtype=torch.float64).to(self.device).contiguous()
+        if var.numel() != F * cfg.C:
+            raise ValueError("soft_demap_nw: need var [F, C] for eq [F*D, C]")
+        n = F * cfg.D * cfg.C * cfg.mu
+        if out is None:
+            llr = self._new((n,), torch.float32)
+        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
+        else:
+            llr = out
+        self._check(self.lib.gf3_soft_demap_nw(self._h, _ptr(eq), _ptr(var), F, _ptr(llr), self._stream()))
+        return llr
+
     # ------------------------------------------------------------------ host ingest (streams from host memory / longer than HBM)
     def receive_host(self, samples, chunk_samples=1 << 24, list_cap=None):
         """chirp sync + demodulation (the arithmetic of receiver.receive, OFDM.py:581-603) of a stream that lives in

@@ -368,6 +368,24 @@ int gf3_soft_demap_csi(gf3_ctx *ctx, const void *d_eq_c128, const void *d_Hs_c12
                        int64_t F, float *d_llr_f32, void *stream);
 
 /*
+ * Noise-weighted soft demapping (not in the reference): per-carrier effective noise variances measured on the equalised
+ * data symbols themselves, and max-log LLRs divided by them.  Opt-in; gf3_soft_demap_csi is unchanged.
+ *   gf3_noise_estimate:  v[f, c] = (1/D) sum_l |eq[f, l, c] - s|^2, s the constellation point the hard decision picks
+ *     (gf3_demap_hard's rule; a NaN / Inf symbol makes v[f, c] non-finite).  fp64, summed in a fixed order (symbols
+ *     l = w, w + 8, ... ascending for w = 0 .. 7, then the eight partial sums in the order of w): two calls give
+ *     identical bits.
+ *   gf3_soft_demap_nw:  LLR[f, l, c, b] = maxlog(eq[f, l, c]; sigma^2 = 1)[b] * w[f, c] with vbar[f] = mean_c v[f, c] and
+ *     w = 0 where v[f, c] is not finite (the LLR is then +0: an erasure), else 1 for the whole packet where vbar[f] is 0
+ *     or not finite (a noiseless synthetic stream), else 1 / max(v[f, c], 1e-6 vbar[f]).  No |H^|^2 factor: the
+ *     residual is measured after the divide by H^ and already contains it.
+ *   d_eq_c128 [F*D, C] (gf3_demod_frames' d_eq)   d_var_f64 [F, C]   d_llr_f32 [F*D*C*mu], bit order and sign as
+ *   gf3_soft_demap_csi.  F == 0 is a no-op; at most 65535 packets per call.
+ */
+int gf3_noise_estimate(gf3_ctx *ctx, const void *d_eq_c128, int64_t F, double *d_var_f64, void *stream);
+int gf3_soft_demap_nw(gf3_ctx *ctx, const void *d_eq_c128, const double *d_var_f64, int64_t F, float *d_llr_f32,
+                      void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64; the
  * shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, 64) for the circulant whose
  * row z has its one in column (z + s) mod 64.  Block columns 0 .. nb-mb-1 carry the message (systematic part), the
