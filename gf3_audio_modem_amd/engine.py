@@ -50,11 +50,13 @@ def square_qam_table(mu):
 
 
 def map_bits(bits2d, const_points, const_bits):
-    """transmitter.map (OFDM.py:196-197): rows of mu bits -> constellation points."""
+    """transmitter.map (OFDM.py:196-197): rows of mu bits -> constellation points.  A label that no point carries
+    (a table of M < 2^mu points) maps to the table's first point, as gf3_tx_frames maps it."""
     const_bits = np.asarray(const_bits)
+    const_points = np.asarray(const_points, dtype=complex)
     mu = const_bits.shape[1]
     w = 1 << np.arange(mu - 1, -1, -1)
-    lut = np.zeros(1 << mu, dtype=complex)
+    lut = np.full(1 << mu, const_points[0], dtype=complex)
     lut[(const_bits * w).sum(axis=1)] = const_points
     return lut[(np.asarray(bits2d, dtype=np.int64) * w).sum(axis=-1)]
 

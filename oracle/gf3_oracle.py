@@ -81,6 +81,7 @@ class RxParams:
     thresh: float = 0.4           # OFDM.py:361
     fit_lo: int = 500             # OFDM.py:462
     fit_hi: int = 1000            # OFDM.py:462
+    carriers: np.ndarray = None   # data_carriers as an explicit list of 1-based bins, any order (overrides lo, hi)
 
     @property
     def K(self):                  # OFDM.py:28
@@ -104,11 +105,13 @@ class RxParams:
 
     @property
     def data_carriers(self):      # OFDM.py:47
+        if self.carriers is not None:
+            return np.asarray(self.carriers, dtype=np.int64)
         return np.arange(self.lo, self.hi)
 
     @property
     def C(self):
-        return self.hi - self.lo
+        return len(self.data_carriers)
 
     @property
     def frame_len(self):

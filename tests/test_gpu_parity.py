@@ -11,17 +11,9 @@ import pytest
 import torch
 
 from oracle import gf3_oracle as orc
-from tests.util import LOOPBACKS, load, modeA2_params, params_of, unpack
+from tests.util import LOOPBACKS, engine_for, load, modeA2_params, params_of, unpack
 
 pytestmark = pytest.mark.gpu
-
-
-def engine_for(p, in_dtype=torch.float64, **kw):
-    from gf3_audio_modem_amd import Engine, RxConfig
-    cfg = RxConfig(N=p.N, CP=p.CP, P=p.P, D=p.D, data_bins=p.data_carriers, const_points=p.const_points,
-                   const_bits=p.const_bits, known_bits=p.known_bits, in_dtype=in_dtype,
-                   fit_lo=p.fit_lo, fit_hi=p.fit_hi, **kw)
-    return Engine(cfg)
 
 
 @pytest.mark.parametrize("N", [1024, 2048, 4096, 8192])

@@ -287,3 +287,53 @@ def test_facade_file_framing_matches_the_reference_record(tmp_path, monkeypatch,
     framed = load_file(name)
     hdr = f"{name}\0{len(data)}\0".encode("latin-1")
     assert np.array_equal(np.packbits(framed), np.concatenate([np.frombuffer(hdr, np.uint8), data]))
+
+
+# ---- carrier maps given as a list (RxParams.carriers) and tables other than QPSK / square QAM -----------------------
+def test_carrier_list_equal_to_the_band_changes_nothing():
+    """carriers = arange(lo, hi) is the default band: the same stream, byte for byte, and the same receive outputs."""
+    g = load("g1_n1024_qpsk")
+    p = params_of(g)
+    q = params_of(g, lo=1, hi=2, carriers=np.arange(p.lo, p.hi))            # (lo, hi are ignored once a list is given)
+    assert np.array_equal(q.data_carriers, p.data_carriers) and q.C == p.C and q.data_carriers.dtype.kind == "i"
+    payload = unpack(g, "payload", "n_payload")
+    r = orc.tx_stream(payload, g["fill"], q, gaps=g["gaps"], lead=int(g["lead"]), tail=int(g["tail"]))
+    assert np.array_equal(r, g["r"])
+    a, b = orc.receive(g["r"], p), orc.receive(g["r"], q)
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(orc.xor_decode(a["bits"], p), orc.xor_decode(b["bits"], q))
+
+
+def _zoo():
+    from tests import tables as T
+    return T
+
+
+def _loopback_ids():
+    T = _zoo()
+    return [("qam64", m) for m in T.MAPS] + [(t, "shuffled") for t in T.TABLES if t != "qam64"]
+
+
+@pytest.mark.parametrize("table,mp", _loopback_ids())
+def test_oracle_loopback_on_carrier_lists_and_other_tables(table, mp):
+    """tx_stream -> receive returns the payload for every carrier map (scattered, permuted, descending: the bits follow
+    the order of the list) and every table of the zoo; whitening (xor_decode) undoes itself over a list too."""
+    T = _zoo()
+    N, K = 512, 255
+    p = T.params_for(table, N, T.MAPS[mp](K), P=2, D=3, CP=32)
+    rs = np.random.RandomState(len(table) + len(mp))
+    F = 2
+    payload = T.existing_labels_payload(rs, p, F * p.D * p.C)
+    fill = rs.choice(T.QPSK_FILL, size=K - p.C)
+    full = len(p.const_points) == 1 << p.mu                  # (whitening would ask a table with a missing label for it)
+    sent = orc.xor_decode(payload, p) if full else payload
+    r = orc.tx_stream(sent, fill, p, gaps=rs.randint(0, 60, F), lead=11, tail=9)
+    out = orc.receive(r, p)
+    assert len(out["starts"]) == F and out["eq"].shape == (F * p.D, p.C)
+    assert np.array_equal(out["bits"], sent)
+    assert not full or np.array_equal(orc.xor_decode(out["bits"], p), payload)
+    # the data symbols sit on the listed bins in the listed order, the filler on the others
+    X = out["X"][0, p.P, 1:K + 1] / out["Hest"][0, 0]
+    want = orc.map_bits(sent[: p.C * p.mu].reshape(p.C, p.mu), p)
+    assert np.abs(X[p.data_carriers - 1] - want).max() < 1e-6
+    assert np.allclose(np.delete(X, p.data_carriers - 1), fill, rtol=0, atol=1e-6)

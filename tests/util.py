@@ -32,5 +32,15 @@ def modeA2_params(known_bits):
                         const_points=pts, const_bits=bt, known_bits=known_bits)
 
 
+def engine_for(p, in_dtype=None, **kw):
+    """An Engine configured like the oracle parameter block p (GPU tests)."""
+    import torch
+    from gf3_audio_modem_amd import Engine, RxConfig
+    cfg = RxConfig(N=p.N, CP=p.CP, P=p.P, D=p.D, data_bins=p.data_carriers, const_points=p.const_points,
+                   const_bits=p.const_bits, known_bits=p.known_bits, in_dtype=torch.float64 if in_dtype is None else in_dtype,
+                   fit_lo=p.fit_lo, fit_hi=p.fit_hi, **kw)
+    return Engine(cfg)
+
+
 LOOPBACKS = ["g1_n1024_qpsk", "g2_n4096_qpsk", "g3_n4096_16qam_gr5",
              "g7_n4096_qpsk_drift", "g8_n4096_qpsk_gr5_drift"]
