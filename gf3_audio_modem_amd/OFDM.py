@@ -92,6 +92,13 @@ class CamG:
         # latter also leaves the per-carrier SNR estimate [packets, C] in dB in `last_snr_db`
         self.llr_weighting = "csi"
         self.last_snr_db = None
+        # impulse noise (clicks, dropouts) on the "QCLDPC-*" encodings: `interleave` spreads each packet's coded bits over
+        # all its symbols (coded bit i travels at position (i s) mod nbp; encode() / transmit() apply it, decode() /
+        # receive() undo it), llr_weighting = "noise2d" weights by carrier x symbol noise (1 / (v_c v_s / vbar)) and also
+        # leaves the per-symbol SNR estimate [packets, D] in dB in `last_symbol_snr_db`.  Use the two together: an
+        # interleaver alone spreads garbage nobody has marked over every codeword.
+        self.interleave = False
+        self.last_symbol_snr_db = None
         self._engines = {}
 
     def __repr__(self):
@@ -128,8 +135,11 @@ class CamG:
         return self._engine().chirp_replica()
 
     def _qcldpc_rate(self):
-        """Rate of a "QCLDPC-*" encoding, else None."""
-        return QCLDPC_ENCODINGS.get(self.encoding)
+        """Rate of a "QCLDPC-*" encoding, else None.  The interleaver exists on these encodings only."""
+        rate = QCLDPC_ENCODINGS.get(self.encoding)
+        if self.interleave and rate is None:
+            raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        return rate
 
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
@@ -170,7 +180,11 @@ class transmitter(CamG):
         # exactly the missing length, so a seeded run consumes the generator as the reference does
         per_packet = self.packet_length * self.data_bits_per_symbol
         missing = -len(bits) % per_packet
-        return np.concatenate([bits, np.random.binomial(n=1, p=0.5, size=(missing,))])
+        bits = np.concatenate([bits, np.random.binomial(n=1, p=0.5, size=(missing,))])
+        if self.interleave:                                            # whole packets, the fill included
+            sent = self._engine().interleave(torch.from_numpy(bits.astype(np.uint8)))
+            bits = sent.cpu().numpy().astype(bits.dtype)
+        return bits
 
     def SP(self, bits):
         return bits.reshape(-1, self.data_carriers_per_symbol, self.mu)
@@ -369,6 +383,10 @@ class receiver(transmitter):
             # hard-input decoding (LLR = +-1) of the whole codewords in the stream; receive() decodes from soft values
             code = _qcldpc_code(rate)
             b = np.asarray(bits_encoded)
+            if self.interleave:
+                if len(b) % (self.packet_length * self.data_bits_per_symbol):
+                    raise ValueError("interleave: decode() needs whole packets of packet_length * data_bits_per_symbol bits")
+                b = self._engine().interleave(torch.from_numpy(np.ascontiguousarray(b, dtype=np.uint8)), inverse=True).cpu().numpy()
             n_cw = len(b) // code.n
             llr = 1.0 - 2.0 * torch.as_tensor(np.asarray(b[: n_cw * code.n], dtype=np.float32))
             return code.decode(llr, max_iter=self.ldpc_max_iter).cpu().numpy().reshape(-1).astype(np.int64)
@@ -395,8 +413,8 @@ class receiver(transmitter):
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
-        if self.llr_weighting not in ("csi", "noise"):
-            raise ValueError(f"llr_weighting must be 'csi' or 'noise', not {self.llr_weighting!r}")
+        if self.llr_weighting not in ("csi", "noise", "noise2d"):
+            raise ValueError(f"llr_weighting must be 'csi', 'noise' or 'noise2d', not {self.llr_weighting!r}")
         r = _as_samples(signal)
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
@@ -421,15 +439,24 @@ class receiver(transmitter):
         if rate is not None:
             # soft path: weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
             code = _qcldpc_code(rate, eng.device)
-            if self.llr_weighting == "noise":
-                var = eng.noise_estimate(o["eq"])
-                llr = eng.soft_demap_nw(o["eq"], var)
+            if self.llr_weighting in ("noise", "noise2d"):
+                if self.llr_weighting == "noise":
+                    var = eng.noise_estimate(o["eq"])
+                    llr = eng.soft_demap_nw(o["eq"], var)
+                else:
+                    var, var_s = eng.noise_estimate2(o["eq"])
+                    llr = eng.soft_demap_nw2(o["eq"], var, var_s, deinterleave=self.interleave)
                 # SNR report 10 log10(Es / v') with the demapper's floor, [F, C]: rides home in the small copy below
                 pts = self._tables()[0]
-                floored = torch.maximum(var, 1e-6 * var.mean(dim=1, keepdim=True))
-                snr_t = 10.0 * torch.log10(float(np.mean(np.abs(pts) ** 2)) / floored)
+                floor = 1e-6 * var.mean(dim=1, keepdim=True)
+                es = float(np.mean(np.abs(pts) ** 2))
+                snr_t = 10.0 * torch.log10(es / torch.maximum(var, floor))
+                if self.llr_weighting == "noise2d":                 # the same report per symbol, [F, D], behind it
+                    snr_t = torch.cat([snr_t, 10.0 * torch.log10(es / torch.maximum(var_s, floor))], dim=1)
             else:
                 llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
+            if self.interleave and self.llr_weighting != "noise2d":
+                llr = eng.interleave(llr, inverse=True)
             n_cw = llr.numel() // code.n
             bits_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter).reshape(-1)
         else:
@@ -437,7 +464,7 @@ class receiver(transmitter):
         # everything else the host needs, in ONE small copy behind the kernels: first packet's Hs / He, the slopes, and the
         # ragged-packet flag (a packet that runs past the recording: the reference's get_symbols fails on it)
         K, F = self.K, self.no_packets
-        noise = rate is not None and self.llr_weighting == "noise"
+        noise = rate is not None and self.llr_weighting in ("noise", "noise2d")
         small = torch.cat([torch.view_as_real(o["Hs"][0]).reshape(-1), torch.view_as_real(o["He"][0]).reshape(-1), o["slope"]]
                           + ([snr_t.reshape(-1)] if noise else []) + [o["status"].to(torch.float64)])
         host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=True)
@@ -451,7 +478,10 @@ class receiver(transmitter):
         Hest_start0, Hest_end0 = h[: 2 * K].view(np.complex128).copy(), h[2 * K: 4 * K].view(np.complex128).copy()
         self._last_slope = h[4 * K: 4 * K + F].copy()
         if noise:
-            self.last_snr_db = h[4 * K + F: 4 * K + F + snr_t.numel()].reshape(F, -1).copy()
+            rows = h[4 * K + F: 4 * K + F + snr_t.numel()].reshape(F, -1)
+            self.last_snr_db = rows[:, : self.data_carriers_per_symbol].copy()
+            if self.llr_weighting == "noise2d":
+                self.last_symbol_snr_db = rows[:, self.data_carriers_per_symbol:].copy()
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())

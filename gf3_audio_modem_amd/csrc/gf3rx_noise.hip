@@ -1,10 +1,19 @@
 // libgf3rx -- decision-directed per-carrier noise estimate and the noise-weighted soft demapper (gf3_noise_estimate,
-// gf3_soft_demap_nw).  See DESIGN.md §12.
+// gf3_soft_demap_nw), their carrier x symbol forms for impulse noise (gf3_noise_estimate_cs, gf3_soft_demap_nw_cs) and
+// the packet interleaver (gf3_interleave).  See DESIGN.md §12.
 //
 //   v[f, c]   = (1/D) sum_l |eq[f, l, c] - s|^2, s the point the hard decision picks (in-order scan, strict <)
 //   vbar[f]   = mean_c v[f, c]
 //   w[f, c]   = 0 where v is not finite; 1 for the whole packet where vbar is 0 or not finite; else 1 / max(v, 1e-6 vbar)
 //   LLR       = maxlog(eq; sigma^2 = 1) * w   (float32; +0 where w = 0: an erasure, whatever the symbol held)
+//
+//
+// carrier x symbol form (clicks, dropouts: a few whole symbols are garbage):
+//   vs[f, l]  = (1/C) sum_c |eq[f, l, c] - s|^2
+//   w[f,l,c]  = 0 where v[f, c] or vs[f, l] is not finite; else 1 for the whole packet where vbar is 0 or not finite;
+//               else 1 / max(v vs / vbar, 1e-6 vbar)
+// packet interleaver: coded bit i of a packet's nbp = D C mu travels at position pi(i) = (i s) mod nbp, s the smallest
+// integer >= C mu + 1 coprime to nbp.
 //
 // Every sum runs in a fixed order (no floating-point atomics): two runs give identical bits.
 #include "gf3rx_demap.h"
@@ -112,6 +121,208 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_kernel(NoiseArgs a) 
     }
 }
 
+// ---- carrier x symbol estimate ---------------------------------------------------------------------------------
+// noise_estimate_cs: ONE pass over eq gives both variances, so a workgroup owns a whole packet (there is no other way
+// to finish both sums without a second pass or memory shared between workgroups).  16 waves = 2 carrier halves g x 8
+// symbol phases w; lane = carrier as in noise_estimate_kernel: half g holds the 64-carrier columns g ncg .. g ncg + ncg
+// - 1, wave (g, w) walks the symbols l = w, w + 8, ... ascending and reads its ncg columns of each (ncg loads of 1 KB
+// in flight).  Carrier sums: one register per column, added in that symbol order, the 8 phases meet in LDS and are
+// added in the order of w, then / D -- the order of noise_estimate_kernel, so v is the same bits.  Symbol sums: a lane
+// adds its columns' terms in ascending column order, an xor butterfly (32, 16, .. 1) adds the 64 lanes, the two
+// halves meet in LDS and are added g = 0 then 1, then / C.
+constexpr int CS_THREADS = 1024;
+constexpr int CS_MAX_NCG = 16;          // columns per half at most: C <= 2 * 16 * 64
+
+struct NoiseCsArgs {
+    const cplx* eq; double* var_c; double* var_s;
+    int D, C, ncg;
+    DemapTab t;
+};
+
+template <int HI, int NCG>
+__global__ __launch_bounds__(CS_THREADS) void noise_estimate_cs_kernel(NoiseCsArgs a) {
+    extern __shared__ double cs_lds[];              // [8][C] carrier partial sums, [D][2] symbol partial sums
+    double* part = cs_lds;
+    double* spart = cs_lds + 8 * (size_t)a.C;
+    const int lane = threadIdx.x & 63, w = (threadIdx.x >> 6) & 7, g = threadIdx.x >> 9;
+    const int64_t f = blockIdx.x;
+    const Levels<HI> lv(a.t);
+    const cplx* p = a.eq + (f * a.D) * (int64_t)a.C;
+    double acc[NCG];
+#pragma unroll
+    for (int k = 0; k < NCG; ++k) acc[k] = 0.0;
+    // the lane's carrier in column k of its half is c0 + 64 k: taken while it is below cend (the load of any other slot
+    // takes carrier 0 and its term is dropped)
+    const int c0 = g * a.ncg * 64 + lane, cend = min(a.C, (g + 1) * a.ncg * 64);
+    for (int l = w; l < a.D; l += 8) {
+        const cplx* row = p + (int64_t)l * a.C;
+        double srow = 0.0;
+        constexpr int NB = NCG > 8 ? 4 : NCG;         // loads in flight per batch (more would spill: 128 VGPRs at 16 waves)
+#pragma unroll
+        for (int k0 = 0; k0 < NCG; k0 += NB) {
+            cplx e[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) e[k] = row[c0 + 64 * (k0 + k) < cend ? c0 + 64 * (k0 + k) : 0];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) {
+                double d2;
+                if constexpr (HI > 0) d2 = axis_min_d2<(1 << HI)>(e[k].x, lv.lvI) + axis_min_d2<(1 << HI)>(e[k].y, lv.lvQ);
+                else d2 = table_min_d2(e[k], a.t.cre, a.t.cim, a.t.M);
+                d2 = c0 + 64 * (k0 + k) < cend ? d2 : 0.0;
+                acc[k0 + k] += d2;
+                srow += d2;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) srow += __shfl_xor(srow, off);
+        if (lane == 0) spart[2 * l + g] = srow;
+    }
+#pragma unroll
+    for (int k = 0; k < NCG; ++k)
+        if (c0 + 64 * k < cend) part[(size_t)w * a.C + c0 + 64 * k] = acc[k];
+    __syncthreads();
+    for (int c = threadIdx.x; c < a.C; c += CS_THREADS) {
+        double s = part[c];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) s += part[(size_t)k * a.C + c];
+        a.var_c[f * a.C + c] = s / (double)a.D;
+    }
+    for (int l = threadIdx.x; l < a.D; l += CS_THREADS)
+        a.var_s[f * a.D + l] = (spart[2 * l] + spart[2 * l + 1]) / (double)a.C;
+}
+
+// ---- packet interleaver ----------------------------------------------------------------------------------------
+// pi(i) = (i s) mod nbp and its inverse pi^-1(p) = (p s^-1) mod nbp.  Kernels never divide per element: a thread takes
+// one 64-bit product modulo nbp for its first element and walks on by precomputed steps with a conditional subtract
+// (nbp < 2^31, so the sums fit 32 bits).
+struct Perm { uint32_t nbp, s, sinv; };              // s, sinv already reduced modulo nbp
+
+GF3_DEV uint32_t addmod(uint32_t x, uint32_t step, uint32_t n) { x += step; return x >= n ? x - n : x; }
+
+bool perm_of(const gf3_ctx* c, Perm& p) {
+    const int64_t B = (int64_t)c->cfg.C * c->cfg.mu, nbp = B * c->cfg.D;
+    if (nbp < 1 || nbp >= (int64_t)1 << 31) return false;
+    auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t r = x % y; x = y; y = r; } return x; };
+    int64_t s = B + 1;
+    while (gcd(s, nbp) != 1) ++s;
+    // extended Euclid: s x == 1 (mod nbp)
+    int64_t r0 = nbp, r1 = s % nbp, x0 = 0, x1 = 1;
+    while (r1) { const int64_t q = r0 / r1, r = r0 - q * r1, x = x0 - q * x1; r0 = r1; r1 = r; x0 = x1; x1 = x; }
+    p.nbp = (uint32_t)nbp; p.s = (uint32_t)(s % nbp); p.sinv = (uint32_t)(((x0 % nbp) + nbp) % nbp);
+    return true;
+}
+
+constexpr int IL_THREADS = 256, IL_PER = 8;          // elements per thread, 256 apart
+
+// out[f, j] = in[f, (j m) mod nbp]: m = s undoes the interleaver, m = s^-1 applies it.  Stores are contiguous, loads strided.
+template <typename T>
+__global__ __launch_bounds__(IL_THREADS) void interleave_kernel(const T* in, T* out, uint32_t nbp, uint32_t m, uint32_t step) {
+    const int64_t base = (int64_t)blockIdx.y * nbp;
+    const uint64_t j0 = (uint64_t)blockIdx.x * (IL_THREADS * IL_PER) + threadIdx.x;
+    if (j0 >= nbp) return;
+    uint32_t idx = (uint32_t)((j0 * m) % nbp);
+#pragma unroll
+    for (int u = 0; u < IL_PER; ++u) {
+        const uint64_t j = j0 + (uint64_t)u * IL_THREADS;
+        if (j < nbp) out[base + j] = in[base + idx];
+        idx = addmod(idx, step, nbp);
+    }
+}
+
+// ---- carrier x symbol demapper ---------------------------------------------------------------------------------
+// soft_demap_nw_cs: soft_demap_nw_kernel with the weight 1 / max(v vs / vbar, floor) formed per symbol from two factors
+// kept in LDS: ic[c] = vbar / v[c] and is[l] = 1 / vs[l] (0 marks an erasure, 1 a flat packet), w = ic is capped at
+// 1 / floor -- one multiply and a compare per symbol, no division in the stream.  vbar comes from the same tree as in
+// soft_demap_nw_kernel: the same bits there, here, and in every workgroup of the packet.  DEINT: each LLR goes to its
+// coded position pi^-1(p) of the packet instead of its transmitted position p.
+struct NwCsArgs {
+    const cplx* eq; const double* var_c; const double* var_s; float* llr;
+    int D, C, Dc;
+    uint32_t nbp, sinv, step_c, step_l;             // DEINT: (256 mu s^-1) mod nbp, (C mu s^-1) mod nbp
+    DemapTab t;
+};
+
+template <int HI, bool DEINT>
+__global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_cs_kernel(NwCsArgs a) {
+    extern __shared__ double nw_lds[];              // [256] partial sums, [C] carrier factors, [Dc] symbol factors
+    double* red = nw_lds;
+    double* ic = nw_lds + NW_THREADS;
+    double* is = ic + a.C;
+    const int t = threadIdx.x, C = a.C;
+    const int64_t f = blockIdx.y;
+    const double* v = a.var_c + f * C;
+    const int l0 = blockIdx.x * a.Dc, l1 = min(l0 + a.Dc, a.D);
+    double s = 0.0;
+    for (int c = t; c < C; c += NW_THREADS) s += v[c];
+    red[t] = s;
+    __syncthreads();
+#pragma unroll
+    for (int h = NW_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
+    }
+    const double vbar = red[0] / (double)C;
+    const bool flat = !(vbar > 0.0) || !(vbar < INFINITY);          // 0, NaN, Inf: the packet's weights are 1
+    const double wmax = flat ? 1.0 : 1.0 / (1e-6 * vbar);
+    for (int c = t; c < C; c += NW_THREADS) {
+        const double x = v[c];
+        ic[c] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : vbar / x;
+    }
+    for (int l = l0 + t; l < l1; l += NW_THREADS) {
+        const double x = a.var_s[f * a.D + l];
+        is[l - l0] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : 1.0 / x;
+    }
+    __syncthreads();
+    const Levels<HI> lv(a.t);
+    const int mu = a.t.mu;
+    float* pk = a.llr + f * (int64_t)a.nbp;         // DEINT: the packet's LLRs
+    uint32_t irow = 0;                              // DEINT: coded position of bit 0 of (l, carrier t)
+    if constexpr (DEINT) irow = (uint32_t)(((uint64_t)((int64_t)l0 * C + t) * (uint64_t)mu % a.nbp) * a.sinv % a.nbp);
+    for (int l = l0; l < l1; ++l) {
+        const int64_t row = (f * a.D + l) * (int64_t)C;
+        const double sl = is[l - l0];
+        uint32_t i0 = irow;
+        for (int c = t; c < C; c += NW_THREADS) {
+            const cplx e = a.eq[row + c];
+            const double cf = ic[c], pr = cf * sl;
+            // a zero factor: erasure; pr not below the cap (v vs / vbar under the floor, Inf from a zero variance) or not
+            // positive: the cap
+            const double w = (cf == 0.0 || sl == 0.0) ? 0.0 : (pr > 0.0 && pr < wmax) ? pr : wmax;
+            if constexpr (HI > 0) {
+                constexpr int MU = 2 * HI;
+                double diff[MU];
+                maxlog_bin<HI, HI>(e, lv.lvI, lv.lvQ, diff);
+                float out[MU];
+#pragma unroll
+                for (int b = 0; b < MU; ++b) out[b] = w == 0.0 ? 0.0f : (float)(diff[b] * w);
+                if constexpr (DEINT) {
+                    uint32_t i = i0;
+#pragma unroll
+                    for (int b = 0; b < MU; ++b) { pk[i] = out[b]; i = addmod(i, a.sinv, a.nbp); }
+                } else store_llr<MU>(a.llr, row + c, out);
+            } else {
+                float out[8];
+#pragma unroll
+                for (int b = 0; b < 8; ++b) out[b] = 0.0f;
+                if (w != 0.0) maxlog_table(e, a.t, w, out);
+                if constexpr (DEINT) {
+                    uint32_t i = i0;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        if (b < mu) { pk[i] = out[b]; i = addmod(i, a.sinv, a.nbp); }
+                } else {
+                    float* dst = a.llr + (row + c) * mu;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        if (b < mu) dst[b] = out[b];
+                }
+            }
+            if constexpr (DEINT) i0 = addmod(i0, a.step_c, a.nbp);
+        }
+        if constexpr (DEINT) irow = addmod(irow, a.step_l, a.nbp);
+    }
+}
+
 // binary-indexed grid up to 64-QAM -> its HI, anything else -> 0 (as run_demap chooses its kernels)
 int grid_bits(const gf3_ctx* c) {
     int hI = 0, hQ = 0;
@@ -159,6 +370,85 @@ extern "C" int gf3_soft_demap_nw(gf3_ctx* c, const void* d_eq, const double* d_v
         case 3: hipLaunchKernelGGL(soft_demap_nw_kernel<3>, grid, block, lds, st, a); break;
         default: hipLaunchKernelGGL(soft_demap_nw_kernel<0>, grid, block, lds, st, a); break;
     }
+    HIPCHK(c, hipGetLastError());
+    return GF3_OK;
+}
+
+// (NCG in steps of 4: a slot beyond the half's columns costs a repeated load of carrier 0)
+template <int HI>
+hipError_t launch_noise_cs(const NoiseCsArgs& a, int64_t F, size_t lds, hipStream_t st) {
+    if (a.ncg <= 4) return launch(noise_estimate_cs_kernel<HI, 4>, F, CS_THREADS, lds, st, a);
+    if (a.ncg <= 8) return launch(noise_estimate_cs_kernel<HI, 8>, F, CS_THREADS, lds, st, a);
+    if (a.ncg <= 12) return launch(noise_estimate_cs_kernel<HI, 12>, F, CS_THREADS, lds, st, a);
+    return launch(noise_estimate_cs_kernel<HI, 16>, F, CS_THREADS, lds, st, a);
+}
+
+extern "C" int gf3_noise_estimate_cs(gf3_ctx* c, const void* d_eq, int64_t F, double* d_var_c, double* d_var_s, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_eq || !d_var_c || !d_var_s || F < 0) return fail(c, GF3_EINVAL, "gf3_noise_estimate_cs: bad argument");
+    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_noise_estimate_cs: at most 65535 packets per call");
+    NoiseCsArgs a{(const cplx*)d_eq, d_var_c, d_var_s, c->cfg.D, c->cfg.C, 0, demap_tab(c)};
+    a.ncg = ((a.C + 63) / 64 + 1) / 2;
+    const size_t lds = (8 * (size_t)a.C + 2 * (size_t)a.D) * sizeof(double);
+    if (a.ncg > CS_MAX_NCG || lds > 160 * 1024)
+        return fail(c, GF3_ERANGE, "gf3_noise_estimate_cs: a packet's partial sums (64 C + 16 D bytes) must fit 160 KB of LDS, C <= 2048");
+    hipStream_t st = (hipStream_t)stream;
+    switch (grid_bits(c)) {
+        case 1: HIPCHK(c, launch_noise_cs<1>(a, F, lds, st)); break;
+        case 2: HIPCHK(c, launch_noise_cs<2>(a, F, lds, st)); break;
+        case 3: HIPCHK(c, launch_noise_cs<3>(a, F, lds, st)); break;
+        default: HIPCHK(c, launch_noise_cs<0>(a, F, lds, st)); break;
+    }
+    return GF3_OK;
+}
+
+extern "C" int gf3_soft_demap_nw_cs(gf3_ctx* c, const void* d_eq, const double* d_var_c, const double* d_var_s, int64_t F,
+                                    int32_t deinterleave, float* d_llr, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_eq || !d_var_c || !d_var_s || !d_llr || F < 0 || (deinterleave != 0 && deinterleave != 1))
+        return fail(c, GF3_EINVAL, "gf3_soft_demap_nw_cs: bad argument");
+    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_soft_demap_nw_cs: at most 65535 packets per call");
+    Perm pm;
+    if (!perm_of(c, pm)) return fail(c, GF3_ERANGE, "gf3_soft_demap_nw_cs: D C mu must be below 2^31");
+    NwCsArgs a{(const cplx*)d_eq, d_var_c, d_var_s, d_llr, c->cfg.D, c->cfg.C, 0, pm.nbp, pm.sinv, 0, 0, demap_tab(c)};
+    a.step_c = (uint32_t)((uint64_t)NW_THREADS * c->cfg.mu % pm.nbp * pm.sinv % pm.nbp);
+    a.step_l = (uint32_t)((uint64_t)a.C * c->cfg.mu % pm.nbp * pm.sinv % pm.nbp);
+    int64_t nchunk = (8 * (int64_t)c->n_cu + F - 1) / F;            // as gf3_soft_demap_nw
+    if (nchunk > a.D) nchunk = a.D;
+    if (nchunk < 1) nchunk = 1;
+    a.Dc = (int)((a.D + nchunk - 1) / nchunk);
+    const dim3 grid((unsigned)((a.D + a.Dc - 1) / a.Dc), (unsigned)F), block(NW_THREADS);
+    const size_t lds = (size_t)(NW_THREADS + a.C + a.Dc) * sizeof(double);
+    hipStream_t st = (hipStream_t)stream;
+#define GF3_NWCS(HI) do { if (deinterleave) hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, true>), grid, block, lds, st, a); \
+                          else hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, false>), grid, block, lds, st, a); } while (0)
+    switch (grid_bits(c)) {
+        case 1: GF3_NWCS(1); break;
+        case 2: GF3_NWCS(2); break;
+        case 3: GF3_NWCS(3); break;
+        default: GF3_NWCS(0); break;
+    }
+#undef GF3_NWCS
+    HIPCHK(c, hipGetLastError());
+    return GF3_OK;
+}
+
+extern "C" int gf3_interleave(gf3_ctx* c, const void* d_in, void* d_out, int64_t F, int32_t elem_bytes, int32_t inverse, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_in || !d_out || d_in == d_out || F < 0 || (elem_bytes != 1 && elem_bytes != 4) || (inverse != 0 && inverse != 1))
+        return fail(c, GF3_EINVAL, "gf3_interleave: bad argument (elem_bytes 1 or 4, inverse 0 or 1, out of place)");
+    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_interleave: at most 65535 packets per call");
+    Perm pm;
+    if (!perm_of(c, pm)) return fail(c, GF3_ERANGE, "gf3_interleave: D C mu must be below 2^31");
+    const uint32_t m = inverse ? pm.s : pm.sinv;
+    const uint32_t step = (uint32_t)((uint64_t)IL_THREADS % pm.nbp * m % pm.nbp);
+    const dim3 grid((pm.nbp + IL_THREADS * IL_PER - 1) / (IL_THREADS * IL_PER), (unsigned)F), block(IL_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4) hipLaunchKernelGGL(interleave_kernel<uint32_t>, grid, block, 0, st, (const uint32_t*)d_in, (uint32_t*)d_out, pm.nbp, m, step);
+    else hipLaunchKernelGGL(interleave_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)d_in, (uint8_t*)d_out, pm.nbp, m, step);
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }

@@ -469,6 +469,54 @@ class Engine:
         self._check(self.lib.gf3_soft_demap_nw(self._h, _ptr(eq), _ptr(var), F, _ptr(llr), self._stream()))
         return llr
 
+    def noise_estimate2(self, eq):
+        """Per-carrier AND per-symbol noise variance of each packet from one pass over eq [F*D, C]
+        (gf3_noise_estimate_cs): var_c [F, C] is noise_estimate's output bit for bit, var_s [F, D] the mean over the
+        carriers of the same residuals.  Fixed summation order: two calls give identical bits."""
+        eq, F = self._eq_packets(eq, "noise_estimate2")
+        var_c = self._new((F, self.cfg.C), torch.float64)
+        var_s = self._new((F, self.cfg.D), torch.float64)
+        self._check(self.lib.gf3_noise_estimate_cs(self._h, _ptr(eq), F, _ptr(var_c), _ptr(var_s), self._stream()))
+        return var_c, var_s
+
+    def soft_demap_nw2(self, eq, var_c, var_s, deinterleave=False, out=None):
+        """Carrier x symbol noise-weighted max-log LLRs (gf3_soft_demap_nw_cs): maxlog(eq; sigma^2 = 1) /
+        max(var_c[f, c] var_s[f, l] / vbar[f], 1e-6 vbar[f]), vbar = mean_c var_c; weight 1 for a packet whose vbar is 0
+        or not finite, LLR 0 where var_c or var_s is not finite.  deinterleave: write each packet's LLRs in coded order
+        (the packet interleaver undone), else in transmitted order.  -> float32 [F*D*C*mu], sign as soft_demap_csi."""
+        cfg = self.cfg
+        eq, F = self._eq_packets(eq, "soft_demap_nw2")
+        var_c = torch.as_tensor(var_c, dtype=torch.float64).to(self.device).contiguous()
+        var_s = torch.as_tensor(var_s, dtype=torch.float64).to(self.device).contiguous()
+        if var_c.numel() != F * cfg.C or var_s.numel() != F * cfg.D:
+            raise ValueError("soft_demap_nw2: need var_c [F, C] and var_s [F, D] for eq [F*D, C]")
+        n = F * cfg.D * cfg.C * cfg.mu
+        if out is None:
+            llr = self._new((n,), torch.float32)
+        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
+        else:
+            llr = out
+        self._check(self.lib.gf3_soft_demap_nw_cs(self._h, _ptr(eq), _ptr(var_c), _ptr(var_s), F, int(bool(deinterleave)),
+                                                  _ptr(llr), self._stream()))
+        return llr
+
+    def interleave(self, x, inverse=False):
+        """The packet interleaver on whole packets of nbp = D*C*mu elements (gf3_interleave): x is uint8 or float32 with a
+        multiple of nbp elements; coded element i of a packet moves to position (i s) mod nbp, `inverse` moves it back.
+        -> a new tensor of x's shape and dtype."""
+        x = torch.as_tensor(x)
+        if x.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("interleave: x must be uint8 or float32")
+        x = x.to(self.device).contiguous()
+        nbp = self.cfg.D * self.cfg.C * self.cfg.mu
+        if x.numel() % nbp:
+            raise ValueError(f"interleave: need whole packets of D*C*mu = {nbp} elements")
+        out = self._new(tuple(x.shape), x.dtype)
+        self._check(self.lib.gf3_interleave(self._h, _ptr(x), _ptr(out), x.numel() // nbp, x.element_size(), int(bool(inverse)),
+                                            self._stream()))
+        return out
+
     # ------------------------------------------------------------------ host ingest (streams from host memory / longer than HBM)
     def receive_host(self, samples, chunk_samples=1 << 24, list_cap=None):
         """chirp sync + demodulation (the arithmetic of receiver.receive, OFDM.py:581-603) of a stream that lives in

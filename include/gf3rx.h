@@ -386,6 +386,34 @@ int gf3_soft_demap_nw(gf3_ctx *ctx, const void *d_eq_c128, const double *d_var_f
                       void *stream);
 
 /*
+ * Impulse noise (clicks, dropouts: a few whole data symbols are garbage): the carrier x symbol form of the pair above and
+ * a packet-wide bit interleaver.  The two only work together: spread over every codeword, unmarked garbage is worse
+ * than garbage left in place.  Opt-in; the entry points above are unchanged.  (The names carry no digit because the
+ * project's ABI check reads the header's declarations as lower-case words: "cs" = carrier x symbol.)
+ *   gf3_noise_estimate_cs:  one pass over eq gives v[f, c] as gf3_noise_estimate does -- the same bits -- and
+ *     vs[f, l] = (1/C) sum_c |eq[f, l, c] - s|^2.  fp64, fixed order (a lane adds the terms of its carriers c = 64 k +
+ *     lane for the columns k of its half of the carriers ascending, an xor butterfly 32, 16, .. 1 adds the 64 lanes,
+ *     then first half + second half): two calls give identical bits.  One workgroup per packet keeps 64 C + 16 D bytes
+ *     of partial sums in LDS: GF3_ERANGE beyond 160 KB or C > 2048.
+ *   gf3_soft_demap_nw_cs:  LLR = maxlog(eq; sigma^2 = 1) * w[f, l, c] with vbar[f] = mean_c v[f, c] (the number
+ *     gf3_soft_demap_nw uses) and w = 0 where v[f, c] or vs[f, l] is not finite (+0: an erasure), else 1 for the whole
+ *     packet where vbar[f] is 0 or not finite, else 1 / max(v[f, c] vs[f, l] / vbar[f], 1e-6 vbar[f]).
+ *     deinterleave = 0: LLRs in transmitted order, as gf3_soft_demap_nw writes them.  1: the LLR of transmitted position
+ *     pi(i) is written at coded position i of its packet -- bit for bit gf3_interleave(inverse = 1) of the former.
+ *   gf3_interleave:  the bare permutation of [F, nbp] arrays of 1- or 4-byte elements, nbp = D C mu per packet.  Coded
+ *     bit i travels at position pi(i) = (i s) mod nbp, s the smallest integer >= C mu + 1 with gcd(s, nbp) = 1 (2801 for
+ *     2800 bits per symbol and D = 180): consecutive coded bits land in consecutive symbols.
+ *     inverse = 0: out[pi(i)] = in[i] (transmit side).  1: out[i] = in[pi(i)].  Out of place; nbp < 2^31.
+ *   d_var_c_f64 [F, C]   d_var_s_f64 [F, D]   F == 0 is a no-op; at most 65535 packets per call.
+ */
+int gf3_noise_estimate_cs(gf3_ctx *ctx, const void *d_eq_c128, int64_t F, double *d_var_c_f64, double *d_var_s_f64,
+                          void *stream);
+int gf3_soft_demap_nw_cs(gf3_ctx *ctx, const void *d_eq_c128, const double *d_var_c_f64, const double *d_var_s_f64,
+                         int64_t F, int32_t deinterleave, float *d_llr_f32, void *stream);
+int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32_t elem_bytes, int32_t inverse,
+                   void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64; the
  * shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, 64) for the circulant whose
  * row z has its one in column (z + s) mod 64.  Block columns 0 .. nb-mb-1 carry the message (systematic part), the
