@@ -147,8 +147,9 @@ GF3_DEV void corr_window(const CorrArgs& a, const int64_t b, double2* smem) {
 }
 // LISTED: the windows are those of a device-side list (the screened sync's unresolved windows, gf3rx_fscreen.h), whose
 // length lives on the device: the grid is the list's capacity and workgroups past its length return at once (65 536 empty
-// workgroups are ~25 us; a persistent grid walking the list was tried -- the loop's invariants spill 4-36 registers of a
-// kernel that has none to spare).  The plain instantiation is the kernel it was.
+// workgroups are ~25 us).  A bounded grid whose workgroups walk the list, the last of them zeroing the length for the next
+// call, was built twice: the loop's invariants spill 2-37 vector and 31-44 scalar registers of a kernel that has none to
+// spare (the compiler's resource report, every instantiation).  The plain instantiation is the kernel it was.
 template <int NC, int DT, bool LISTED = false>
 __global__ __launch_bounds__(NC / 8, 2) void corr_kernel(CorrArgs a) {
     extern __shared__ double2 smem[];

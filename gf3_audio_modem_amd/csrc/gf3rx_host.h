@@ -6,7 +6,7 @@
 //   gf3rx_demod_split.hip, gf3rx_dsplit_{qpsk,scan,full}.hip   the two-phase demodulation of long packets
 //   gf3rx_corr.hip           corr_kernel, spec_kernel, ols_kernel
 //   gf3rx_screen.hip         scr_ring_kernel, scr_ols_kernel, scr_refine_kernel (gf3rx_screen.h)
-//   gf3rx_fscreen.hip        corr_screen_kernel: the opt-in fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
+//   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
 //   gf3rx_stamp.cpp          the build stamp (source hash), recompiled on every change
 //   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide
 //   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
@@ -22,6 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 #include "gf3rx.h"
@@ -189,10 +191,19 @@ struct gf3_ctx {
     // single-precision screening plan of the frames-mode sync (gf3rx_fscreen.h): 2048-sample transforms, partitions of 2048 - wmax + 1 taps
     struct { bool ok = false; int Q = 0, Lp = 0, wmax = 0; cf *d_tw = nullptr, *d_twn = nullptr; float4* d_Hs = nullptr;
              float *d_H0N = nullptr, *d_Hinf = nullptr; } fscr;
-    // The ONLY field a call may write after gf3_ctx_create: the default evaluation mode of the legacy entry point
+    // Two things a call may write after gf3_ctx_create.  (i) The default evaluation mode of the legacy entry point
     // gf3_sync_stream (gf3_sync_stream_mode sets it; gf3_sync_stream_ex takes the mode per call and never reads it).
     // 0: by stream length (screen from GF3_SCR_MIN_SAMPLES on); 1: fp64 only; 2: screen whenever a plan exists; 3: as 2 with the general kernel
     std::atomic<int> default_stream_mode{0};
+    // (ii) The workspaces of the frames-mode sync in auto mode (gf3_sync_frames; sync_frames_impl), under fs_mu: one
+    // [count | pad | F window numbers] buffer per (stream, host thread), created on first use and grow-only.  Calls of one
+    // thread on one stream share a buffer through stream order; other streams and other threads have their own.  A buffer
+    // that is outgrown may still be read by a queued kernel: it goes to fs_retired, which gf3_ctx_destroy frees after a
+    // device synchronise.
+    struct FsWork { hipStream_t stream; std::thread::id thread; void* d = nullptr; int64_t bytes = 0; };
+    std::mutex fs_mu;
+    std::vector<FsWork> fs_work;
+    std::vector<void*> fs_retired;
     std::vector<double> chirp;
     std::vector<cplx> known_pts;
 };

@@ -261,12 +261,16 @@ class Engine:
             _ptr(o["slope"]), _ptr(o.get("Hest")), _ptr(o["bits"]), self._stream()))
         return o
 
-    def sync_frames(self, x, F, stride, win_lo, win_hi, want_peak=False, out_starts=None, screened=False, work=None):
+    def sync_frames(self, x, F, stride, win_lo, win_hi, want_peak=False, out_starts=None, screened=None, work=None):
         """Batched windowed chirp sync: first-pilot sample index per frame (int64, -1 = none).
         out_starts: optional preallocated int64 [F] device tensor to write into.
-        screened: evaluate the windows in fp32 with a proven bound first (gf3_sync_frames_ex mode 1) and run the fp64
-        kernel only on the windows the bound cannot decide: the same indices.  work: optional preallocated uint8 workspace
-        (gf3_sync_frames_workspace_bytes; its first int32 then holds the number of windows that went to fp64)."""
+        screened: None (default): the library decides (gf3_sync_frames_ex mode -1) -- the windows are evaluated in fp32 with
+        a proven bound first, in a workspace the library keeps per stream, and the fp64 kernel runs only on the windows the
+        bound cannot decide: the all-fp64 indices.  False: the all-fp64 kernel on every window (mode 0).  True: the screen in
+        the caller's workspace (mode 1).  work: uint8 workspace of sync_frames_workspace(F) for screened=True (allocated
+        here when absent); its first int32 then holds the number of windows that went to fp64.
+        want_peak: the fp64 peak VALUES are asked for, so the all-fp64 kernel runs whatever `screened` says (and a `work`
+        given reports 0).  sync_frames_last() tells which way a call went."""
         x = self._samples(x)
         if out_starts is not None:
             if out_starts.dtype != torch.int64 or out_starts.numel() != F or not out_starts.is_contiguous():
@@ -277,9 +281,20 @@ class Engine:
         peak = self._new((F,), torch.float64) if want_peak else None
         if screened and work is None:
             work = self.sync_frames_workspace(F)
+        if screened and (work.dtype != torch.uint8 or not work.is_contiguous() or not work.is_cuda
+                         or work.numel() < int(self.lib.gf3_sync_frames_workspace_bytes(self._h, F))):
+            raise ValueError("work must be a contiguous uint8 device tensor of at least sync_frames_workspace(F) bytes")
+        mode = -1 if screened is None else (1 if screened else 0)
         self._check(self.lib.gf3_sync_frames_ex(self._h, _ptr(x), x.numel(), F, stride, win_lo, win_hi,
-                                                _ptr(starts), _ptr(peak), 1 if screened else 0, _ptr(work) if screened else None, self._stream()))
+                                                _ptr(starts), _ptr(peak), mode, _ptr(work) if screened else None, self._stream()))
         return (starts, peak) if want_peak else starts
+
+    def sync_frames_last(self):
+        """Of the calling thread's last sync_frames call on the current stream: dict(path = 0 screened | 2 all fp64 | -1 no
+        such call, unresolved_capacity = windows its fp64 pass could take).  No device read."""
+        path, cap = C.c_int32(-1), C.c_int32(0)
+        self._check(self.lib.gf3_sync_frames_last(self._h, self._stream(), C.byref(path), C.byref(cap)))
+        return dict(path=int(path.value), unresolved_capacity=int(cap.value))
 
     def sync_frames_workspace(self, F):
         return self._new((int(self.lib.gf3_sync_frames_workspace_bytes(self._h, F)),), torch.uint8)

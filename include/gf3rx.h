@@ -16,14 +16,16 @@
  *     look-up tables.  `stream` is a hipStream_t passed as void* (NULL = the
  *     default stream).  All work is enqueued asynchronously on that stream;
  *     only gf3_sync_stream synchronises (it returns a count to the host).
- *   - a context is immutable after creation: no call writes into it, so
+ *   - a context's tables and plans are immutable after creation, so
  *     concurrent calls on one context from different host threads / on
  *     different streams are safe (every call brings its own workspace and
  *     outputs; error text and diagnostics are kept per calling THREAD, not in
  *     the context, and so are the 256 bytes of pinned host memory the calls
- *     that return counts read them back into).  The one exception is the legacy convenience
+ *     that return counts read them back into).  Two exceptions: the legacy convenience
  *     gf3_sync_stream_mode, which stores a default mode for the legacy entry
- *     point gf3_sync_stream; gf3_sync_stream_ex takes the mode per call.
+ *     point gf3_sync_stream (gf3_sync_stream_ex takes the mode per call), and
+ *     the small workspaces gf3_sync_frames keeps in the context, one per
+ *     (stream, host thread), under a mutex of the context's own.
  *   - complex128 arrays are interleaved (re, im) doubles, as NumPy stores them.
  */
 #ifndef GF3RX_H
@@ -181,29 +183,46 @@ int gf3_equalise(gf3_ctx *ctx, const void *d_data, const void *d_start, const vo
  * correlation normalised by the window maximum, first local extremum above
  * `thresh`.  d_starts[f] = sample index of the first pilot symbol (chirp start +
  * Lc), ready to be passed to gf3_demod_frames; -1 where nothing qualifies.
+ *
+ * This entry point is gf3_sync_frames_ex in mode -1 (auto): the indices are those of the all-fp64 kernel, taken in fp32
+ * wherever a proven bound decides them (see below), in a workspace the context owns.
  */
 int gf3_sync_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in,
                     int64_t F, int64_t stride, int32_t win_lo, int32_t win_hi,
                     int64_t *d_starts, double *d_peak_or_null, void *stream);
 
 /*
- * The same search with an fp32 SCREEN in front (gf3rx_fscreen.h), opt-in: mode 1 evaluates every window in single
+ * The same search with the evaluation chosen per call.  The fp32 SCREEN (gf3rx_fscreen.h) evaluates every window in single
  * precision with a proven bound on |fp32 lag - exact lag| (2048-sample transforms held by one wave each, the chirp's
  * partition spectra multiplied in, one inverse transform) and takes the decision -- the index of the first extremum above
  * thresh x the window's maximum -- only where the bound decides it: every lag is certainly out, certainly in, or undecided,
  * and a window is resolved when no undecided lag precedes the first certain one.  Unresolved windows (noise at the threshold,
  * flat tops, non-finite samples, a maximum the bound cannot tell from zero) are listed on the device and the all-fp64 kernel
  * runs on exactly those.  No decision rests on an fp32 value the bound does not back: d_starts is what mode 0 writes.
- *   mode    0: all fp64 (== gf3_sync_frames)   1: screened
- *   d_work  gf3_sync_frames_workspace_bytes(ctx, F) bytes of device memory (mode 1; NULL selects mode 0); after the call its
- *           first int32 holds the number of windows that went to the fp64 kernel
- * Falls back to mode 0 when d_peak is asked for (an fp64 VALUE), when the window is wider than the context's max_window or
- * than 1024 lags, and when F exceeds 2^31.
+ *   mode   -1: auto (== gf3_sync_frames).  The screen, in a workspace the context keeps for the calling thread on this
+ *              stream (created on first use, grow-only: a call with a larger F than any before it on that stream allocates
+ *              device memory; outgrown buffers are freed by gf3_ctx_destroy).  Calls of one thread on one stream share the
+ *              workspace through stream order; other streams and threads have their own, at most 64 per context.
+ *              All fp64 instead when the screen does not apply (below), and when no workspace can be had: the stream is
+ *              being captured into a graph and no large-enough workspace exists yet (nothing is allocated under capture:
+ *              call once with the largest F before capturing), the allocation fails, or all 64 are taken.  d_work is ignored.
+ *           0: all fp64: the all-fp64 kernel on every window (the reference the screen is tested against)
+ *           1: the screen in the CALLER's workspace d_work (NULL selects mode 0)
+ *   d_work  mode 1: AT LEAST gf3_sync_frames_workspace_bytes(ctx, F) bytes of device memory -- the library cannot check the
+ *           size of a device pointer, a smaller buffer is written past its end.  After the call its first int32 holds the
+ *           number of windows that went to the fp64 kernel (0 when the call ran all fp64 for one of the reasons below).
+ * The screen does not apply -- every mode then runs all fp64 -- when d_peak is asked for (an fp64 VALUE), when the window is
+ * wider than the context's max_window or than 1024 lags, and when F exceeds 2^31.
+ *
+ * gf3_sync_frames_last: what the CALLING THREAD's last gf3_sync_frames / gf3_sync_frames_ex call did, if that call was on
+ * this context and stream, without a device read: *path = 0 screened, 2 all fp64, -1 no such call;
+ * *unresolved_capacity (optional) = windows the fp64 pass of a screened call could take (F), 0 otherwise.
  */
 int64_t gf3_sync_frames_workspace_bytes(const gf3_ctx *ctx, int64_t F);
 int gf3_sync_frames_ex(gf3_ctx *ctx, const void *d_in, int64_t n_in, int64_t F, int64_t stride,
                        int32_t win_lo, int32_t win_hi, int64_t *d_starts, double *d_peak_or_null,
                        int32_t mode, void *d_work, void *stream);
+int gf3_sync_frames_last(const gf3_ctx *ctx, void *stream, int32_t *path, int32_t *unresolved_capacity);
 /* tests: the screening pass alone.  d_y32 [F][W] fp32 lags, d_err [F] the bound of each window, d_cls [F] 0 resolved with a
  * detection / 1 resolved without / 2 unresolved (d_starts[f] is then left alone); d_work as above */
 int gf3_debug_frames_screen(gf3_ctx *ctx, const void *d_in, int64_t n_in, int64_t F, int64_t stride,

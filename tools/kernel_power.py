@@ -15,7 +15,7 @@ F = args.frames
 starts = eng.sync_frames(big, F, args.stride, bench.WIN_LO, bench.WIN_LO + args.window)
 bits = torch.empty((F, eng.bytes_per_frame), dtype=torch.uint8, device="cuda")
 out = {}
-for name, fn in (("corr_kernel", lambda: eng.sync_frames(big, F, args.stride, bench.WIN_LO, bench.WIN_LO + args.window, out_starts=starts)),
+for name, fn in (("corr_kernel", lambda: eng.sync_frames(big, F, args.stride, bench.WIN_LO, bench.WIN_LO + args.window, out_starts=starts, screened=False)),
                  ("demod_kernel", lambda: eng.demod_frames(big, starts, out_bits=bits))):
     for _ in range(3): fn()
     torch.cuda.synchronize()
