@@ -1,6 +1,6 @@
 // Frames-mode chirp sync, screened: the search window of one packet evaluated in fp32 with a proven bound, the decision
 // taken only where the bound decides it -- the frames counterpart of gf3rx_screen.h (what gf3_sync_frames runs whenever it
-// applies: sync_frames_impl in gf3rx_abi.hip; gf3_sync_frames_ex mode 0 is the all-fp64 corr_kernel on every window).
+// applies: sync_frames_impl in gf3rx_sync_frames.hip; gf3_sync_frames_ex mode 0 is the all-fp64 corr_kernel on every window).
 //
 // What the window rule of corr_kernel (the reference's peak rule applied to a window, OFDM.py:359-361) needs of the W lags
 //   y[j] = sum_k r[s0 + j + k] c[k]:    M = max_j y[j];   first j in [1, W-2] with y[j]/M > thresh and

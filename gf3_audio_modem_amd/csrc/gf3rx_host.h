@@ -1,5 +1,5 @@
 // Host-side plumbing shared by the translation units of libgf3rx: kernel argument blocks, the context, error
-// reporting, launch helpers and the launchers each kernel family exports to the ABI layer (gf3rx_abi.hip, gf3rx_sync.hip).
+// reporting, launch helpers and the launchers each kernel family exports to the units that hold the C ABI.
 // Kernels live in per-family translation units compiled in parallel (gf3_audio_modem_amd/build.py):
 //   gf3rx_fft.hip            rfft_kernel, tx_kernel
 //   gf3rx_demod_{qpsk,scan,full}.hip   the three modes of demod_kernel (gf3rx_demod.h)
@@ -12,8 +12,11 @@
 //   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
 //   gf3rx_noise.hip          noise_estimate_kernel, soft_demap_nw_kernel + gf3_noise_estimate, gf3_soft_demap_nw; their
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
-//                            (the per-symbol demapper arithmetic they share with gf3rx_abi.hip is gf3rx_demap.h)
-//   gf3rx_abi.hip            context, plans, the remaining entry points, demappers, zero forcing, Schmidl-Cox
+//                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
+//   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
+//   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
+//   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
+//   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex), gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -206,6 +209,7 @@ struct gf3_ctx {
     std::vector<void*> fs_retired;
     std::vector<double> chirp;
     std::vector<cplx> known_pts;
+    std::vector<void*> owned;           // every device allocation that lives as long as the context (gf3rx_ctx.hip)
 };
 
 // ============================================================================
@@ -213,7 +217,7 @@ struct gf3_ctx {
 // ============================================================================
 // Message of the calling thread's last failure.  One buffer per host thread, none in the context: concurrent calls
 // on one context (different streams, different threads) cannot overwrite each other's text, and a failing call
-// writes nothing into the context it was given.  (gf3rx_abi.hip owns the buffer and `fail`.)
+// writes nothing into the context it was given.  (gf3rx_ctx.hip owns the buffer and `fail`.)
 int fail(const gf3_ctx*, int code, const char* fmt, ...);
 #define HIPCHK(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
     return fail(c, GF3_EHIP, "%s failed: %s", #x, hipGetErrorString(e_)); } while (0)

@@ -1,0 +1,100 @@
+// libgf3rx -- the frames-mode chirp sync: gf3_sync_frames* and the dispatch between the all-fp64 corr_kernel and the fp32
+// screen with a proven bound (gf3rx_fscreen.h), with the workspaces the context keeps for the screen's unresolved list.
+#include "gf3rx_host.h"
+#include "gf3rx_fscreen.h"
+
+extern "C" int64_t gf3_sync_frames_workspace_bytes(const gf3_ctx* c, int64_t F) {
+    if (!c || F < 0) return 0;
+    return (int64_t)((size_t)F * sizeof(int) + 64);           // [count | pad | unresolved window numbers]
+}
+
+// What the calling thread's last frames sync did (gf3_sync_frames_last): kept per host thread like every other diagnostic.
+static thread_local struct { const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0; } g_fs_last;
+#define GF3_FS_MAX_WORKSPACES 64
+
+// The context's workspace of the calling thread on this stream, holding at least `bytes`; nullptr: none can be had now (the
+// stream is being captured and nothing large enough exists, the table is full, the allocation failed) -- the caller
+// then runs the fp64 kernel.  An outgrown buffer is retired, not freed: a queued kernel may still read it.
+static void* fs_workspace(gf3_ctx* c, hipStream_t st, int64_t bytes) {
+    const std::thread::id me = std::this_thread::get_id();
+    std::lock_guard<std::mutex> lock(c->fs_mu);
+    gf3_ctx::FsWork* e = nullptr;
+    for (auto& w : c->fs_work) if (w.stream == st && w.thread == me) { e = &w; break; }
+    if (e && e->bytes >= bytes) return e->d;
+    if (!e && c->fs_work.size() >= GF3_FS_MAX_WORKSPACES) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (cap != hipStreamCaptureStatusNone) return nullptr;               // an allocation would break the capture
+    int64_t want = bytes;
+    if (e && want < e->bytes + e->bytes / 2) want = e->bytes + e->bytes / 2;   // (a slowly growing F: few retired buffers)
+    void* d = nullptr;
+    if (hipMalloc(&d, (size_t)want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (e) { c->fs_retired.push_back(e->d); e->d = d; e->bytes = want; }
+    else c->fs_work.push_back(gf3_ctx::FsWork{st, me, d, want});
+    return d;
+}
+
+// mode 0: all fp64 (corr_kernel on every window).  mode 1: fp32 screen with a proven bound per window (gf3rx_fscreen.h) in
+// the caller's workspace; the windows it cannot decide are listed and corr_kernel runs on those.  mode -1 (auto, what plain
+// gf3_sync_frames means): as mode 1 in a workspace the context owns, whenever the screen applies and such a workspace can
+// be had; all fp64 otherwise.  The starts are the same every way.
+static int sync_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t F, int64_t stride, int32_t win_lo, int32_t win_hi,
+                            int64_t* d_starts, double* d_peak, int32_t mode, void* d_work, float* dbg_y32, float* dbg_err, int* dbg_cls,
+                            bool screen_only, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_in || !d_starts || F < 0 || mode < -1 || mode > 1) return fail(c, GF3_EINVAL, "gf3_sync_frames: bad argument");
+    const int W = win_hi - win_lo;
+    const CorrPlan& pl = c->frames_plan;
+    if (W < 3 || W > pl.W) return fail(c, GF3_EINVAL, "gf3_sync_frames: window %d outside [3, %d]", W, pl.W);
+    hipStream_t st = (hipStream_t)stream;
+    CorrArgs a{};
+    a.t = pl.t; a.in = d_in; a.n_in = n_in; a.dt = c->cfg.in_dtype;
+    a.Hq = pl.d_Hq; a.Q = pl.Q; a.Lp = pl.Lp; a.Lc = c->Lc; a.Wmax = W;
+    a.stride = stride; a.win_lo = win_lo; a.W = W; a.starts = d_starts; a.peak = d_peak; a.thresh = c->cfg.thresh;
+    const auto& fp = c->fscr;
+    // the screen serves index-only calls within its plan's window; a caller that wants the fp64 peak VALUE gets the fp64 kernel
+    const bool can_screen = fp.ok && W <= fp.wmax && !d_peak && F <= 0x7fffffff;
+    if (mode == 1 && !d_work) mode = 0;
+    void* work = mode == 1 ? d_work : nullptr;
+    if (mode == -1 && can_screen) work = fs_workspace(c, st, gf3_sync_frames_workspace_bytes(c, F));
+    const bool screened = can_screen && work;
+    if (screen_only && !screened) return fail(c, GF3_EINVAL, "gf3_debug_frames_screen: no screening plan for this window (max_window %d)", fp.wmax);
+    g_fs_last.ctx = c; g_fs_last.stream = stream; g_fs_last.path = screened ? 0 : 2; g_fs_last.cap = screened ? (int32_t)F : 0;
+    if (!screened) {
+        if (d_work) HIPCHK(c, hipMemsetAsync(d_work, 0, 64, st));      // a caller's workspace never keeps an earlier call's count
+        HIPCHK(c, run_corr(c, pl, a, F, st));
+        return GF3_OK;
+    }
+    int* count = (int*)work;
+    int* list = (int*)((char*)work + 64);
+    HIPCHK(c, hipMemsetAsync(count, 0, 64, st));
+    FScreenArgs fa{d_in, n_in, c->cfg.in_dtype, fp.d_tw, fp.d_twn, fp.d_Hs, fp.d_H0N, fp.d_Hinf, fp.Q, fp.Lp, c->Lc, W,
+                   stride, win_lo, W, (float)c->cfg.thresh, d_starts, list, count, dbg_y32, dbg_err, dbg_cls};
+    HIPCHK(c, launch_fscreen(c, fa, F, st));
+    if (screen_only) return GF3_OK;
+    a.list = list; a.count = count;
+    HIPCHK(c, run_corr(c, pl, a, F, st, true));               // (grid = the list's capacity; workgroups past its length return at once)
+    return GF3_OK;
+}
+extern "C" int gf3_sync_frames(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t F, int64_t stride,
+                               int32_t win_lo, int32_t win_hi, int64_t* d_starts, double* d_peak, void* stream) {
+    return sync_frames_impl(c, d_in, n_in, F, stride, win_lo, win_hi, d_starts, d_peak, -1, nullptr, nullptr, nullptr, nullptr, false, stream);
+}
+extern "C" int gf3_sync_frames_ex(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t F, int64_t stride,
+                                  int32_t win_lo, int32_t win_hi, int64_t* d_starts, double* d_peak, int32_t mode, void* d_work, void* stream) {
+    return sync_frames_impl(c, d_in, n_in, F, stride, win_lo, win_hi, d_starts, d_peak, mode, d_work, nullptr, nullptr, nullptr, false, stream);
+}
+extern "C" int gf3_sync_frames_last(const gf3_ctx* c, void* stream, int32_t* path, int32_t* unresolved_capacity) {
+    if (!c || !path) return fail(c, GF3_EINVAL, "gf3_sync_frames_last: null argument");
+    const bool mine = g_fs_last.ctx == c && g_fs_last.stream == stream;
+    *path = mine ? g_fs_last.path : -1;
+    if (unresolved_capacity) *unresolved_capacity = mine ? g_fs_last.cap : 0;
+    return GF3_OK;
+}
+// tests: the screening pass alone -- fp32 lags [F][W], the bound per window, the verdict per window (0 resolved with a
+// detection, 1 resolved without, 2 unresolved: d_starts is then left alone), the unresolved windows in d_work
+extern "C" int gf3_debug_frames_screen(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t F, int64_t stride, int32_t win_lo, int32_t win_hi,
+                                       int64_t* d_starts, float* d_y32, float* d_err, int32_t* d_cls, void* d_work, void* stream) {
+    return sync_frames_impl(c, d_in, n_in, F, stride, win_lo, win_hi, d_starts, nullptr, 1, d_work, d_y32, d_err, d_cls, true, stream);
+}

@@ -1,9 +1,9 @@
 """A zoo of constellation tables and carrier maps, and the demodulation cases built from them (plain data and small
 builders; nothing here touches a GPU).
 
-Tables are `(points, bits)` in the oracle's format.  Each one is built to take one branch of the table classification in
-`gf3_ctx_create` (csrc/gf3rx_abi.hip), named in the comment next to it; `classify` restates that classification so that
-tests/test_tables_maps_cpu.py can check that every table lands where its comment says.
+Tables are `(points, bits)` in the oracle's format.  Each one is built to take one branch of the table classification of
+`gf3_ctx_create` (`classify_table`, csrc/gf3rx_ctx.hip), named in the comment next to it; `classify` restates that
+classification so that tests/test_tables_maps_cpu.py can check that every table lands where its comment says.
 
 Carrier maps are functions K -> int array of 1-based FFT bins (K = N/2 - 1), in the order the output bits follow.  Only
 `contig` is ascending and gap-free: every other map has `contig_lo == 0` in the library and goes through its `pos[]`
@@ -75,9 +75,9 @@ EXPECTED_CLASS = dict(qpsk_ref="qpsk", qpsk_reordered="uniform", qpsk_relabelled
 
 
 def classify(points, bits):
-    """The table classes of gf3_ctx_create, restated: 'qpsk' (the reference's table: sign kernel), 'uniform' (separable
-    grid, equally spaced levels on both axes: per-axis fast path in the fused kernel), 'sep' (separable grid only: the
-    soft demapper's grid kernel; literal scan in the fused kernel), 'scan' (anything else)."""
+    """The table classes of classify_table (csrc/gf3rx_ctx.hip), restated: 'qpsk' (the reference's table: sign kernel),
+    'uniform' (separable grid, equally spaced levels on both axes: per-axis fast path in the fused kernel), 'sep' (separable
+    grid only: the soft demapper's grid kernel; literal scan in the fused kernel), 'scan' (anything else)."""
     points, bits = np.asarray(points, dtype=complex), np.asarray(bits)
     M, mu = bits.shape
     lab = (bits * (1 << np.arange(mu - 1, -1, -1))).sum(axis=1)
