@@ -99,6 +99,10 @@ class CamG:
         # interleaver alone spreads garbage nobody has marked over every codeword.
         self.interleave = False
         self.last_symbol_snr_db = None
+        # "QCLDPC-*" with llr_weighting = "csi": True takes receive() from samples to weighted LLRs in one launch
+        # (Engine.demod_frames_llr) instead of demod_frames(eq) + soft_demap_csi; same decisions, LLRs equal to float32
+        # rounding.  Opt-in; ValueError with the noise weights, ignored by the other encodings and by graph_output.
+        self.fused_llr = False
         self._engines = {}
 
     def __repr__(self):
@@ -415,6 +419,10 @@ class receiver(transmitter):
         print(self)
         if self.llr_weighting not in ("csi", "noise", "noise2d"):
             raise ValueError(f"llr_weighting must be 'csi', 'noise' or 'noise2d', not {self.llr_weighting!r}")
+        fused = bool(self.fused_llr) and self._qcldpc_rate() is not None
+        if fused and self.llr_weighting != "csi":
+            raise ValueError(f"fused_llr needs llr_weighting 'csi': {self.llr_weighting!r} weights by the whole packet's "
+                             "residuals, which the fused kernel does not have")
         r = _as_samples(signal)
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
@@ -434,8 +442,9 @@ class receiver(transmitter):
         self.no_packets = int(starts.numel())
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
-        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ("eq",) if rate is not None else ())
-        o = eng.demod_frames(x, starts, want=want)
+        fused = fused and not graph_output                      # (the plots need eq: the staged path)
+        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ("eq",) if rate is not None and not fused else ())
+        o = eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
         if rate is not None:
             # soft path: weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
             code = _qcldpc_code(rate, eng.device)
@@ -453,6 +462,8 @@ class receiver(transmitter):
                 snr_t = 10.0 * torch.log10(es / torch.maximum(var, floor))
                 if self.llr_weighting == "noise2d":                 # the same report per symbol, [F, D], behind it
                     snr_t = torch.cat([snr_t, 10.0 * torch.log10(es / torch.maximum(var_s, floor))], dim=1)
+            elif fused:
+                llr = o["llr"]                                  # samples -> weighted LLRs in the one launch above
             else:
                 llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
             if self.interleave and self.llr_weighting != "noise2d":

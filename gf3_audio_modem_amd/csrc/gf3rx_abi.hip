@@ -48,6 +48,29 @@ extern "C" int gf3_demod_frames(gf3_ctx* c, const void* d_in, int64_t n_in, cons
     return gf3_demod_frames_ex(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, nullptr, 1, stream);
 }
 
+// Samples to weighted max-log LLRs in one launch (MODE_SOFT of demod_kernel): what gf3_demod_frames(eq, Hs, He) +
+// gf3_soft_demap_csi compute in three steps, without the eq round trip.  The max-log difference is defined for every
+// table the context accepts (gf3_soft_demap applies no table condition either), so none is refused here.
+extern "C" int gf3_demod_frames_llr(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                                    float* d_llr, int32_t weight, void* d_Hs, void* d_He, double* d_slope, int32_t* d_status,
+                                    void* d_work, int32_t mode, void* stream) {
+    DeviceGuard dg(c);
+    if (c && F == 0) return GF3_OK;
+    if (!c || !d_in || !d_off || !d_llr || F < 0 || mode < 0 || mode > 2 || ((uintptr_t)d_llr & 3))
+        return fail(c, GF3_EINVAL, "gf3_demod_frames_llr: bad argument");
+    if (weight != 0 && weight != 1) return fail(c, GF3_EINVAL, "gf3_demod_frames_llr: weight must be 0 (unit) or 1 (|H^|^2)");
+    DemodArgs a = demod_args(c);
+    a.in = d_in; a.n_in = n_in; a.off = d_off; a.stamps = c->stamps;
+    a.Hs = (cplx*)d_Hs; a.He = (cplx*)d_He; a.slope = d_slope; a.status = d_status;
+    a.bits = (uint8_t*)d_llr; a.row_bytes = (int)sizeof(float) * c->cfg.D * c->cfg.C * c->cfg.mu; a.ring = 0;
+    int hI = 0, hQ = 0;
+    a.soft = 1; a.soft_weight = weight; a.sep = c->sep; a.soft_stage = demod_soft_stages(c) ? 1 : 0;
+    a.soft_kind = (c->sep.nI > 0 && sep_is_binary(c->sep, c->cfg.mu, hI, hQ) && hI <= 3) ? hI : 0;
+    if (d_work && demod_wants_split(c, F, mode)) return demod_split(c, a, F, d_work, (hipStream_t)stream);
+    HIPCHK(c, launch_demod_soft(c, a, F, (hipStream_t)stream));
+    return GF3_OK;
+}
+
 extern "C" int gf3_equalise(gf3_ctx* c, const void* d_data, const void* d_start, const void* d_end, int64_t F,
                             void* d_eq_all, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
                             uint8_t* d_bits, void* stream) {

@@ -1,9 +1,10 @@
 // demod_kernel: the fused demodulation of one packet per workgroup, and the decision helpers it shares with the
-// stand-alone demappers.  A header because its three modes are compiled in three translation units
-// (gf3rx_demod_qpsk.hip, gf3rx_demod_scan.hip, gf3rx_demod_full.hip) and the two-phase kernels of long packets
-// (gf3rx_demod_split.h) reuse its pieces.
+// stand-alone demappers.  A header because its four modes are compiled in four translation units
+// (gf3rx_demod_qpsk.hip, gf3rx_demod_scan.hip, gf3rx_demod_full.hip, gf3rx_demod_soft.hip) and the two-phase kernels of
+// long packets (gf3rx_demod_split.h) reuse its pieces.
 #pragma once
 #include "gf3rx_host.h"
+#include "gf3rx_demap.h"
 
 // ============================================================================
 // fused demodulation of one packet per workgroup
@@ -96,7 +97,36 @@ GF3_DEV double rcp_n1(double x) {
 // MODE_QPSK : bits only, reference QPSK table.  The channel magnitude model
 //             (1-f)|Hs| + f|He| is positive, so X/Hest and X*conj(u*rot) have the same signs and
 //             the decision needs neither the division nor |Hs|, |He|: per-carrier state is u alone.
-enum { MODE_FULL = 0, MODE_SCAN = 1, MODE_QPSK = 2 };
+// MODE_SOFT : no bits: weighted max-log LLRs of every data carrier (gf3_demod_frames_llr), float32 in the reference's
+//             bit order, from the un-normalised symbol and the magnitude model the table modes hold anyway
+enum { MODE_FULL = 0, MODE_SCAN = 1, MODE_QPSK = 2, MODE_SOFT = 3 };
+// MODE_SOFT, one data carrier: e = ep / mag as MODE_FULL forms it, the max-log differences of gf3rx_demap.h, times w in
+// fp64, rounded to float32 once.  kind (wave-uniform) = h of a binary-indexed 2^h x 2^h grid (sep_is_binary), 0: any table.
+GF3_DEV void soft_llr(cplx e, const DemodArgs& a, double w, float* dst) {
+    if (a.soft_kind == 1) {
+        const double lvI[2] = {a.sep.lvI[0], a.sep.lvI[1]}, lvQ[2] = {a.sep.lvQ[0], a.sep.lvQ[1]};
+        double diff[2];
+        maxlog_bin<1, 1>(e, lvI, lvQ, diff);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) dst[b] = (float)(diff[b] * w);
+    } else if (a.soft_kind == 2) {
+        double lvI[4], lvQ[4], diff[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { lvI[k] = a.sep.lvI[k]; lvQ[k] = a.sep.lvQ[k]; }
+        maxlog_bin<2, 2>(e, lvI, lvQ, diff);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) dst[b] = (float)(diff[b] * w);
+    } else if (a.soft_kind == 3) {
+        double lvI[8], lvQ[8], diff[6];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { lvI[k] = a.sep.lvI[k]; lvQ[k] = a.sep.lvQ[k]; }
+        maxlog_bin<3, 3>(e, lvI, lvQ, diff);
+#pragma unroll
+        for (int b = 0; b < 6; ++b) dst[b] = (float)(diff[b] * w);
+    } else {
+        maxlog_table(e, DemapTab{a.M, a.mu, a.cre, a.cim, a.clab, a.sep}, w, dst);
+    }
+}
 // Every mode runs at two waves per SIMD.  MODE_QPSK keeps the two ping-pong FFT buffers.  The table modes carry two more
 // doubles of state per carrier (the magnitude model a0 + da f_l), which do not fit the register file next to the
 // transform at two workgroups per CU; they live in LDS ([8][T] pairs, one conflict-free 16-byte read per carrier per
@@ -433,7 +463,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     for (int l = l_lo; l < l_hi; ++l) {
         if constexpr (SPECTRA) { lds_barrier(); load_spectra(a.sp_data + ((int64_t)f * D + l) * K); }
         else transform(2 * P + l);
-        if (l > l_lo) pack_words(l - 1, false);
+        if constexpr (MODE != MODE_SOFT) { if (l > l_lo) pack_words(l - 1, false); }
         const double fl = ((double)l + 0.5 * (double)P) / denom;          // (l + P/2)/(D+P)
         uint8_t* lab_l = labs + (l & (a.ring - 1)) * C;
         if constexpr (MODE == MODE_QPSK) {
@@ -456,6 +486,45 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
             }
 #pragma unroll
             for (int s = 0; s < 8; ++s) if (psl[s] >= 0) lab_l[psl[s]] = (uint8_t)lab[s];
+        } else if constexpr (MODE == MODE_SOFT) {
+            // `row` is the packet's LLR row here (float32 [D][C][mu], row_bytes = 4 D C mu).  A thread's eight slots are
+            // not adjacent carriers, so a symbol's C mu values are staged in the FFT buffer -- free between the transform's
+            // last read and the next transform's first barrier -- and leave as aligned 16-byte vectors: the staging offset
+            // sh makes LDS and memory agree modulo 16 bytes, the row's ragged ends go out element by element.  A symbol
+            // that does not fit the buffer (soft_stage = 0, host: demod_soft_stages) is stored by its owners directly.
+            float* grow = (float*)row + (int64_t)l * Bs;
+            const int sh = a.soft_stage ? (int)(((uintptr_t)grow >> 2) & 3) : 0;
+            float* dst = a.soft_stage ? (float*)lds + sh : grow;
+            if (a.soft_stage) lds_barrier();                               // every thread has its spectrum out of the buffer
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const cplx g = u[s];
+                const cplx ep = cmul_conj(v[s], g);
+                u[s] = cmul(g, gstep[s]);
+                const int ps = pos_of(s);
+                const double2 md = mags[s * T + tid];
+                const double mag = fma(md.y, fl, md.x);
+                if (ps >= 0) {
+                    const double hm = mag * (1.0 / XS);                    // |Hest|: the magnitudes carry the transform's factor
+                    soft_llr(cscale(ep, rcp_nr(mag)), a, a.soft_weight ? hm * hm : 1.0, dst + ps * mu);
+                }
+            }
+            if (a.soft_stage) {
+                lds_barrier();
+                const float* st = (const float*)lds;
+                float* gal = grow - sh;                                    // 16-byte aligned
+                const int nv = (sh + Bs + 3) >> 2;
+                for (int i = launder(tid); i < nv; i += T) {
+                    const float4 q = *(const float4*)(st + 4 * i);
+                    const int lo = 4 * i - sh;                             // element 0 of the vector, counted in the row
+                    if (lo >= 0 && lo + 4 <= Bs) *(float4*)(gal + 4 * i) = q;
+                    else {
+                        const float qe[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (lo + j >= 0 && lo + j < Bs) gal[4 * i + j] = qe[j];
+                    }
+                }
+            }
         } else {
             // Fast path, straight-line over the eight carriers: equalise, then the nearest grid point per axis
             // (decide_fast).  A decision within 1e-9 of a spacing of a boundary, a NaN / Inf symbol or a table that
@@ -516,8 +585,10 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
         }
     }
     GF3_STAMP(4);
-    lds_barrier();
-    pack_words(l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
+    if constexpr (MODE != MODE_SOFT) {
+        lds_barrier();
+        pack_words(l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
+    }
     GF3_STAMP(5);
     GF3_STAMP_RT(7);
 }
@@ -547,6 +618,17 @@ inline size_t demod_lds_bytes(const gf3_ctx* c, bool lean = false) {
     const size_t fft = (inplace || !pp_size) ? (size_t)(c->NC + c->NC / 8) * sizeof(cplx) : (size_t)2 * c->NC * sizeof(cplx);
     const size_t mags = lean ? 0 : (size_t)c->NC * sizeof(double2);
     const size_t tail = fft + (size_t)((demod_ring(c) * c->cfg.C + 15) & ~15) + mags;
+    const size_t fit = (size_t)2 * (c->fit_hi - c->fit_lo) * sizeof(cplx);
+    return 32 * sizeof(double) + (size_t)2 * (64 + c->NC / 64 + 1) * sizeof(cplx) + (fit > tail ? fit : tail);
+}
+// MODE_SOFT: no decision ring; the (a0, da) pairs follow the FFT buffer directly, and a symbol's LLRs are staged IN the
+// FFT buffer (NC + NC/8 points) when they fit with the alignment shift (<= 3 floats) and the last vector's overhang
+// (<= 3 more: read, never stored) -- no LDS beyond the table modes'.
+inline bool demod_soft_stages(const gf3_ctx* c) {
+    return (size_t)c->cfg.C * c->cfg.mu * sizeof(float) + 8 * sizeof(float) <= (size_t)(c->NC + c->NC / 8) * sizeof(cplx);
+}
+inline size_t demod_soft_lds_bytes(const gf3_ctx* c) {
+    const size_t tail = (size_t)(c->NC + c->NC / 8) * sizeof(cplx) + (size_t)c->NC * sizeof(double2);
     const size_t fit = (size_t)2 * (c->fit_hi - c->fit_lo) * sizeof(cplx);
     return 32 * sizeof(double) + (size_t)2 * (64 + c->NC / 64 + 1) * sizeof(cplx) + (fit > tail ? fit : tail);
 }

@@ -125,7 +125,8 @@ int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStrea
         HIPCHK(c, e);
     }
     hipError_t e = hipSuccess;
-    if (a.eq || a.Hest) e = launch_dsplit_full(c, a, F * a.nchunk, st);
+    if (a.soft) e = launch_dsplit_soft(c, a, F * a.nchunk, st);
+    else if (a.eq || a.Hest) e = launch_dsplit_full(c, a, F * a.nchunk, st);
     else if (c->qpsk_q > 0.0) e = launch_dsplit_qpsk(c, a, F * a.nchunk, st);
     else e = launch_dsplit_scan(c, a, F * a.nchunk, st);
     HIPCHK(c, e);

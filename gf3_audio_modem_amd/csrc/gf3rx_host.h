@@ -2,8 +2,8 @@
 // reporting, launch helpers and the launchers each kernel family exports to the units that hold the C ABI.
 // Kernels live in per-family translation units compiled in parallel (gf3_audio_modem_amd/build.py):
 //   gf3rx_fft.hip            rfft_kernel, tx_kernel
-//   gf3rx_demod_{qpsk,scan,full}.hip   the three modes of demod_kernel (gf3rx_demod.h)
-//   gf3rx_demod_split.hip, gf3rx_dsplit_{qpsk,scan,full}.hip   the two-phase demodulation of long packets
+//   gf3rx_demod_{qpsk,scan,full,soft}.hip   the four modes of demod_kernel (gf3rx_demod.h)
+//   gf3rx_demod_split.hip, gf3rx_dsplit_{qpsk,scan,full,soft}.hip   the two-phase demodulation of long packets
 //   gf3rx_corr.hip           corr_kernel, spec_kernel, ols_kernel
 //   gf3rx_screen.hip         scr_ring_kernel, scr_ols_kernel, scr_refine_kernel (gf3rx_screen.h)
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
@@ -16,7 +16,7 @@
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
-//   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex), gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
+//   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex), gf3_demod_frames_llr, gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -91,6 +91,13 @@ struct DemodArgs {
     // Dc consecutive data symbols, from the channel state the estimate stage left in Hs / He / slope
     int Dc, nchunk;
     const double* psum;       // [F][2][N] time-domain sums of each side's P pilot symbols (input of the estimate stage)
+    // MODE_SOFT (gf3_demod_frames_llr; appended: the other modes' argument offsets are what they were).  `bits` is then the
+    // float32 LLR array and row_bytes = 4 D C mu; ring = 0 (no decisions are staged).
+    int soft;                 // 1: the soft mode is asked for (host dispatch)
+    int soft_weight;          // 0: unit weight, 1: |Hest|^2
+    int soft_kind;            // h of a binary-indexed 2^h x 2^h grid (maxlog_bin<h, h>), 0: maxlog_table
+    int soft_stage;           // 1: a symbol's LLRs are staged in the FFT buffer (demod_soft_stages)
+    SepTab sep;
 };
 
 #ifdef GF3_STAMPS
@@ -291,12 +298,14 @@ hipError_t launch_demod_qpsk(const gf3_ctx* c, const DemodArgs& a, int64_t F, hi
 hipError_t launch_demod_scan(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
 hipError_t launch_demod_full(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
 hipError_t launch_demod_spectra(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
+hipError_t launch_demod_soft(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);      // gf3rx_demod_soft.hip: LLRs, no bits
 // gf3rx_demod_split.hip + gf3rx_dsplit_{qpsk,scan,full}.hip: the two-phase form for long packets, few at a time
 bool demod_wants_split(const gf3_ctx* c, int64_t F, int mode);
 int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStream_t st);
 hipError_t launch_dsplit_qpsk(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
 hipError_t launch_dsplit_scan(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
 hipError_t launch_dsplit_full(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
+hipError_t launch_dsplit_soft(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
 // gf3rx_corr.hip
 hipError_t run_corr(const gf3_ctx* c, const CorrPlan& pl, const CorrArgs& a, int64_t grid, hipStream_t st, bool listed = false);
 // gf3rx_fscreen.hip: the screened frames sync (fp32 with a bound per window; unresolved windows are listed for corr_kernel)

@@ -237,6 +237,42 @@ class Engine:
             _ptr(work), 0 if split is None else (2 if split else 1), self._stream()))
         return o
 
+    def demod_frames_llr(self, x, frame_offsets, weight="csi", want=(), split=None, out=None):
+        """Samples to weighted max-log LLRs in one launch (gf3_demod_frames_llr: the fused kernel's soft output mode).
+        Returns dict with 'llr' (float32 [F*D*C*mu], the reference's bit order, LLR > 0 <=> bit 0) plus any of 'Hs', 'He',
+        'slope', 'status'.  weight: "csi" -- |H^|^2, what demod_frames(want eq, Hs, He) + soft_demap_csi give -- or "none"
+        (soft_demap(eq, 1.0)); an int goes to the library as it is.  split: as in demod_frames.  out: optional contiguous
+        float32 tensor of F*D*C*mu elements to write into."""
+        cfg = self.cfg
+        x = self._samples(x)
+        off = torch.as_tensor(frame_offsets, dtype=torch.int64).to(self.device).contiguous()
+        F = off.numel()
+        n = F * cfg.D * cfg.C * cfg.mu
+        if isinstance(weight, str):
+            if weight not in ("csi", "none"):
+                raise ValueError(f"weight must be 'csi' or 'none', not {weight!r}")
+            weight = 1 if weight == "csi" else 0
+        if out is None:
+            llr = self._new((n,), torch.float32)
+        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
+        else:
+            llr = out
+        o = {"llr": llr}
+        if "Hs" in want: o["Hs"] = self._new((F, cfg.K), torch.complex128)
+        if "He" in want: o["He"] = self._new((F, cfg.K), torch.complex128)
+        if "slope" in want: o["slope"] = self._new((F,), torch.float64)
+        if "status" in want: o["status"] = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        work = None
+        if F and (split or (split is None and self.lib.gf3_demod_split_plan(self._h, F, 0, None, None))):
+            work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)
+        rc = self.lib.gf3_demod_frames_llr(
+            self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(llr), int(weight), _ptr(o.get("Hs")), _ptr(o.get("He")),
+            _ptr(o.get("slope")), _ptr(o.get("status")), _ptr(work), 0 if split is None else (2 if split else 1), self._stream())
+        if rc != 0:                                                # (a bad `weight` is the library's to refuse: Gf3Error)
+            raise Gf3Error(f"gf3rx error {rc}: {self.lib.gf3_last_error(self._h).decode()}")
+        return o
+
     def demod_plan(self, F, split=None):
         """How demod_frames(F packets, split=...) runs: dict(split: two-phase form or not, Dc: data symbols per workgroup of
         its data stage, chunks: workgroups per packet)."""

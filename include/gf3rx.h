@@ -387,6 +387,28 @@ int gf3_soft_demap_csi(gf3_ctx *ctx, const void *d_eq_c128, const void *d_Hs_c12
                        int64_t F, float *d_llr_f32, void *stream);
 
 /*
+ * Samples to weighted max-log LLRs in ONE launch (not in the reference): get_symbols ... equalise and the data-carrier
+ * select (OFDM.py:391-480, 603) as gf3_demod_frames runs them, with the soft demapper and the CSI weight in the place of
+ * demap + PS -- the fused kernel's soft output mode.  Replaces gf3_demod_frames(d_eq, d_Hs, d_He) + gf3_soft_demap_csi on the
+ * coded receive path: the equalised symbols never travel to memory, the weight |H^|^2 is taken from the magnitude model
+ * the kernel holds per carrier, and (max-log difference) x weight is rounded to float32 once (the staged pair rounds twice:
+ * the two agree to 1.5 x 2^-23 relative).  No hard bits are produced.
+ *   d_llr_f32 [F*D*C*mu] in the reference's bit order (packet -> symbol -> data carrier in data_bins order -> bit);
+ *             LLR > 0 <=> bit 0.  The layout gf3_soft_demap_csi writes.
+ *   weight    0: unit weight (gf3_soft_demap(eq, 1.0))      1: |H^_{f,l,k}|^2 (gf3_soft_demap_csi)
+ *   d_Hs, d_He, d_slope, d_status   optional, as in gf3_demod_frames (the same values, bit for bit, in the same form)
+ *   d_work, mode                    as in gf3_demod_frames_ex (gf3_demod_workspace_bytes; NULL: the one-launch kernel)
+ * A frame whose samples fall outside [0, n_in) gets a row of +0.0f (erasures to a decoder) and sets bit 0 of *d_status.
+ * Every table the context accepts has max-log LLRs (gf3_soft_demap refuses none), so none is refused here; GF3_EINVAL for a
+ * weight other than 0 or 1.  Non-finite samples are outside this call's contract.  F == 0 is a no-op.
+ */
+int gf3_demod_frames_llr(gf3_ctx *ctx, const void *d_in, int64_t n_in,
+                         const int64_t *d_frame_offsets, int64_t F,
+                         float *d_llr_f32, int32_t weight,
+                         void *d_Hs, void *d_He, double *d_slope, int32_t *d_status,
+                         void *d_work, int32_t mode, void *stream);
+
+/*
  * Noise-weighted soft demapping (not in the reference): per-carrier effective noise variances measured on the equalised
  * data symbols themselves, and max-log LLRs divided by them.  Opt-in; gf3_soft_demap_csi is unchanged.
  *   gf3_noise_estimate:  v[f, c] = (1/D) sum_l |eq[f, l, c] - s|^2, s the constellation point the hard decision picks
