@@ -26,18 +26,20 @@ __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 _NP2T = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32,
          np.dtype("int16"): torch.int16, np.dtype("uint8"): torch.uint8}
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "known_bits.npz")
-# channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), n = 1536
+# channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), of block
+# length CamG.ldpc_n = 1536 (the default), 3072 or 6144 coded bits
 QCLDPC_ENCODINGS = {"QCLDPC-1/2": "1/2", "QCLDPC-2/3": "2/3", "QCLDPC-3/4": "3/4", "QCLDPC-5/6": "5/6"}
+QCLDPC_LIFTING = {1536: 64, 3072: 128, 6144: 256}          # ldpc_n -> lifting size Z (24 block columns)
 _codes = {}
 
 
-def _qcldpc_code(rate, device=None):
-    """One QCLDPC object per (rate, device), made on first use (the code tables are uploaded once)."""
+def _qcldpc_code(rate, device=None, Z=64):
+    """One QCLDPC object per (rate, Z, device), made on first use (the code tables are uploaded once)."""
     from .ldpc import QCLDPC
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    code = _codes.get((rate, dev))
+    code = _codes.get((rate, Z, dev))
     if code is None:
-        code = _codes[(rate, dev)] = QCLDPC(rate, dev)
+        code = _codes[(rate, Z, dev)] = QCLDPC(rate, dev, Z=Z)
     return code
 
 
@@ -87,6 +89,7 @@ class CamG:
         self.bits_per_symbol = self.K * self.mu
         self.known_sequence = _load_known_sequence(self.ofdm_symbol_size)
         self.ldpc_max_iter = 50                 # decoder iterations at most (encodings "QCLDPC-*")
+        self.ldpc_n = 1536                      # coded bits per codeword: 1536, 3072 or 6144 (encodings "QCLDPC-*")
         # LLR weights of receive() on the "QCLDPC-*" encodings: "csi" = |H^|^2 (white noise assumed), "noise" = 1 / the
         # per-carrier noise variance measured on each packet's equalised symbols (coloured noise, interferers); the
         # latter also leaves the per-carrier SNR estimate [packets, C] in dB in `last_snr_db`
@@ -145,6 +148,14 @@ class CamG:
             raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
         return rate
 
+    def _qcldpc(self, rate, device=None):
+        """The code of this rate at block length `ldpc_n`, on `device` (None: the current one)."""
+        Z = QCLDPC_LIFTING.get(self.ldpc_n)
+        if Z is None:
+            raise ValueError(f"ldpc_n must be one of {', '.join(map(str, QCLDPC_LIFTING))}, not {self.ldpc_n!r}")
+        # (the default length keeps the (rate, device) call, which is what a stand-in for `_qcldpc_code` takes)
+        return _qcldpc_code(rate, device) if Z == 64 else _qcldpc_code(rate, device, Z=Z)
+
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
         pts, tb = self._tables()
@@ -174,7 +185,7 @@ class transmitter(CamG):
         if rate is not None:
             # QC-LDPC (not in the reference): zero padding to whole codewords, encoded on the GPU; the codewords then
             # fill packets like uncoded bits (the coin-flip fill below)
-            code = _qcldpc_code(rate)
+            code = self._qcldpc(rate)
             msg = np.concatenate([bits.astype(np.uint8) & 1, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
             bits = code.encode(torch.from_numpy(msg)).cpu().numpy().reshape(-1).astype(np.int64)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
@@ -385,7 +396,7 @@ class receiver(transmitter):
         rate = self._qcldpc_rate()
         if rate is not None:
             # hard-input decoding (LLR = +-1) of the whole codewords in the stream; receive() decodes from soft values
-            code = _qcldpc_code(rate)
+            code = self._qcldpc(rate)
             b = np.asarray(bits_encoded)
             if self.interleave:
                 if len(b) % (self.packet_length * self.data_bits_per_symbol):
@@ -447,7 +458,7 @@ class receiver(transmitter):
         o = eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
         if rate is not None:
             # soft path: weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
-            code = _qcldpc_code(rate, eng.device)
+            code = self._qcldpc(rate, eng.device)
             if self.llr_weighting in ("noise", "noise2d"):
                 if self.llr_weighting == "noise":
                     var = eng.noise_estimate(o["eq"])

@@ -1,7 +1,8 @@
 """Quasi-cyclic LDPC forward error correction on the GPU (gf3_ldpc_* of include/gf3rx.h).
 
-The code family is the project's own (tools/make_qcldpc.py -> data/qcldpc_z64.json): lifting size Z = 64, 24 block
-columns, n = 1536 coded bits, rates 1/2, 2/3, 3/4, 5/6 (k = 768, 1024, 1152, 1280), dual-diagonal parity part.
+The code family is the project's own (tools/make_qcldpc.py -> data/qcldpc_z<Z>.json): lifting size Z = 64 (the
+default), 128 or 256, 24 block columns, n = 24 Z = 1536 / 3072 / 6144 coded bits, rates 1/2, 2/3, 3/4, 5/6
+(k = 12 Z, 16 Z, 18 Z, 20 Z), dual-diagonal parity part.
 Encoding and the layered normalised min-sum decoder run in hand-written HIP (csrc/gf3rx_ldpc.hip); there is no host
 implementation to fall back to.
 """
@@ -15,16 +16,19 @@ import torch
 from . import _lib
 from .engine import Gf3Error
 
-_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "qcldpc_z64.json")
+_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 RATES = ("1/2", "2/3", "3/4", "5/6")
-Z = 64
+LIFTINGS = (64, 128, 256)
+Z = 64                                  # the default lifting size
 
 
-def shift_table(rate):
-    """int16 [mb, 24] shift table of one rate (-1 = zero block)."""
+def shift_table(rate, Z=64):
+    """int16 [mb, 24] shift table of one rate of the family of lifting size Z (-1 = zero block)."""
     if rate not in RATES:
         raise ValueError(f"unknown QC-LDPC rate {rate!r} (one of {', '.join(RATES)})")
-    with open(_DATA) as f:
+    if Z not in LIFTINGS:
+        raise ValueError(f"no QC-LDPC family of lifting size Z={Z} (one of {', '.join(map(str, LIFTINGS))})")
+    with open(os.path.join(_DATA, f"qcldpc_z{Z}.json")) as f:
         return np.array(json.load(f)["rates"][rate], dtype=np.int16)
 
 
@@ -35,21 +39,23 @@ def _ptr(t):
 class QCLDPC:
     """One code of the family on one GPU.  Immutable; encode / decode are asynchronous on the current stream.
 
-    QCLDPC(rate, device=None), or QCLDPC(shifts=<int16 [mb, nb] table>) for a code of one's own (Z = 64)."""
+    QCLDPC(rate, device=None, Z=64), or QCLDPC(shifts=<int16 [mb, nb] table>, Z=64) for a code of one's own; Z is the
+    lifting size, 64, 128 or 256 (n = Z nb)."""
 
-    def __init__(self, rate="1/2", device=None, shifts=None):
+    def __init__(self, rate="1/2", device=None, shifts=None, Z=64):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise Gf3Error("no GPU visible: QC-LDPC coding has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.rate = None if shifts is not None else rate
-        sh = np.ascontiguousarray(shift_table(rate) if shifts is None else shifts, dtype=np.int16)
+        self.Z = int(Z)
+        sh = np.ascontiguousarray(shift_table(rate, self.Z) if shifts is None else shifts, dtype=np.int16)
         if sh.ndim != 2:
             raise ValueError("shifts must be a 2-D table [mb, nb]")
         self.shifts = sh
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self.lib.gf3_ldpc_create(sh.shape[0], sh.shape[1], Z, sh.ctypes.data_as(C.c_void_p), C.byref(h))
+            rc = self.lib.gf3_ldpc_create(sh.shape[0], sh.shape[1], self.Z, sh.ctypes.data_as(C.c_void_p), C.byref(h))
         if rc != 0:
             msg = self.lib.gf3_last_error(None).decode()
             raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(msg)

@@ -455,26 +455,30 @@ int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32
                    void *stream);
 
 /*
- * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64; the
- * shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, 64) for the circulant whose
- * row z has its one in column (z + s) mod 64.  Block columns 0 .. nb-mb-1 carry the message (systematic part), the
- * last mb the parity; codeword bit j*64 + t is bit t of block column j.  n = 64 nb, k = 64 (nb - mb).  The project's
- * own family (rates 1/2, 2/3, 3/4, 5/6 at n = 1536) is gf3_audio_modem_amd/data/qcldpc_z64.json.
- *   - gf3_ldpc_create validates Z == 64, 0 < mb < nb <= 32, every shift in [-1, 64) and at least two non-zero blocks
- *     per block row, and uploads the table to the current device.  It records whether the parity part is
- *     dual-diagonal (first parity column shifts x, 0, x at rows 0, some middle row and mb-1; every other parity
- *     column shift 0 at rows c-1 and c): only then can gf3_ldpc_encode encode (GF3_EINVAL otherwise); any valid
- *     code decodes.  Error text of create / encode / decode: gf3_last_error(NULL), per calling thread.
+ * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64, 128
+ * or 256; the shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, Z) for the
+ * circulant whose row z has its one in column (z + s) mod Z.  Block columns 0 .. nb-mb-1 carry the message (systematic
+ * part), the last mb the parity; codeword bit j*Z + t is bit t of block column j.  n = Z nb, k = Z (nb - mb).  The
+ * project's own families (rates 1/2, 2/3, 3/4, 5/6 at n = 1536, 3072, 6144) are
+ * gf3_audio_modem_amd/data/qcldpc_z64.json, qcldpc_z128.json and qcldpc_z256.json.
+ *   - gf3_ldpc_create validates Z in {64, 128, 256} (any other: GF3_EINVAL, the text names "Z=<value>"),
+ *     0 < mb < nb <= 32, every shift in [-1, Z) and at least two non-zero blocks per block row, and uploads the table
+ *     to the current device.  Z > 64 also needs mb <= 12 (GF3_EINVAL otherwise): codes of more block rows decode at
+ *     Z = 64 only.  It records whether the parity part is dual-diagonal (first parity column shifts x, 0, x at rows 0,
+ *     some middle row and mb-1; every other parity column shift 0 at rows c-1 and c): only then can gf3_ldpc_encode
+ *     encode (GF3_EINVAL otherwise); any valid code decodes.  Error text of create / encode / decode:
+ *     gf3_last_error(NULL), per calling thread.
  *   - a code object is immutable: share it across threads and streams freely.  Encode and decode are asynchronous on
  *     `stream` and run on the device the code was created on.
  *   - gf3_ldpc_encode: d_msg [n_cw, k] uint8 0/1 -> d_cw [n_cw, n] uint8 0/1, systematic first.
  *   - gf3_ldpc_decode: layered normalised min-sum (alpha = 0.75; block rows in order, within a row the non-zero
- *     blocks in column order), one wavefront per codeword, stopping after the first full iteration whose decisions
- *     satisfy every check, or after max_iter >= 1 iterations.  d_llr [n_cw, n] f32, LLR > 0 <=> bit 0; non-finite
- *     LLRs are outside the contract.  d_bits [n_cw, k] uint8 decisions of the systematic part (1 <=> APP < 0);
- *     d_app [n_cw, n] f32 a-posteriori LLRs or NULL; d_iters [n_cw] int32 or NULL: iterations used, -max_iter when the
- *     syndrome is still non-zero after max_iter.  The float32 arithmetic is fixed (no contraction): results are
- *     bit-identical to a float32 restatement of the same schedule.
+ *     blocks in column order), Z/64 wavefronts per codeword (one at Z = 64; at Z = 128, 256 one workgroup, its waves
+ *     meeting at a barrier after every block row), stopping after the first full iteration whose decisions satisfy
+ *     every check of the codeword, or after max_iter >= 1 iterations.  d_llr [n_cw, n] f32, LLR > 0 <=> bit 0;
+ *     non-finite LLRs are outside the contract.  d_bits [n_cw, k] uint8 decisions of the systematic part
+ *     (1 <=> APP < 0); d_app [n_cw, n] f32 a-posteriori LLRs or NULL; d_iters [n_cw] int32 or NULL: iterations used,
+ *     -max_iter when the syndrome is still non-zero after max_iter.  The float32 arithmetic is fixed (no contraction)
+ *     and the same for every Z: results are bit-identical to a float32 restatement of the same schedule.
  */
 typedef struct gf3_ldpc gf3_ldpc;
 int gf3_ldpc_create(int32_t mb, int32_t nb, int32_t Z, const int16_t *h_shifts, gf3_ldpc **out);
