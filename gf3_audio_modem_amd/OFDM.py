@@ -106,6 +106,16 @@ class CamG:
         # (Engine.demod_frames_llr) instead of demod_frames(eq) + soft_demap_csi; same decisions, LLRs equal to float32
         # rounding.  Opt-in; ValueError with the noise weights, ignored by the other encodings and by graph_output.
         self.fused_llr = False
+        # "QCLDPC-*": outer_code = (G, R) adds R Reed-Solomon parity codewords to every group of G data codewords
+        # (outer.py); decode() / receive() then rewrite up to R codewords per group that the LDPC decoder gave up on.
+        # Groups are strided over the stream (member t of group g is codeword t NG + g).  None: no outer code.
+        # Every "QCLDPC-*" receive() / decode() leaves {"codewords", "inner_failed", "recovered", "groups_failed",
+        # "failed_codewords"} in `last_decode_report` (failed_codewords: numbers of the codewords whose LDPC decoding did
+        # not converge; recovered: how many of them were rewritten; groups_failed: groups beyond repair).  With an outer
+        # code the report covers the NG (G + R) codewords of the groups; without one the receiver cannot tell the coin-flip
+        # fill of the last packet from the message, so every whole codeword counts and the fill shows up as failed.
+        self.outer_code = None
+        self.last_decode_report = None
         self._engines = {}
 
     def __repr__(self):
@@ -146,6 +156,8 @@ class CamG:
         rate = QCLDPC_ENCODINGS.get(self.encoding)
         if self.interleave and rate is None:
             raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        if rate is None:
+            self._outer()                       # (ValueError: the outer code exists on these encodings only)
         return rate
 
     def _qcldpc(self, rate, device=None):
@@ -155,6 +167,44 @@ class CamG:
             raise ValueError(f"ldpc_n must be one of {', '.join(map(str, QCLDPC_LIFTING))}, not {self.ldpc_n!r}")
         # (the default length keeps the (rate, device) call, which is what a stand-in for `_qcldpc_code` takes)
         return _qcldpc_code(rate, device) if Z == 64 else _qcldpc_code(rate, device, Z=Z)
+
+    def _outer(self):
+        """(G, R) of `outer_code`, or None.  The outer code exists on the "QCLDPC-*" encodings only."""
+        if self.outer_code is None:
+            return None
+        if QCLDPC_ENCODINGS.get(self.encoding) is None:
+            raise ValueError(f"outer_code needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        try:
+            G, R = (int(v) for v in self.outer_code)
+        except (TypeError, ValueError):
+            raise ValueError(f"outer_code must be None or (G, R), not {self.outer_code!r}")
+        return G, R
+
+    def outer_layout(self, F):
+        """(cap, NG) for F packets: the whole codewords they hold and the outer-code groups among them (NG = 0 without
+        `outer_code`).  Member t of group g travels as codeword t NG + g; codewords NG (G + R) .. cap - 1 and the rest
+        of the last packet are fill."""
+        per_packet = self.packet_length * self.data_bits_per_symbol
+        gr = self._outer()
+        if gr is None:
+            return F * per_packet // self.ldpc_n, 0
+        from .outer import layout
+        return layout(F, per_packet, self.ldpc_n, *gr)
+
+    def _outer_rs(self, code, device=None):
+        from .outer import OuterRS
+        G, R = self._outer()
+        return OuterRS(G, R, code.k, device)
+
+    def _decode_report(self, iters, status):
+        """`last_decode_report` from the decoder's iteration counts and (outer code) the group statuses, host arrays."""
+        status = np.asarray(status)
+        if len(status):                                         # (outer code: the members of the groups; the rest is fill)
+            iters = iters[: len(status) * sum(self._outer())]
+        failed = np.flatnonzero(np.asarray(iters) < 0)
+        self.last_decode_report = {"codewords": int(len(iters)), "inner_failed": int(len(failed)),
+                                   "recovered": int(status[status > 0].sum()), "groups_failed": int((status < 0).sum()),
+                                   "failed_codewords": failed.astype(np.int64)}
 
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
@@ -186,8 +236,22 @@ class transmitter(CamG):
             # QC-LDPC (not in the reference): zero padding to whole codewords, encoded on the GPU; the codewords then
             # fill packets like uncoded bits (the coin-flip fill below)
             code = self._qcldpc(rate)
-            msg = np.concatenate([bits.astype(np.uint8) & 1, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
-            bits = code.encode(torch.from_numpy(msg)).cpu().numpy().reshape(-1).astype(np.int64)
+            if self._outer() is None:
+                msg = np.concatenate([bits.astype(np.uint8) & 1, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
+            else:
+                # outer code: the smallest packet count whose groups hold the message; zero padding to whole groups; the
+                # parity codewords; member t of group g is sent as codeword t NG + g (data members first)
+                from .outer import packets_for
+                G, R = self._outer()
+                rs = self._outer_rs(code)
+                F = packets_for(len(bits), self.packet_length * self.data_bits_per_symbol, code.n, code.k, G, R)
+                NG = self.outer_layout(F)[1]
+                data = torch.zeros(NG * G * code.k, dtype=torch.uint8)
+                data[: len(bits)] = torch.from_numpy(bits.astype(np.uint8) & 1)
+                data = data.to(rs.device).reshape(NG, G, code.k)
+                par = rs.encode(data).reshape(NG, R, code.k)
+                msg = torch.cat([data.transpose(0, 1), par.transpose(0, 1)]).contiguous().reshape(-1)
+            bits = code.encode(torch.as_tensor(msg)).cpu().numpy().reshape(-1).astype(np.int64)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
             mask = np.resize(np.asarray(self.known_sequence[:self.data_bits_per_symbol]), bits.shape)
             bits = bits ^ mask.astype(bits.dtype)
@@ -404,7 +468,10 @@ class receiver(transmitter):
                 b = self._engine().interleave(torch.from_numpy(np.ascontiguousarray(b, dtype=np.uint8)), inverse=True).cpu().numpy()
             n_cw = len(b) // code.n
             llr = 1.0 - 2.0 * torch.as_tensor(np.asarray(b[: n_cw * code.n], dtype=np.float32))
-            return code.decode(llr, max_iter=self.ldpc_max_iter).cpu().numpy().reshape(-1).astype(np.int64)
+            dec, iters = code.decode(llr, max_iter=self.ldpc_max_iter, want_iters=True)
+            dec, status = self._outer_recover(code, dec, iters, len(b))
+            self._decode_report(iters.cpu().numpy(), status.cpu().numpy())
+            return dec.cpu().numpy().reshape(-1).astype(np.int64)
         if self.encoding == "XOR":
             n = len(bits_encoded)
             known = torch.as_tensor(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.int64))
@@ -413,6 +480,21 @@ class receiver(transmitter):
             k = known.to(dev).repeat(-(-n // len(known)))[:n]
             return torch.bitwise_xor(b, k).cpu().numpy()
         return bits_encoded
+
+    def _outer_recover(self, code, dec, iters, n_coded):
+        """The outer code's part of decode() / receive(): dec [n_cw, k] decisions and iters [n_cw] of all whole
+        codewords of n_coded received coded bits (whole packets) -> (message bits, group statuses).  Without
+        `outer_code`: dec as it is and no statuses."""
+        if self._outer() is None:
+            return dec.reshape(-1), torch.empty(0, dtype=torch.int32, device=dec.device)
+        G, R = self._outer()
+        per_packet = self.packet_length * self.data_bits_per_symbol
+        if n_coded % per_packet:
+            raise ValueError("outer_code: need whole packets of packet_length * data_bits_per_symbol bits")
+        NG = self.outer_layout(n_coded // per_packet)[1]
+        rows = NG * (G + R)
+        fixed, status = self._outer_rs(code, dec.device).recover(dec[:rows], iters[:rows])
+        return fixed[: NG * G].reshape(G, NG, code.k).transpose(0, 1).reshape(-1), status
 
     def _decode_packed(self, eng, packed):
         """PS + decode of receive(): the packed decisions are still on the device; one kernel unpacks them, applies the
@@ -480,7 +562,8 @@ class receiver(transmitter):
             if self.interleave and self.llr_weighting != "noise2d":
                 llr = eng.interleave(llr, inverse=True)
             n_cw = llr.numel() // code.n
-            bits_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter).reshape(-1)
+            dec, iters_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter, want_iters=True)
+            bits_t, status_t = self._outer_recover(code, dec, iters_t, llr.numel())
         else:
             bits_t = self._decode_packed(eng, o["bits"])
         # everything else the host needs, in ONE small copy behind the kernels: first packet's Hs / He, the slopes, and the
@@ -488,7 +571,9 @@ class receiver(transmitter):
         K, F = self.K, self.no_packets
         noise = rate is not None and self.llr_weighting in ("noise", "noise2d")
         small = torch.cat([torch.view_as_real(o["Hs"][0]).reshape(-1), torch.view_as_real(o["He"][0]).reshape(-1), o["slope"]]
-                          + ([snr_t.reshape(-1)] if noise else []) + [o["status"].to(torch.float64)])
+                          + ([snr_t.reshape(-1)] if noise else [])
+                          + ([iters_t.to(torch.float64), status_t.to(torch.float64)] if rate is not None else [])   # (the decode report)
+                          + [o["status"].to(torch.float64)])
         host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=True)
         host.copy_(small, non_blocking=True)
         torch.cuda.current_stream(small.device).synchronize()
@@ -504,6 +589,9 @@ class receiver(transmitter):
             self.last_snr_db = rows[:, : self.data_carriers_per_symbol].copy()
             if self.llr_weighting == "noise2d":
                 self.last_symbol_snr_db = rows[:, self.data_carriers_per_symbol:].copy()
+        if rate is not None:
+            tail = h[len(h) - 1 - status_t.numel() - iters_t.numel(): len(h) - 1]
+            self._decode_report(tail[: iters_t.numel()], tail[iters_t.numel():])
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())

@@ -7,9 +7,11 @@ Layout
   ingest.py  Engine.receive_host: a stream in host memory, piece by piece, with the global-maximum rule kept exact
   OFDM.py    drop-in mirror of the reference's `receiver` class (same names/shapes)
   ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
+  outer.py   OuterRS: Reed-Solomon erasure code across codewords (repairs the codewords the LDPC decoder gives up on)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)
 """
 from .engine import Engine, RxConfig, qpsk_table, square_qam_table  # noqa: F401
 from .ldpc import QCLDPC  # noqa: F401
+from .outer import OuterRS  # noqa: F401
 
 __version__ = "0.1.0"

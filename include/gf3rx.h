@@ -489,6 +489,29 @@ int gf3_ldpc_encode(const gf3_ldpc *code, const uint8_t *d_msg, int64_t n_cw, ui
 int gf3_ldpc_decode(const gf3_ldpc *code, const float *d_llr, int64_t n_cw, int32_t max_iter,
                     uint8_t *d_bits, float *d_app_or_null, int32_t *d_iters_or_null, void *stream);
 
+/*
+ * Outer Reed-Solomon erasure code across codewords (not in the reference): R parity codewords per group of G data
+ * codewords repair any R members of the group that the inner decoder reports as failed (d_iters < 0), exactly.
+ * Stateless: no object, no workspace, no host synchronisation; asynchronous on `stream` of the current device.
+ *   Field GF(2^8), polynomial x^8 + x^4 + x^3 + x^2 + 1 (0x11D).  Byte b of a member is its message bits 8b .. 8b+7,
+ *   most significant first; every array holds one byte per bit (0 / 1) and must be 8-byte aligned.
+ *   Parity is systematic, from the Cauchy matrix C[r][j] = 1 / (r xor (R + j)):  P_r[b] = xor_j C[r][j] D_j[b].
+ *   1 <= R <= 16, G >= 1, G + R <= 255, k a multiple of 8 in [8, 2^20]: GF3_EINVAL otherwise, text in
+ *   gf3_last_error(NULL).  NG == 0 is a no-op.
+ *   - gf3_outer_encode: d_msg_bits [NG*G, k], member j of group g is row g*G + j  ->  d_par_bits [NG*R, k], row g*R + r.
+ *   - gf3_outer_recover: d_bits [(G+R)*NG, k] in TRANSMITTED order, member t of group g is row t*NG + g (t < G data,
+ *     then parity), repaired in place; d_iters [(G+R)*NG] in the same order, < 0 = erased; d_status [NG]:
+ *       0     no data member erased: nothing is written;
+ *       -e_d  e_d data members erased and fewer than e_d parity members survive: nothing is written;
+ *       e_d   the e_d erased data members are rewritten from the surviving data members and the first e_d surviving
+ *             parity members (in index order).  Erased rows are never read; parity rows are never written.
+ *     A member whose decoder converged to a wrong codeword (iters > 0) counts as good: that is not detected.
+ */
+int gf3_outer_encode(const uint8_t *d_msg_bits, int64_t NG, int32_t G, int32_t R, int32_t k,
+                     uint8_t *d_par_bits, void *stream);
+int gf3_outer_recover(uint8_t *d_bits, const int32_t *d_iters, int64_t NG, int32_t G, int32_t R, int32_t k,
+                      int32_t *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
