@@ -19,6 +19,7 @@ import os
 import numpy as np
 import torch
 
+from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
 from .engine import Engine, RxConfig, map_bits
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
@@ -26,10 +27,6 @@ __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 _NP2T = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32,
          np.dtype("int16"): torch.int16, np.dtype("uint8"): torch.uint8}
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "known_bits.npz")
-# channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), of block
-# length CamG.ldpc_n = 1536 (the default), 3072 or 6144 coded bits
-QCLDPC_ENCODINGS = {"QCLDPC-1/2": "1/2", "QCLDPC-2/3": "2/3", "QCLDPC-3/4": "3/4", "QCLDPC-5/6": "5/6"}
-QCLDPC_LIFTING = {1536: 64, 3072: 128, 6144: 256}          # ldpc_n -> lifting size Z (24 block columns)
 _codes = {}
 
 
@@ -151,60 +148,21 @@ class CamG:
         """OFDM.py:106-109 (replica built inside gf3_ctx_create)."""
         return self._engine().chirp_replica()
 
+    # ---- the coded chain ("QCLDPC-*": coding.py) ------------------------------------------------------------------------
+    def _chain(self) -> CodedChain:
+        """The coding attributes as they are at this call; codes come from this module's `_qcldpc_code`, looked up late."""
+        return CodedChain(self.encoding, self.ldpc_n, self.ldpc_max_iter, self.llr_weighting, self.interleave, self.fused_llr,
+                          self.outer_code, per_packet=self.packet_length * self.data_bits_per_symbol,
+                          make_code=lambda *a, **kw: _qcldpc_code(*a, **kw))
+
     def _qcldpc_rate(self):
-        """Rate of a "QCLDPC-*" encoding, else None.  The interleaver exists on these encodings only."""
-        rate = QCLDPC_ENCODINGS.get(self.encoding)
-        if self.interleave and rate is None:
-            raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
-        if rate is None:
-            self._outer()                       # (ValueError: the outer code exists on these encodings only)
-        return rate
-
-    def _qcldpc(self, rate, device=None):
-        """The code of this rate at block length `ldpc_n`, on `device` (None: the current one)."""
-        Z = QCLDPC_LIFTING.get(self.ldpc_n)
-        if Z is None:
-            raise ValueError(f"ldpc_n must be one of {', '.join(map(str, QCLDPC_LIFTING))}, not {self.ldpc_n!r}")
-        # (the default length keeps the (rate, device) call, which is what a stand-in for `_qcldpc_code` takes)
-        return _qcldpc_code(rate, device) if Z == 64 else _qcldpc_code(rate, device, Z=Z)
-
-    def _outer(self):
-        """(G, R) of `outer_code`, or None.  The outer code exists on the "QCLDPC-*" encodings only."""
-        if self.outer_code is None:
-            return None
-        if QCLDPC_ENCODINGS.get(self.encoding) is None:
-            raise ValueError(f"outer_code needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
-        try:
-            G, R = (int(v) for v in self.outer_code)
-        except (TypeError, ValueError):
-            raise ValueError(f"outer_code must be None or (G, R), not {self.outer_code!r}")
-        return G, R
+        """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave or outer_code on another encoding)."""
+        return self._chain().rate()
 
     def outer_layout(self, F):
-        """(cap, NG) for F packets: the whole codewords they hold and the outer-code groups among them (NG = 0 without
-        `outer_code`).  Member t of group g travels as codeword t NG + g; codewords NG (G + R) .. cap - 1 and the rest
-        of the last packet are fill."""
-        per_packet = self.packet_length * self.data_bits_per_symbol
-        gr = self._outer()
-        if gr is None:
-            return F * per_packet // self.ldpc_n, 0
-        from .outer import layout
-        return layout(F, per_packet, self.ldpc_n, *gr)
-
-    def _outer_rs(self, code, device=None):
-        from .outer import OuterRS
-        G, R = self._outer()
-        return OuterRS(G, R, code.k, device)
-
-    def _decode_report(self, iters, status):
-        """`last_decode_report` from the decoder's iteration counts and (outer code) the group statuses, host arrays."""
-        status = np.asarray(status)
-        if len(status):                                         # (outer code: the members of the groups; the rest is fill)
-            iters = iters[: len(status) * sum(self._outer())]
-        failed = np.flatnonzero(np.asarray(iters) < 0)
-        self.last_decode_report = {"codewords": int(len(iters)), "inner_failed": int(len(failed)),
-                                   "recovered": int(status[status > 0].sum()), "groups_failed": int((status < 0).sum()),
-                                   "failed_codewords": failed.astype(np.int64)}
+        """(cap, NG) for F packets: the whole codewords they hold and the outer-code groups among them (NG = 0 without one).
+        Member t of group g travels as codeword t NG + g; codewords NG (G + R) .. cap - 1 and the last packet's rest are fill."""
+        return self._chain().outer_layout(F)
 
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
@@ -231,34 +189,16 @@ class transmitter(CamG):
         if self.encoding == "LDPC":
             raise NotImplementedError("LDPC encoding is out of scope (pyldpc; marked broken in the reference, OFDM.py:21)")
         bits = np.asarray(bits)
-        rate = self._qcldpc_rate()
-        if rate is not None:
-            # QC-LDPC (not in the reference): zero padding to whole codewords, encoded on the GPU; the codewords then
-            # fill packets like uncoded bits (the coin-flip fill below)
-            code = self._qcldpc(rate)
-            if self._outer() is None:
-                msg = np.concatenate([bits.astype(np.uint8) & 1, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
-            else:
-                # outer code: the smallest packet count whose groups hold the message; zero padding to whole groups; the
-                # parity codewords; member t of group g is sent as codeword t NG + g (data members first)
-                from .outer import packets_for
-                G, R = self._outer()
-                rs = self._outer_rs(code)
-                F = packets_for(len(bits), self.packet_length * self.data_bits_per_symbol, code.n, code.k, G, R)
-                NG = self.outer_layout(F)[1]
-                data = torch.zeros(NG * G * code.k, dtype=torch.uint8)
-                data[: len(bits)] = torch.from_numpy(bits.astype(np.uint8) & 1)
-                data = data.to(rs.device).reshape(NG, G, code.k)
-                par = rs.encode(data).reshape(NG, R, code.k)
-                msg = torch.cat([data.transpose(0, 1), par.transpose(0, 1)]).contiguous().reshape(-1)
-            bits = code.encode(torch.as_tensor(msg)).cpu().numpy().reshape(-1).astype(np.int64)
+        chain = self._chain()
+        rate = chain.rate()
+        if rate is not None:                                           # QC-LDPC (not in the reference): the codewords
+            bits = chain.encode(bits, rate)                            # fill packets like uncoded bits (the fill below)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
             mask = np.resize(np.asarray(self.known_sequence[:self.data_bits_per_symbol]), bits.shape)
             bits = bits ^ mask.astype(bits.dtype)
         # fill the last packet with coin flips (OFDM.py:168-173, 178-185): ONE draw from the legacy global RNG, of
         # exactly the missing length, so a seeded run consumes the generator as the reference does
-        per_packet = self.packet_length * self.data_bits_per_symbol
-        missing = -len(bits) % per_packet
+        missing = -len(bits) % chain.per_packet
         bits = np.concatenate([bits, np.random.binomial(n=1, p=0.5, size=(missing,))])
         if self.interleave:                                            # whole packets, the fill included
             sent = self._engine().interleave(torch.from_numpy(bits.astype(np.uint8)))
@@ -457,21 +397,13 @@ class receiver(transmitter):
     def decode(self, bits_encoded):
         if self.encoding == "LDPC":
             raise NotImplementedError("LDPC decoding is out of scope (pyldpc; marked broken in the reference, OFDM.py:21)")
-        rate = self._qcldpc_rate()
+        chain = self._chain()
+        rate = chain.rate()
         if rate is not None:
             # hard-input decoding (LLR = +-1) of the whole codewords in the stream; receive() decodes from soft values
-            code = self._qcldpc(rate)
-            b = np.asarray(bits_encoded)
-            if self.interleave:
-                if len(b) % (self.packet_length * self.data_bits_per_symbol):
-                    raise ValueError("interleave: decode() needs whole packets of packet_length * data_bits_per_symbol bits")
-                b = self._engine().interleave(torch.from_numpy(np.ascontiguousarray(b, dtype=np.uint8)), inverse=True).cpu().numpy()
-            n_cw = len(b) // code.n
-            llr = 1.0 - 2.0 * torch.as_tensor(np.asarray(b[: n_cw * code.n], dtype=np.float32))
-            dec, iters = code.decode(llr, max_iter=self.ldpc_max_iter, want_iters=True)
-            dec, status = self._outer_recover(code, dec, iters, len(b))
-            self._decode_report(iters.cpu().numpy(), status.cpu().numpy())
-            return dec.cpu().numpy().reshape(-1).astype(np.int64)
+            dec, iters, status = chain.decode(chain.code(rate), chain.hard_llrs(bits_encoded, self._engine))
+            self.last_decode_report = decode_report(iters.cpu().numpy(), status.cpu().numpy(), chain.outer())
+            return dec.cpu().numpy().astype(np.int64)
         if self.encoding == "XOR":
             n = len(bits_encoded)
             known = torch.as_tensor(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.int64))
@@ -480,21 +412,6 @@ class receiver(transmitter):
             k = known.to(dev).repeat(-(-n // len(known)))[:n]
             return torch.bitwise_xor(b, k).cpu().numpy()
         return bits_encoded
-
-    def _outer_recover(self, code, dec, iters, n_coded):
-        """The outer code's part of decode() / receive(): dec [n_cw, k] decisions and iters [n_cw] of all whole
-        codewords of n_coded received coded bits (whole packets) -> (message bits, group statuses).  Without
-        `outer_code`: dec as it is and no statuses."""
-        if self._outer() is None:
-            return dec.reshape(-1), torch.empty(0, dtype=torch.int32, device=dec.device)
-        G, R = self._outer()
-        per_packet = self.packet_length * self.data_bits_per_symbol
-        if n_coded % per_packet:
-            raise ValueError("outer_code: need whole packets of packet_length * data_bits_per_symbol bits")
-        NG = self.outer_layout(n_coded // per_packet)[1]
-        rows = NG * (G + R)
-        fixed, status = self._outer_rs(code, dec.device).recover(dec[:rows], iters[:rows])
-        return fixed[: NG * G].reshape(G, NG, code.k).transpose(0, 1).reshape(-1), status
 
     def _decode_packed(self, eng, packed):
         """PS + decode of receive(): the packed decisions are still on the device; one kernel unpacks them, applies the
@@ -510,12 +427,8 @@ class receiver(transmitter):
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
-        if self.llr_weighting not in ("csi", "noise", "noise2d"):
-            raise ValueError(f"llr_weighting must be 'csi', 'noise' or 'noise2d', not {self.llr_weighting!r}")
-        fused = bool(self.fused_llr) and self._qcldpc_rate() is not None
-        if fused and self.llr_weighting != "csi":
-            raise ValueError(f"fused_llr needs llr_weighting 'csi': {self.llr_weighting!r} weights by the whole packet's "
-                             "residuals, which the fused kernel does not have")
+        chain = self._chain()
+        rate, fused = chain.check_receive()                     # (the refusals: before any GPU work)
         r = _as_samples(signal)
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
@@ -523,79 +436,43 @@ class receiver(transmitter):
         # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
         # stay on the one-shot path.
         chunk = getattr(self, "host_chunk_samples", None)
-        rate = self._qcldpc_rate()
         if not graph_output and (chunk or len(r) > (1 << 27)):
             if rate is not None:
                 raise NotImplementedError(f"encoding {self.encoding!r}: the piece-wise host path of long recordings (or "
                                           "host_chunk_samples) has no soft-decision decoding; receive shorter recordings")
             return self._receive_chunked(eng, r, int(chunk or (1 << 25)))
+        # 1. sync
         x = eng._samples(r)
         peaks = eng.sync_stream(x)
         starts = (peaks + 2)[:-1]                               # OFDM.py:393-395
         self.no_packets = int(starts.numel())
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
-        fused = fused and not graph_output                      # (the plots need eq: the staged path)
-        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if graph_output else ("eq",) if rate is not None and not fused else ())
-        o = eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
+        # 2. demodulate
+        o = chain.demodulate(eng, x, starts, rate, fused, graph_output)
+        # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
+        need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
         if rate is not None:
-            # soft path: weighted max-log LLRs -> layered min-sum on the whole codewords of the stream
-            code = self._qcldpc(rate, eng.device)
-            if self.llr_weighting in ("noise", "noise2d"):
-                if self.llr_weighting == "noise":
-                    var = eng.noise_estimate(o["eq"])
-                    llr = eng.soft_demap_nw(o["eq"], var)
-                else:
-                    var, var_s = eng.noise_estimate2(o["eq"])
-                    llr = eng.soft_demap_nw2(o["eq"], var, var_s, deinterleave=self.interleave)
-                # SNR report 10 log10(Es / v') with the demapper's floor, [F, C]: rides home in the small copy below
-                pts = self._tables()[0]
-                floor = 1e-6 * var.mean(dim=1, keepdim=True)
-                es = float(np.mean(np.abs(pts) ** 2))
-                snr_t = 10.0 * torch.log10(es / torch.maximum(var, floor))
-                if self.llr_weighting == "noise2d":                 # the same report per symbol, [F, D], behind it
-                    snr_t = torch.cat([snr_t, 10.0 * torch.log10(es / torch.maximum(var_s, floor))], dim=1)
-            elif fused:
-                llr = o["llr"]                                  # samples -> weighted LLRs in the one launch above
-            else:
-                llr = eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
-            if self.interleave and self.llr_weighting != "noise2d":
-                llr = eng.interleave(llr, inverse=True)
-            n_cw = llr.numel() // code.n
-            dec, iters_t = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter, want_iters=True)
-            bits_t, status_t = self._outer_recover(code, dec, iters_t, llr.numel())
+            llr, snr = chain.llrs(eng, o, self._tables()[0])
+            bits_t, need["iters"], need["status"] = chain.decode(chain.code(rate, eng.device), llr)
         else:
             bits_t = self._decode_packed(eng, o["bits"])
-        # everything else the host needs, in ONE small copy behind the kernels: first packet's Hs / He, the slopes, and the
-        # ragged-packet flag (a packet that runs past the recording: the reference's get_symbols fails on it)
-        K, F = self.K, self.no_packets
-        noise = rate is not None and self.llr_weighting in ("noise", "noise2d")
-        small = torch.cat([torch.view_as_real(o["Hs"][0]).reshape(-1), torch.view_as_real(o["He"][0]).reshape(-1), o["slope"]]
-                          + ([snr_t.reshape(-1)] if noise else [])
-                          + ([iters_t.to(torch.float64), status_t.to(torch.float64)] if rate is not None else [])   # (the decode report)
-                          + [o["status"].to(torch.float64)])
-        host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=True)
-        host.copy_(small, non_blocking=True)
-        torch.cuda.current_stream(small.device).synchronize()
-        if host[-1] != 0:                                       # (before anything is printed: get_symbols fails first in the reference)
+        # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
+        # packet that runs past the recording: the reference's get_symbols fails on it)
+        got = fetch({**need, **snr, "ragged": o["status"]})
+        if got["ragged"][0] != 0:                               # (before anything is printed: get_symbols fails first in the reference)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
         bits = bits_t.cpu().numpy().astype(np.int64) if rate is not None else bits_t.numpy()
-        h = host.numpy()
-        Hest_start0, Hest_end0 = h[: 2 * K].view(np.complex128).copy(), h[2 * K: 4 * K].view(np.complex128).copy()
-        self._last_slope = h[4 * K: 4 * K + F].copy()
-        if noise:
-            rows = h[4 * K + F: 4 * K + F + snr_t.numel()].reshape(F, -1)
-            self.last_snr_db = rows[:, : self.data_carriers_per_symbol].copy()
-            if self.llr_weighting == "noise2d":
-                self.last_symbol_snr_db = rows[:, self.data_carriers_per_symbol:].copy()
+        self._last_slope = got["slope"]
+        for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only
+            setattr(self, name, got[name])
         if rate is not None:
-            tail = h[len(h) - 1 - status_t.numel() - iters_t.numel(): len(h) - 1]
-            self._decode_report(tail[: iters_t.numel()], tail[iters_t.numel():])
+            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer())
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())
-        return bits, Hest_start0, Hest_end0
+        return bits, got["Hs0"], got["He0"]
 
     def _receive_chunked(self, eng, r, chunk):
         try:

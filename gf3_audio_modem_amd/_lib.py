@@ -3,6 +3,8 @@ missing or does not load, importing the engine raises."""
 import ctypes as C
 import os
 
+import torch
+
 from .build import lib_path
 
 GF3_OK, GF3_EINVAL, GF3_EHIP, GF3_ENOMEM, GF3_ERANGE, GF3_ENODETECT = 0, -1, -2, -3, -4, -5
@@ -12,9 +14,29 @@ c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
 
 
+class Gf3Error(RuntimeError):
+    pass
+
+
 def ptr(t):
     """A tensor's device (or host) address as the ABI takes it; None stays NULL."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """The current torch stream of `device` as the ABI takes it."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def last_error():
+    """The calling thread's last error text (the buffer is per thread: gf3_last_error does not look at its argument)."""
+    return load().gf3_last_error(None).decode()
+
+
+def check(rc, prefix=True):
+    """An ABI return code: ValueError for GF3_EINVAL, else Gf3Error, with the library's text (prefix=False: bare, as the create calls report)."""
+    if rc != 0:
+        raise (ValueError if rc == GF3_EINVAL else Gf3Error)(f"gf3rx error {rc}: {last_error()}" if prefix else last_error())
 
 
 class Gf3Config(C.Structure):

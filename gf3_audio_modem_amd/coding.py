@@ -1,0 +1,178 @@
+"""The coded chain of the "QCLDPC-*" encodings in one place: settings and refusals, message bits -> coded bits, what the
+demodulator must produce, its outputs -> LLRs, LLRs (or hard bits) -> message bits, the decode report.  The façade
+(OFDM.py) builds a CodedChain from its public attributes at every call and keeps what is the reference's: XOR, the
+coin-flip fill, the prints.  `fetch` is the one small device-to-host copy receive() ends with."""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from .outer import OuterRS, from_transmitted, layout, packets_for, to_transmitted
+
+# channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), of block
+# length CamG.ldpc_n = 1536 (the default), 3072 or 6144 coded bits
+QCLDPC_ENCODINGS = {"QCLDPC-1/2": "1/2", "QCLDPC-2/3": "2/3", "QCLDPC-3/4": "3/4", "QCLDPC-5/6": "5/6"}
+QCLDPC_LIFTING = {1536: 64, 3072: 128, 6144: 256}          # ldpc_n -> lifting size Z (24 block columns)
+
+
+def fetch(tensors):
+    """{name: tensor}, all on one device -> {name: NumPy array of the tensor's shape and dtype}, through ONE
+    concatenation, ONE copy (pinned and non-blocking from a GPU) and ONE stream synchronisation.  The values travel as
+    float64: complex ones as (re, im) pairs, integers converted, which is exact for the int32 values sent here."""
+    parts = [(torch.view_as_real(t) if t.is_complex() else t).reshape(-1).to(torch.float64) for t in tensors.values()]
+    small = torch.cat(parts)
+    host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=small.is_cuda)
+    host.copy_(small, non_blocking=True)
+    if small.is_cuda:
+        torch.cuda.current_stream(small.device).synchronize()
+    out, at = {}, 0
+    for (name, t), part in zip(tensors.items(), parts):
+        a = host[at: at + part.numel()].numpy().copy()
+        at += part.numel()
+        a = a.view(np.complex128) if t.is_complex() else a
+        out[name] = a.astype(torch.empty(0, dtype=t.dtype).numpy().dtype, copy=False).reshape(tuple(t.shape))
+    return out
+
+
+def decode_report(iters, status, outer=None):
+    """`last_decode_report` from the decoder's iteration counts and the group statuses (host arrays; no statuses without
+    an outer code).  With the outer code (G, R) it covers the members of the groups -- the rest is fill."""
+    iters, status = np.asarray(iters), np.asarray(status)
+    if len(status):
+        iters = iters[: len(status) * sum(outer)]
+    failed = np.flatnonzero(iters < 0)
+    return {"codewords": int(len(iters)), "inner_failed": int(len(failed)), "recovered": int(status[status > 0].sum()),
+            "groups_failed": int((status < 0).sum()), "failed_codewords": failed.astype(np.int64)}
+
+
+@dataclass
+class CodedChain:
+    """The façade's coding attributes as they are at one call, and the steps that depend on them."""
+    encoding: str
+    ldpc_n: int
+    ldpc_max_iter: int
+    llr_weighting: str
+    interleave: bool
+    fused_llr: bool
+    outer_code: object
+    per_packet: int                         # coded bits a packet carries
+    make_code: object                       # (rate, device[, Z=Z]) -> QCLDPC: the façade's `_qcldpc_code`
+
+    # ---- settings and their refusals -----------------------------------------------------------------------------------
+    def rate(self):
+        """Rate of a "QCLDPC-*" encoding, else None.  The interleaver exists on these encodings only."""
+        rate = QCLDPC_ENCODINGS.get(self.encoding)
+        if self.interleave and rate is None:
+            raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        if rate is None:
+            self.outer()                        # (ValueError: the outer code exists on these encodings only)
+        return rate
+
+    def code(self, rate, device=None):
+        """The code of this rate at block length `ldpc_n`, on `device` (None: the current one)."""
+        Z = QCLDPC_LIFTING.get(self.ldpc_n)
+        if Z is None:
+            raise ValueError(f"ldpc_n must be one of {', '.join(map(str, QCLDPC_LIFTING))}, not {self.ldpc_n!r}")
+        # (the default length keeps the (rate, device) call, which is what a stand-in for `_qcldpc_code` takes)
+        return self.make_code(rate, device) if Z == 64 else self.make_code(rate, device, Z=Z)
+
+    def outer(self):
+        """(G, R) of `outer_code`, or None.  The outer code exists on the "QCLDPC-*" encodings only."""
+        if self.outer_code is None:
+            return None
+        if QCLDPC_ENCODINGS.get(self.encoding) is None:
+            raise ValueError(f"outer_code needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        try:
+            G, R = (int(v) for v in self.outer_code)
+        except (TypeError, ValueError):
+            raise ValueError(f"outer_code must be None or (G, R), not {self.outer_code!r}")
+        return G, R
+
+    def outer_layout(self, F):
+        """(cap, NG) for F packets: the whole codewords they hold and the outer-code groups among them (0 without one)."""
+        gr = self.outer()
+        return (F * self.per_packet // self.ldpc_n, 0) if gr is None else layout(F, self.per_packet, self.ldpc_n, *gr)
+
+    def check_receive(self):
+        """What receive() refuses before any GPU work -> (rate, fused: take the sample-to-LLR path)."""
+        if self.llr_weighting not in ("csi", "noise", "noise2d"):
+            raise ValueError(f"llr_weighting must be 'csi', 'noise' or 'noise2d', not {self.llr_weighting!r}")
+        rate = self.rate()
+        fused = rate is not None and bool(self.fused_llr)
+        if fused and self.llr_weighting != "csi":
+            raise ValueError(f"fused_llr needs llr_weighting 'csi': {self.llr_weighting!r} weights by the whole packet's "
+                             "residuals, which the fused kernel does not have")
+        return rate, fused
+
+    # ---- transmit side ---------------------------------------------------------------------------------------------------
+    def encode(self, bits, rate):
+        """Message bits -> coded bits (int64, host): zero padding to whole codewords, encoded on the GPU.  Outer code: the
+        smallest packet count whose groups hold the message, zero padding to whole groups, then the parity codewords."""
+        code = self.code(rate)
+        gr = self.outer()
+        bits = bits.astype(np.uint8) & 1
+        if gr is None:
+            msg = np.concatenate([bits, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
+        else:
+            G, R = gr
+            rs = OuterRS(G, R, code.k)
+            NG = self.outer_layout(packets_for(len(bits), self.per_packet, code.n, code.k, G, R))[1]
+            data = torch.zeros(NG * G * code.k, dtype=torch.uint8)
+            data[: len(bits)] = torch.from_numpy(bits)
+            data = data.to(rs.device).reshape(NG, G, code.k)
+            msg = to_transmitted(data, rs.encode(data).reshape(NG, R, code.k)).reshape(-1)
+        return code.encode(torch.as_tensor(msg)).cpu().numpy().reshape(-1).astype(np.int64)
+
+    # ---- receive side ----------------------------------------------------------------------------------------------------
+    def demodulate(self, eng, x, starts, rate, fused, plots):
+        """receive()'s demodulator call: Hs, He, slopes, ragged flag; eq for the staged soft path, eq and Hest for the plots
+        (which therefore take the staged path); LLRs straight from the samples when fused."""
+        fused = fused and not plots
+        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plots else ("eq",) if rate is not None and not fused else ())
+        return eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
+
+    def llrs(self, eng, o, points):
+        """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: SNR rows in dB} of the noise
+        weightings: 10 log10(Es / v') with the demapper's floor, `last_snr_db` [F, C], `last_symbol_snr_db` [F, D])."""
+        snr = {}
+        if self.llr_weighting == "csi":
+            llr = o["llr"] if "llr" in o else eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
+        else:
+            if self.llr_weighting == "noise":
+                var, var_s = eng.noise_estimate(o["eq"]), None
+                llr = eng.soft_demap_nw(o["eq"], var)
+            else:
+                var, var_s = eng.noise_estimate2(o["eq"])
+                llr = eng.soft_demap_nw2(o["eq"], var, var_s, deinterleave=self.interleave)
+            floor = 1e-6 * var.mean(dim=1, keepdim=True)
+            es = float(np.mean(np.abs(points) ** 2))
+            snr["last_snr_db"] = 10.0 * torch.log10(es / torch.maximum(var, floor))
+            if var_s is not None:
+                snr["last_symbol_snr_db"] = 10.0 * torch.log10(es / torch.maximum(var_s, floor))
+        if self.interleave and self.llr_weighting != "noise2d":     # ("noise2d" de-interleaved inside its demapper)
+            llr = eng.interleave(llr, inverse=True)
+        return llr, snr
+
+    def hard_llrs(self, bits, engine):
+        """Received hard bits -> +-1 LLRs in coded order; `engine()` is asked for only to undo the interleaver."""
+        b = np.asarray(bits)
+        if self.interleave:
+            if len(b) % self.per_packet:
+                raise ValueError("interleave: decode() needs whole packets of packet_length * data_bits_per_symbol bits")
+            b = engine().interleave(torch.from_numpy(np.ascontiguousarray(b, dtype=np.uint8)), inverse=True).cpu().numpy()
+        return 1.0 - 2.0 * torch.as_tensor(np.asarray(b, dtype=np.float32))
+
+    def decode(self, code, llr):
+        """LLRs in coded order -> (message bits, iters [n_cw], group statuses) on the code's device: layered min-sum on every
+        whole codeword, then the outer code rewrites up to R given-up members per group (no statuses without one)."""
+        n_cw = llr.numel() // code.n
+        dec, iters = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter, want_iters=True)
+        gr = self.outer()
+        if gr is None:
+            return dec.reshape(-1), iters, torch.empty(0, dtype=torch.int32, device=dec.device)
+        if llr.numel() % self.per_packet:
+            raise ValueError("outer_code: need whole packets of packet_length * data_bits_per_symbol bits")
+        NG = self.outer_layout(llr.numel() // self.per_packet)[1]
+        rows = NG * sum(gr)
+        fixed, status = OuterRS(*gr, code.k, dec.device).recover(dec[:rows], iters[:rows])
+        return from_transmitted(fixed, NG, gr[0]).reshape(-1), iters, status

@@ -8,6 +8,7 @@ library, constructing an Engine raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from dataclasses import dataclass, field
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, ingest
+from ._lib import Gf3Error, ptr as _ptr  # noqa: F401  (Gf3Error is importable from here as before)
 from .ingest import DIRECT_PIECE_BYTES, host_pieces  # noqa: F401  (the cut of a host stream, importable from here as before)
 
 _TORCH_DT = {_lib.DT_F64: torch.float64, _lib.DT_F32: torch.float32,
@@ -104,13 +106,6 @@ class RxConfig:
         return map_bits(kb, self.const_points, self.const_bits)
 
 
-class Gf3Error(RuntimeError):
-    pass
-
-
-_ptr = _lib.ptr
-
-
 class Engine:
     """One gf3_ctx on one GPU."""
 
@@ -145,9 +140,7 @@ class Engine:
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self.lib.gf3_ctx_create(C.byref(g), C.byref(h))
-        if rc != 0:
-            msg = self.lib.gf3_last_error(None).decode()
-            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(msg)
+        _lib.check(rc, prefix=False)
         self._h = h
         self._sync_mode = 0
         self._tls = threading.local()
@@ -169,13 +162,10 @@ class Engine:
             pass
 
     # ------------------------------------------------------------------ helpers
-    def _check(self, rc):
-        if rc != 0:
-            msg = self.lib.gf3_last_error(self._h).decode()
-            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(f"gf3rx error {rc}: {msg}")
+    _check = staticmethod(_lib.check)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     def _samples(self, x):
         """1-D (or any-D contiguous) device tensor of samples in the configured dtype."""
@@ -190,6 +180,36 @@ class Engine:
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
+    def _dev(self, x, dtype=torch.complex128):
+        """x as a contiguous tensor of `dtype` (complex128 unless said otherwise) on this engine's device."""
+        return torch.as_tensor(x, dtype=dtype).to(self.device).contiguous()
+
+    def _out(self, out, shape, dtype, what, name="out"):
+        """`out` if it is contiguous, of `dtype` and of prod(shape) = `what` elements (else ValueError); a fresh tensor for None."""
+        if out is None:
+            return self._new(shape, dtype)
+        if out.dtype != dtype or out.numel() != math.prod(shape) or not out.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[1]} tensor of {what} elements")
+        return out
+
+    def _wanted(self, want, F, names):
+        """The optional demodulator outputs among `names` that `want` asks for, allocated for F packets."""
+        cfg, c128 = self.cfg, torch.complex128
+        kinds = {"eq": ((F * cfg.D, cfg.C), c128), "Hs": ((F, cfg.K), c128), "He": ((F, cfg.K), c128),
+                 "slope": ((F,), torch.float64), "Hest": ((F, cfg.D, cfg.K), c128)}
+        o = {k: self._new(*kinds[k]) for k in names if k in want and k in kinds}
+        if "status" in want:                                       # (the kernels only ever set bits in it)
+            o["status"] = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        return o
+
+    def _split_work(self, F, split):
+        """(workspace, mode) of a demodulator call.  The two-phase form needs a workspace (pilot sums, and Hs / He / slope
+        when they are not asked for): allocated exactly when the library would choose that form (at most 2 x CUs packets)."""
+        work = None
+        if F and (split or (split is None and self.lib.gf3_demod_split_plan(self._h, F, 0, None, None))):
+            work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)
+        return work, 0 if split is None else (2 if split else 1)
+
     # ------------------------------------------------------------------ ABI calls
     def chirp_replica(self):
         out = np.empty(self.cfg.chirp_length)
@@ -199,12 +219,9 @@ class Engine:
     def rfft_batch(self, x, offsets, out=None):
         """[n_sym, N/2+1] complex128 spectra of the N samples starting at each offset."""
         x = self._samples(x)
-        offsets = torch.as_tensor(offsets, dtype=torch.int64).to(self.device).contiguous()
+        offsets = self._dev(offsets, torch.int64)
         n = offsets.numel()
-        if out is None:
-            out = self._new((n, self.cfg.N // 2 + 1), torch.complex128)
-        elif out.dtype != torch.complex128 or out.numel() != n * (self.cfg.N // 2 + 1) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous complex128 tensor of n_sym * (N/2+1) elements")
+        out = self._out(out, (n, self.cfg.N // 2 + 1), torch.complex128, "n_sym * (N/2+1)")
         self._check(self.lib.gf3_rfft_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
         return out
 
@@ -214,27 +231,16 @@ class Engine:
         split: None -- the library chooses between one packet per workgroup and the two-phase form for long packets,
         few at a time (gf3_demod_frames_ex: pilot sums, estimate, data symbols spread over the chip; the reference's own
         geometry of 3 packets x 220 symbols); False / True force the one or the other."""
-        cfg = self.cfg
         x = self._samples(x)
-        off = torch.as_tensor(frame_offsets, dtype=torch.int64).to(self.device).contiguous()
+        off = self._dev(frame_offsets, torch.int64)
         F = off.numel()
         bits = out_bits if out_bits is not None else self._new((F, self.bytes_per_frame), torch.uint8)
-        o = {"bits": bits}
-        if "eq" in want: o["eq"] = self._new((F * cfg.D, cfg.C), torch.complex128)
-        if "Hs" in want: o["Hs"] = self._new((F, cfg.K), torch.complex128)
-        if "He" in want: o["He"] = self._new((F, cfg.K), torch.complex128)
-        if "slope" in want: o["slope"] = self._new((F,), torch.float64)
-        if "Hest" in want: o["Hest"] = self._new((F, cfg.D, cfg.K), torch.complex128)
-        if "status" in want: o["status"] = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        # the two-phase form needs a workspace (pilot sums, and Hs / He / slope when they are not asked for): allocated exactly
-        # when the library would choose that form (at most 2 x CUs packets)
-        work = None
-        if F and (split or (split is None and self.lib.gf3_demod_split_plan(self._h, F, 0, None, None))):
-            work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)
+        o = {"bits": bits, **self._wanted(want, F, ("eq", "Hs", "He", "slope", "Hest", "status"))}
+        work, mode = self._split_work(F, split)
         self._check(self.lib.gf3_demod_frames_ex(
             self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(bits), _ptr(o.get("eq")), _ptr(o.get("Hs")),
             _ptr(o.get("He")), _ptr(o.get("slope")), _ptr(o.get("Hest")), _ptr(o.get("status")),
-            _ptr(work), 0 if split is None else (2 if split else 1), self._stream()))
+            _ptr(work), mode, self._stream()))
         return o
 
     def demod_frames_llr(self, x, frame_offsets, weight="csi", want=(), split=None, out=None):
@@ -243,34 +249,21 @@ class Engine:
         'slope', 'status'.  weight: "csi" -- |H^|^2, what demod_frames(want eq, Hs, He) + soft_demap_csi give -- or "none"
         (soft_demap(eq, 1.0)); an int goes to the library as it is.  split: as in demod_frames.  out: optional contiguous
         float32 tensor of F*D*C*mu elements to write into."""
-        cfg = self.cfg
         x = self._samples(x)
-        off = torch.as_tensor(frame_offsets, dtype=torch.int64).to(self.device).contiguous()
+        off = self._dev(frame_offsets, torch.int64)
         F = off.numel()
-        n = F * cfg.D * cfg.C * cfg.mu
         if isinstance(weight, str):
             if weight not in ("csi", "none"):
                 raise ValueError(f"weight must be 'csi' or 'none', not {weight!r}")
             weight = 1 if weight == "csi" else 0
-        if out is None:
-            llr = self._new((n,), torch.float32)
-        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
-        else:
-            llr = out
-        o = {"llr": llr}
-        if "Hs" in want: o["Hs"] = self._new((F, cfg.K), torch.complex128)
-        if "He" in want: o["He"] = self._new((F, cfg.K), torch.complex128)
-        if "slope" in want: o["slope"] = self._new((F,), torch.float64)
-        if "status" in want: o["status"] = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        work = None
-        if F and (split or (split is None and self.lib.gf3_demod_split_plan(self._h, F, 0, None, None))):
-            work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)
+        llr = self._llr_out(out, F)
+        o = {"llr": llr, **self._wanted(want, F, ("Hs", "He", "slope", "status"))}
+        work, mode = self._split_work(F, split)
         rc = self.lib.gf3_demod_frames_llr(
             self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(llr), int(weight), _ptr(o.get("Hs")), _ptr(o.get("He")),
-            _ptr(o.get("slope")), _ptr(o.get("status")), _ptr(work), 0 if split is None else (2 if split else 1), self._stream())
+            _ptr(o.get("slope")), _ptr(o.get("status")), _ptr(work), mode, self._stream())
         if rc != 0:                                                # (a bad `weight` is the library's to refuse: Gf3Error)
-            raise Gf3Error(f"gf3rx error {rc}: {self.lib.gf3_last_error(self._h).decode()}")
+            raise Gf3Error(f"gf3rx error {rc}: {_lib.last_error()}")
         return o
 
     def demod_plan(self, F, split=None):
@@ -283,15 +276,12 @@ class Engine:
     def equalise(self, data, start, end, want=("Hest",)):
         """receiver.equalise on frequency-domain symbols [F,D,K], [F,P,K], [F,P,K]."""
         cfg = self.cfg
-        dev = lambda a: torch.as_tensor(a, dtype=torch.complex128).to(self.device).contiguous()
-        data, start, end = dev(data), dev(start), dev(end)
+        data, start, end = self._dev(data), self._dev(start), self._dev(end)
         F = data.shape[0]
         if tuple(data.shape) != (F, cfg.D, cfg.K) or tuple(start.shape) != (F, cfg.P, cfg.K) or tuple(end.shape) != (F, cfg.P, cfg.K):
             raise ValueError("equalise: shapes must be [F,D,K], [F,P,K], [F,P,K]")
-        o = {"eq_all": self._new((F * cfg.D, cfg.K), torch.complex128),
-             "Hs": self._new((F, cfg.K), torch.complex128), "He": self._new((F, cfg.K), torch.complex128),
-             "slope": self._new((F,), torch.float64), "bits": self._new((F, self.bytes_per_frame), torch.uint8)}
-        if "Hest" in want: o["Hest"] = self._new((F, cfg.D, cfg.K), torch.complex128)
+        o = {"eq_all": self._new((F * cfg.D, cfg.K), torch.complex128), "bits": self._new((F, self.bytes_per_frame), torch.uint8),
+             **self._wanted(("Hs", "He", "slope") + tuple(want), F, ("Hs", "He", "slope", "Hest"))}
         self._check(self.lib.gf3_equalise(
             self._h, _ptr(data), _ptr(start), _ptr(end), F, _ptr(o["eq_all"]), _ptr(o["Hs"]), _ptr(o["He"]),
             _ptr(o["slope"]), _ptr(o.get("Hest")), _ptr(o["bits"]), self._stream()))
@@ -308,12 +298,7 @@ class Engine:
         want_peak: the fp64 peak VALUES are asked for, so the all-fp64 kernel runs whatever `screened` says (and a `work`
         given reports 0).  sync_frames_last() tells which way a call went."""
         x = self._samples(x)
-        if out_starts is not None:
-            if out_starts.dtype != torch.int64 or out_starts.numel() != F or not out_starts.is_contiguous():
-                raise ValueError("out_starts must be a contiguous int64 tensor of F elements")
-            starts = out_starts
-        else:
-            starts = self._new((F,), torch.int64)
+        starts = self._out(out_starts, (F,), torch.int64, "F", name="out_starts")
         peak = self._new((F,), torch.float64) if want_peak else None
         if screened and work is None:
             work = self.sync_frames_workspace(F)
@@ -405,15 +390,15 @@ class Engine:
         bits_packed: uint8 [F, bytes_per_frame] (the format demod_frames writes); filler: complex [K],
         value of every non-data carrier.  Returns [F, stride] samples: row f =
         [gaps[f] zeros | chirp | P known symbols | D data symbols | P known symbols | zeros]."""
-        bits = torch.as_tensor(bits_packed, dtype=torch.uint8).to(self.device).contiguous()
+        bits = self._dev(bits_packed, torch.uint8)
         if bits.dim() != 2 or bits.shape[1] != self.bytes_per_frame:
             raise ValueError("bits_packed must be [F, bytes_per_frame]")
         F = bits.shape[0]
-        fill = torch.as_tensor(filler, dtype=torch.complex128).to(self.device).contiguous()
+        fill = self._dev(filler)
         if fill.numel() != self.cfg.K:
             raise ValueError("filler must hold K values (one per carrier)")
         stride = stride or self.cfg.frame_len
-        g = None if gaps is None else torch.as_tensor(gaps, dtype=torch.int64).to(self.device).contiguous()
+        g = None if gaps is None else self._dev(gaps, torch.int64)
         if g is not None and F and int(g.max()) + self.cfg.frame_len > stride:
             raise ValueError("gap + packet does not fit the row stride")
         out = self._new((F, stride), out_dtype)
@@ -433,8 +418,8 @@ class Engine:
         """Known-channel zero forcing (Weekend Challenge.ipynb cells 9-17): FFT(rx) / fft(h, N) on the data carriers,
         then demap.  Returns (eq [n_sym, C] complex128, bits [n_sym, C, mu] uint8, idx [n_sym, C] uint8)."""
         x = self._samples(x)
-        off = torch.as_tensor(sym_offsets, dtype=torch.int64).to(self.device).contiguous()
-        taps = torch.as_tensor(np.asarray(h, dtype=np.float64)).to(self.device).contiguous()
+        off = self._dev(sym_offsets, torch.int64)
+        taps = self._dev(np.asarray(h, dtype=np.float64), torch.float64)
         n = off.numel()
         eq = self._new((n, self.cfg.C), torch.complex128)
         bits = self._new((n, self.cfg.C, self.cfg.mu), torch.uint8)
@@ -445,7 +430,7 @@ class Engine:
         return eq, bits, idx
 
     def demap_hard(self, sym):
-        sym = torch.as_tensor(sym, dtype=torch.complex128).to(self.device).contiguous()
+        sym = self._dev(sym)
         n = sym.numel()
         bits = self._new(tuple(sym.shape) + (self.cfg.mu,), torch.uint8)
         idx = self._new(tuple(sym.shape), torch.uint8)
@@ -453,13 +438,8 @@ class Engine:
         return bits, idx
 
     def soft_demap(self, sym, noise_var, out=None):
-        sym = torch.as_tensor(sym, dtype=torch.complex128).to(self.device).contiguous()
-        if out is None:
-            llr = self._new(tuple(sym.shape) + (self.cfg.mu,), torch.float32)
-        elif out.dtype != torch.float32 or out.numel() != sym.numel() * self.cfg.mu or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of n * mu elements")
-        else:
-            llr = out
+        sym = self._dev(sym)
+        llr = self._out(out, tuple(sym.shape) + (self.cfg.mu,), torch.float32, "n * mu")
         self._check(self.lib.gf3_soft_demap(self._h, _ptr(sym), sym.numel(), float(noise_var), _ptr(llr), self._stream()))
         return llr
 
@@ -468,24 +448,19 @@ class Engine:
         reference's magnitude model |Hs| + (|He| - |Hs|)(l + P/2)/(D + P), from demod_frames' 'eq' [F*D, C] and 'Hs' /
         'He' [F, K].  -> float32 [F*D*C*mu] in the reference's bit order (packet -> symbol -> carrier -> bit)."""
         cfg = self.cfg
-        eq = torch.as_tensor(eq, dtype=torch.complex128).to(self.device).contiguous()
-        Hs = torch.as_tensor(Hs, dtype=torch.complex128).to(self.device).contiguous()
-        He = torch.as_tensor(He, dtype=torch.complex128).to(self.device).contiguous()
+        eq, Hs, He = self._dev(eq), self._dev(Hs), self._dev(He)
         F = Hs.numel() // cfg.K
         if Hs.numel() != F * cfg.K or He.numel() != Hs.numel() or eq.numel() != F * cfg.D * cfg.C:
             raise ValueError("soft_demap_csi: need Hs, He [F, K] and eq [F*D, C]")
-        n = F * cfg.D * cfg.C * cfg.mu
-        if out is None:
-            llr = self._new((n,), torch.float32)
-        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
-        else:
-            llr = out
+        llr = self._llr_out(out, F)
         self._check(self.lib.gf3_soft_demap_csi(self._h, _ptr(eq), _ptr(Hs), _ptr(He), F, _ptr(llr), self._stream()))
         return llr
 
+    def _llr_out(self, out, F):
+        return self._out(out, (F * self.cfg.D * self.cfg.C * self.cfg.mu,), torch.float32, "F*D*C*mu")
+
     def _eq_packets(self, eq, who):
-        eq = torch.as_tensor(eq, dtype=torch.complex128).to(self.device).contiguous()
+        eq = self._dev(eq)
         per = self.cfg.D * self.cfg.C
         if eq.numel() % per:
             raise ValueError(f"{who}: need eq [F*D, C]")
@@ -505,18 +480,11 @@ class Engine:
         in one pass over eq [F*D, C] with var [F, C] from noise_estimate; weight 1 for a packet whose mean variance is 0
         or not finite, LLR 0 on a carrier whose variance is not finite.  -> float32 [F*D*C*mu], order and sign as
         soft_demap_csi."""
-        cfg = self.cfg
         eq, F = self._eq_packets(eq, "soft_demap_nw")
-        var = torch.as_tensor(var, dtype=torch.float64).to(self.device).contiguous()
-        if var.numel() != F * cfg.C:
+        var = self._dev(var, torch.float64)
+        if var.numel() != F * self.cfg.C:
             raise ValueError("soft_demap_nw: need var [F, C] for eq [F*D, C]")
-        n = F * cfg.D * cfg.C * cfg.mu
-        if out is None:
-            llr = self._new((n,), torch.float32)
-        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
-        else:
-            llr = out
+        llr = self._llr_out(out, F)
         self._check(self.lib.gf3_soft_demap_nw(self._h, _ptr(eq), _ptr(var), F, _ptr(llr), self._stream()))
         return llr
 
@@ -535,19 +503,11 @@ class Engine:
         max(var_c[f, c] var_s[f, l] / vbar[f], 1e-6 vbar[f]), vbar = mean_c var_c; weight 1 for a packet whose vbar is 0
         or not finite, LLR 0 where var_c or var_s is not finite.  deinterleave: write each packet's LLRs in coded order
         (the packet interleaver undone), else in transmitted order.  -> float32 [F*D*C*mu], sign as soft_demap_csi."""
-        cfg = self.cfg
         eq, F = self._eq_packets(eq, "soft_demap_nw2")
-        var_c = torch.as_tensor(var_c, dtype=torch.float64).to(self.device).contiguous()
-        var_s = torch.as_tensor(var_s, dtype=torch.float64).to(self.device).contiguous()
-        if var_c.numel() != F * cfg.C or var_s.numel() != F * cfg.D:
+        var_c, var_s = self._dev(var_c, torch.float64), self._dev(var_s, torch.float64)
+        if var_c.numel() != F * self.cfg.C or var_s.numel() != F * self.cfg.D:
             raise ValueError("soft_demap_nw2: need var_c [F, C] and var_s [F, D] for eq [F*D, C]")
-        n = F * cfg.D * cfg.C * cfg.mu
-        if out is None:
-            llr = self._new((n,), torch.float32)
-        elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of F*D*C*mu elements")
-        else:
-            llr = out
+        llr = self._llr_out(out, F)
         self._check(self.lib.gf3_soft_demap_nw_cs(self._h, _ptr(eq), _ptr(var_c), _ptr(var_s), F, int(bool(deinterleave)),
                                                   _ptr(llr), self._stream()))
         return llr

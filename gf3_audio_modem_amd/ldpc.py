@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import Gf3Error
+from ._lib import Gf3Error, ptr as _ptr
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 RATES = ("1/2", "2/3", "3/4", "5/6")
@@ -30,10 +30,6 @@ def shift_table(rate, Z=64):
         raise ValueError(f"no QC-LDPC family of lifting size Z={Z} (one of {', '.join(map(str, LIFTINGS))})")
     with open(os.path.join(_DATA, f"qcldpc_z{Z}.json")) as f:
         return np.array(json.load(f)["rates"][rate], dtype=np.int16)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class QCLDPC:
@@ -56,9 +52,7 @@ class QCLDPC:
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             rc = self.lib.gf3_ldpc_create(sh.shape[0], sh.shape[1], self.Z, sh.ctypes.data_as(C.c_void_p), C.byref(h))
-        if rc != 0:
-            msg = self.lib.gf3_last_error(None).decode()
-            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(msg)
+        _lib.check(rc, prefix=False)
         self._h = h
         self.n = int(self.lib.gf3_ldpc_n(h))
         self.k = int(self.lib.gf3_ldpc_k(h))
@@ -74,14 +68,6 @@ class QCLDPC:
         except Exception:
             pass
 
-    def _check(self, rc):
-        if rc != 0:
-            msg = self.lib.gf3_last_error(None).decode()
-            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(f"gf3rx error {rc}: {msg}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _rows(self, x, dtype, width, what):
         x = torch.as_tensor(x).to(device=self.device, dtype=dtype).contiguous()
         if x.numel() % width:
@@ -92,7 +78,7 @@ class QCLDPC:
         """[n_cw, k] (or flat n_cw*k) 0/1 message bits -> uint8 [n_cw, n] codewords on the device, systematic first."""
         m = self._rows(msg, torch.uint8, self.k, "encode")
         cw = torch.empty((m.shape[0], self.n), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.gf3_ldpc_encode(self._h, _ptr(m), m.shape[0], _ptr(cw), self._stream()))
+        _lib.check(self.lib.gf3_ldpc_encode(self._h, _ptr(m), m.shape[0], _ptr(cw), _lib.stream(self.device)))
         return cw
 
     def decode(self, llr, max_iter=50, want_app=False, want_iters=False):
@@ -103,8 +89,8 @@ class QCLDPC:
         bits = torch.empty((F, self.k), dtype=torch.uint8, device=self.device)
         app = torch.empty((F, self.n), dtype=torch.float32, device=self.device) if want_app else None
         its = torch.empty((F,), dtype=torch.int32, device=self.device) if want_iters else None
-        self._check(self.lib.gf3_ldpc_decode(self._h, _ptr(x), F, int(max_iter), _ptr(bits), _ptr(app), _ptr(its),
-                                             self._stream()))
+        _lib.check(self.lib.gf3_ldpc_decode(self._h, _ptr(x), F, int(max_iter), _ptr(bits), _ptr(app), _ptr(its),
+                                             _lib.stream(self.device)))
         if not (want_app or want_iters):
             return bits
         return (bits,) + ((app,) if want_app else ()) + ((its,) if want_iters else ())

@@ -4,16 +4,10 @@ R parity codewords per group of G data codewords, computed over GF(2^8) on the m
 the group whose inner decoding failed (iters < 0).  Both directions run in hand-written HIP (csrc/gf3rx_outer.hip);
 there is no host implementation to fall back to.  layout() is the arithmetic the façade places groups in packets with.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
-from .engine import Gf3Error
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._lib import Gf3Error, ptr as _ptr
 
 
 def layout(F, per_packet, n, G, R):
@@ -38,6 +32,16 @@ def transmitted_index(g, t, NG):
     return t * NG + g
 
 
+def to_transmitted(data, parity):
+    """data [NG, G, k], parity [NG, R, k] (tensors) -> [(G + R) NG, k]: row transmitted_index(g, t, NG) is member t of group g."""
+    return torch.cat([data.transpose(0, 1), parity.transpose(0, 1)]).reshape(-1, data.shape[-1])
+
+
+def from_transmitted(rows, NG, G):
+    """The inverse on the data members: rows in transmitted order -> [NG G, k], member t of group g in row g G + t."""
+    return rows[: NG * G].reshape(G, NG, rows.shape[-1]).transpose(0, 1).reshape(NG * G, rows.shape[-1])
+
+
 class OuterRS:
     """The code of G data + R parity members on messages of k bits, on one GPU.  Stateless in the library; this object
     only carries the geometry.  1 <= R <= 16, G >= 1, G + R <= 255, k a multiple of 8 (ValueError otherwise)."""
@@ -48,15 +52,7 @@ class OuterRS:
             raise Gf3Error("no GPU visible: the outer code has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.G, self.R, self.k = int(G), int(R), int(k)
-        self._check(self.lib.gf3_outer_encode(None, 0, self.G, self.R, self.k, None, None))     # (the geometry alone)
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self.lib.gf3_last_error(None).decode()
-            raise (ValueError if rc == _lib.GF3_EINVAL else Gf3Error)(f"gf3rx error {rc}: {msg}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self.lib.gf3_outer_encode(None, 0, self.G, self.R, self.k, None, None))     # (the geometry alone)
 
     def _rows(self, x, per_group, what):
         x = torch.as_tensor(x).to(device=self.device, dtype=torch.uint8).contiguous()
@@ -71,7 +67,7 @@ class OuterRS:
         NG = m.shape[0] // self.G
         par = torch.empty((NG * self.R, self.k), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            self._check(self.lib.gf3_outer_encode(_ptr(m), NG, self.G, self.R, self.k, _ptr(par), self._stream()))
+            _lib.check(self.lib.gf3_outer_encode(_ptr(m), NG, self.G, self.R, self.k, _ptr(par), _lib.stream(self.device)))
         return par
 
     def recover(self, bits, iters):
@@ -85,5 +81,5 @@ class OuterRS:
             raise ValueError(f"recover: {it.numel()} iteration counts for {b.shape[0]} rows")
         status = torch.empty((NG,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            self._check(self.lib.gf3_outer_recover(_ptr(b), _ptr(it), NG, self.G, self.R, self.k, _ptr(status), self._stream()))
+            _lib.check(self.lib.gf3_outer_recover(_ptr(b), _ptr(it), NG, self.G, self.R, self.k, _ptr(status), _lib.stream(self.device)))
         return b, status
