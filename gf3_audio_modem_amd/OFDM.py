@@ -113,6 +113,12 @@ class CamG:
         # fill of the last packet from the message, so every whole codeword counts and the fill shows up as failed.
         self.outer_code = None
         self.last_decode_report = None
+        # "QCLDPC-*": codeword_crc = True makes the last 32 message bits of every codeword, parity codewords included, the
+        # CRC-32 of the others (crc.py): a codeword then carries k - 32 message bits.  decode() / receive() check it after
+        # the LDPC decoder; a codeword that converged on something whose CRC does not match is erased for the outer code
+        # like one the decoder gave up on, and counted in two more report keys, "crc_failed" and "crc_failed_codewords"
+        # ("inner_failed" / "failed_codewords" stay the codewords that did not converge).  Both ends must agree on it.
+        self.codeword_crc = False
         self._engines = {}
 
     def __repr__(self):
@@ -153,10 +159,10 @@ class CamG:
         """The coding attributes as they are at this call; codes come from this module's `_qcldpc_code`, looked up late."""
         return CodedChain(self.encoding, self.ldpc_n, self.ldpc_max_iter, self.llr_weighting, self.interleave, self.fused_llr,
                           self.outer_code, per_packet=self.packet_length * self.data_bits_per_symbol,
-                          make_code=lambda *a, **kw: _qcldpc_code(*a, **kw))
+                          make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc))
 
     def _qcldpc_rate(self):
-        """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave or outer_code on another encoding)."""
+        """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
         return self._chain().rate()
 
     def outer_layout(self, F):
@@ -401,8 +407,9 @@ class receiver(transmitter):
         rate = chain.rate()
         if rate is not None:
             # hard-input decoding (LLR = +-1) of the whole codewords in the stream; receive() decodes from soft values
-            dec, iters, status = chain.decode(chain.code(rate), chain.hard_llrs(bits_encoded, self._engine))
-            self.last_decode_report = decode_report(iters.cpu().numpy(), status.cpu().numpy(), chain.outer())
+            dec, iters, status, bad = chain.decode(chain.code(rate), chain.hard_llrs(bits_encoded, self._engine))
+            self.last_decode_report = decode_report(iters.cpu().numpy(), status.cpu().numpy(), chain.outer(),
+                                                    None if bad is None else bad.cpu().numpy())
             return dec.cpu().numpy().astype(np.int64)
         if self.encoding == "XOR":
             n = len(bits_encoded)
@@ -454,7 +461,9 @@ class receiver(transmitter):
         need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
         if rate is not None:
             llr, snr = chain.llrs(eng, o, self._tables()[0])
-            bits_t, need["iters"], need["status"] = chain.decode(chain.code(rate, eng.device), llr)
+            bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
+            if bad is not None:                                 # (codeword_crc: the flags ride in the same copy)
+                need["crc_bad"] = bad
         else:
             bits_t = self._decode_packed(eng, o["bits"])
         # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
@@ -468,7 +477,7 @@ class receiver(transmitter):
         for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only
             setattr(self, name, got[name])
         if rate is not None:
-            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer())
+            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())

@@ -8,10 +8,12 @@ Layout
   OFDM.py    drop-in mirror of the reference's `receiver` class (same names/shapes)
   ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
   outer.py   OuterRS: Reed-Solomon erasure code across codewords (repairs the codewords the LDPC decoder gives up on)
+  crc.py     CodewordCRC: CRC-32 per codeword (catches the codewords the LDPC decoder converged on wrongly)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)
 """
 from .engine import Engine, RxConfig, qpsk_table, square_qam_table  # noqa: F401
 from .ldpc import QCLDPC  # noqa: F401
 from .outer import OuterRS  # noqa: F401
+from .crc import CodewordCRC  # noqa: F401
 
 __version__ = "0.1.0"

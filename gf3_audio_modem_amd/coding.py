@@ -1,12 +1,14 @@
 """The coded chain of the "QCLDPC-*" encodings in one place: settings and refusals, message bits -> coded bits, what the
-demodulator must produce, its outputs -> LLRs, LLRs (or hard bits) -> message bits, the decode report.  The façade
-(OFDM.py) builds a CodedChain from its public attributes at every call and keeps what is the reference's: XOR, the
-coin-flip fill, the prints.  `fetch` is the one small device-to-host copy receive() ends with."""
+demodulator must produce, its outputs -> LLRs, LLRs (or hard bits) -> message bits (through the per-codeword CRC where
+`codeword_crc` is set), the decode report.  The façade (OFDM.py) builds a CodedChain from its public attributes at every
+call and keeps what is the reference's: XOR, the coin-flip fill, the prints.  `fetch` is the one small device-to-host copy
+receive() ends with."""
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
+from .crc import CRC_BITS, CodewordCRC
 from .outer import OuterRS, from_transmitted, layout, packets_for, to_transmitted
 
 # channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), of block
@@ -34,15 +36,21 @@ def fetch(tensors):
     return out
 
 
-def decode_report(iters, status, outer=None):
+def decode_report(iters, status, outer=None, crc_bad=None):
     """`last_decode_report` from the decoder's iteration counts and the group statuses (host arrays; no statuses without
-    an outer code).  With the outer code (G, R) it covers the members of the groups -- the rest is fill."""
+    an outer code).  With the outer code (G, R) it covers the members of the groups -- the rest is fill.  crc_bad: the
+    per-codeword CRC flags where the codewords carry one (`iters` are the decoder's own counts, as they were before
+    CodewordCRC.check): two more keys, the codewords that converged (iters > 0) on something whose CRC does not match."""
     iters, status = np.asarray(iters), np.asarray(status)
     if len(status):
         iters = iters[: len(status) * sum(outer)]
     failed = np.flatnonzero(iters < 0)
-    return {"codewords": int(len(iters)), "inner_failed": int(len(failed)), "recovered": int(status[status > 0].sum()),
-            "groups_failed": int((status < 0).sum()), "failed_codewords": failed.astype(np.int64)}
+    rep = {"codewords": int(len(iters)), "inner_failed": int(len(failed)), "recovered": int(status[status > 0].sum()),
+           "groups_failed": int((status < 0).sum()), "failed_codewords": failed.astype(np.int64)}
+    if crc_bad is not None:
+        wrong = np.flatnonzero((iters > 0) & (np.asarray(crc_bad)[: len(iters)] != 0))
+        rep.update(crc_failed=int(len(wrong)), crc_failed_codewords=wrong.astype(np.int64))
+    return rep
 
 
 @dataclass
@@ -57,13 +65,16 @@ class CodedChain:
     outer_code: object
     per_packet: int                         # coded bits a packet carries
     make_code: object                       # (rate, device[, Z=Z]) -> QCLDPC: the façade's `_qcldpc_code`
+    codeword_crc: bool = False              # the last 32 message bits of every codeword are the CRC of the others (crc.py)
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
-        """Rate of a "QCLDPC-*" encoding, else None.  The interleaver exists on these encodings only."""
+        """Rate of a "QCLDPC-*" encoding, else None.  The interleaver and the codeword CRC exist on these encodings only."""
         rate = QCLDPC_ENCODINGS.get(self.encoding)
         if self.interleave and rate is None:
             raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        if self.codeword_crc and rate is None:
+            raise ValueError(f"codeword_crc needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
         if rate is None:
             self.outer()                        # (ValueError: the outer code exists on these encodings only)
         return rate
@@ -107,20 +118,24 @@ class CodedChain:
     # ---- transmit side ---------------------------------------------------------------------------------------------------
     def encode(self, bits, rate):
         """Message bits -> coded bits (int64, host): zero padding to whole codewords, encoded on the GPU.  Outer code: the
-        smallest packet count whose groups hold the message, zero padding to whole groups, then the parity codewords."""
+        smallest packet count whose groups hold the message, zero padding to whole groups, then the parity codewords.
+        `codeword_crc`: a codeword carries k = code.k - 32 of these bits and the CRC of them, parity codewords included."""
         code = self.code(rate)
         gr = self.outer()
         bits = bits.astype(np.uint8) & 1
+        k = code.k - CRC_BITS if self.codeword_crc else code.k
         if gr is None:
-            msg = np.concatenate([bits, np.zeros(-len(bits) % code.k, dtype=np.uint8)])
+            msg = np.concatenate([bits, np.zeros(-len(bits) % k, dtype=np.uint8)])
         else:
             G, R = gr
-            rs = OuterRS(G, R, code.k)
-            NG = self.outer_layout(packets_for(len(bits), self.per_packet, code.n, code.k, G, R))[1]
-            data = torch.zeros(NG * G * code.k, dtype=torch.uint8)
+            rs = OuterRS(G, R, k)
+            NG = self.outer_layout(packets_for(len(bits), self.per_packet, code.n, k, G, R))[1]
+            data = torch.zeros(NG * G * k, dtype=torch.uint8)
             data[: len(bits)] = torch.from_numpy(bits)
-            data = data.to(rs.device).reshape(NG, G, code.k)
-            msg = to_transmitted(data, rs.encode(data).reshape(NG, R, code.k)).reshape(-1)
+            data = data.to(rs.device).reshape(NG, G, k)
+            msg = to_transmitted(data, rs.encode(data).reshape(NG, R, k)).reshape(-1)
+        if self.codeword_crc:
+            msg = CodewordCRC(code.k).attach(torch.as_tensor(msg))
         return code.encode(torch.as_tensor(msg)).cpu().numpy().reshape(-1).astype(np.int64)
 
     # ---- receive side ----------------------------------------------------------------------------------------------------
@@ -163,16 +178,22 @@ class CodedChain:
         return 1.0 - 2.0 * torch.as_tensor(np.asarray(b, dtype=np.float32))
 
     def decode(self, code, llr):
-        """LLRs in coded order -> (message bits, iters [n_cw], group statuses) on the code's device: layered min-sum on every
-        whole codeword, then the outer code rewrites up to R given-up members per group (no statuses without one)."""
+        """LLRs in coded order -> (message bits, iters [n_cw], group statuses, CRC flags [n_cw] or None) on the code's
+        device: layered min-sum on every whole codeword, then the outer code rewrites up to R given-up members per group
+        (no statuses without one).  `codeword_crc`: the CRC of every codeword is checked in between, the message bits are
+        the payloads, and the outer code also rewrites the members that converged on something whose CRC does not match;
+        the iteration counts returned are the decoder's own."""
         n_cw = llr.numel() // code.n
         dec, iters = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter, want_iters=True)
+        bad, erase = None, iters
+        if self.codeword_crc:
+            dec, bad, erase = CodewordCRC(code.k, dec.device).check(dec, iters.clone())
         gr = self.outer()
         if gr is None:
-            return dec.reshape(-1), iters, torch.empty(0, dtype=torch.int32, device=dec.device)
+            return dec.reshape(-1), iters, torch.empty(0, dtype=torch.int32, device=dec.device), bad
         if llr.numel() % self.per_packet:
             raise ValueError("outer_code: need whole packets of packet_length * data_bits_per_symbol bits")
         NG = self.outer_layout(llr.numel() // self.per_packet)[1]
         rows = NG * sum(gr)
-        fixed, status = OuterRS(*gr, code.k, dec.device).recover(dec[:rows], iters[:rows])
-        return from_transmitted(fixed, NG, gr[0]).reshape(-1), iters, status
+        fixed, status = OuterRS(*gr, dec.shape[1], dec.device).recover(dec[:rows], erase[:rows])
+        return from_transmitted(fixed, NG, gr[0]).reshape(-1), iters, status, bad

@@ -11,6 +11,7 @@
 //   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide
 //   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
 //   gf3rx_outer.hip          rs_encode_kernel, rs_recover_kernel + gf3_outer_encode, gf3_outer_recover (field arithmetic: gf3rx_outer.h)
+//   gf3rx_crc.hip            crc_kernel + gf3_crc_attach, gf3_crc_check (per-codeword CRC-32)
 //   gf3rx_noise.hip          noise_estimate_kernel, soft_demap_nw_kernel + gf3_noise_estimate, gf3_soft_demap_nw; their
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
 //                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)

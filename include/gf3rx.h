@@ -505,12 +505,36 @@ int gf3_ldpc_decode(const gf3_ldpc *code, const float *d_llr, int64_t n_cw, int3
  *       -e_d  e_d data members erased and fewer than e_d parity members survive: nothing is written;
  *       e_d   the e_d erased data members are rewritten from the surviving data members and the first e_d surviving
  *             parity members (in index order).  Erased rows are never read; parity rows are never written.
- *     A member whose decoder converged to a wrong codeword (iters > 0) counts as good: that is not detected.
+ *     A member whose decoder converged to a wrong codeword (iters > 0) counts as good: this call does not detect it.
+ *     gf3_crc_check (below) does, where the codewords carry a CRC: it turns such a member's iters negative first.
  */
 int gf3_outer_encode(const uint8_t *d_msg_bits, int64_t NG, int32_t G, int32_t R, int32_t k,
                      uint8_t *d_par_bits, void *stream);
 int gf3_outer_recover(uint8_t *d_bits, const int32_t *d_iters, int64_t NG, int32_t G, int32_t R, int32_t k,
                       int32_t *d_status, void *stream);
+
+/*
+ * Per-codeword CRC-32 (not in the reference): the last 32 of a codeword's k message bits are the CRC of the k - 32
+ * payload bits before them, so that a codeword the LDPC decoder converged on WRONGLY (zero syndrome, iters > 0) is seen
+ * and can be erased for the outer code; an undetected error has probability 2^-32 per codeword.
+ * Stateless: no object, no workspace, no host synchronisation; asynchronous on `stream` of the current device.
+ *   CRC-32/IEEE (reflected polynomial 0xEDB88320, initial value and final xor 0xFFFFFFFF: zlib's crc32) of the payload
+ *   bytes, byte b being payload bits 8b .. 8b+7, most significant first (the bytes of the outer code); message bit
+ *   k - 32 + i is bit 31 - i of the CRC.  Every array holds one byte per bit (0 / 1; only bit 0 of an input byte is
+ *   read) and the bit arrays must be 8-byte aligned; the payload array and the message array must not overlap.
+ *   k a multiple of 8 in [40, 7936]: GF3_EINVAL otherwise, text in gf3_last_error(NULL).  n_cw == 0 is a no-op.
+ *   - gf3_crc_attach: d_payload [n_cw, k - 32]  ->  d_msg [n_cw, k], each payload followed by its CRC field.
+ *   - gf3_crc_check: d_msg [n_cw, k]; every output may be NULL.
+ *       d_bad [n_cw]             1 where the field differs from the CRC of the row's payload, else 0;
+ *       d_payload [n_cw, k - 32] the payload of every row, bad or not;
+ *       d_iters [n_cw]           updated in place: v > 0 on a bad row becomes -v, every other value stays.  Afterwards
+ *                                d_iters < 0 means "erase" to gf3_outer_recover, and |v| < max_iter on a bad row records
+ *                                that the decoder had converged.
+ *     Two runs give identical bytes (no atomics).
+ */
+int gf3_crc_attach(const uint8_t *d_payload, int64_t n_cw, int32_t k, uint8_t *d_msg, void *stream);
+int gf3_crc_check(const uint8_t *d_msg, int64_t n_cw, int32_t k, uint8_t *d_payload_or_null,
+                  int32_t *d_iters_or_null, uint8_t *d_bad_or_null, void *stream);
 
 #ifdef __cplusplus
 }
