@@ -119,6 +119,17 @@ class CamG:
         # like one the decoder gave up on, and counted in two more report keys, "crc_failed" and "crc_failed_codewords"
         # ("inner_failed" / "failed_codewords" stay the codewords that did not converge).  Both ends must agree on it.
         self.codeword_crc = False
+        # "QCLDPC-*", staged path: phase_tracking = True follows a common phase and a phase slope (a delay) from data symbol
+        # to data symbol inside every packet, decision-directed (Engine.track_phase), and takes them out of the equalised
+        # symbols before the LLR weights: for packets during which the channel moves between the pilot blocks (a phone
+        # moved by a centimetre), which the reference's two-point channel model cannot follow.  receive() then leaves
+        # the track (a in rad, b in rad per bin) [packets, D, 2] in `last_phase_track` -- its last row should be near zero:
+        # the model is anchored at the end pilots, anything else is a cycle slip -- and which symbols were measured (1) or
+        # coasted (0) [packets, D] in `last_phase_measured`; both are None otherwise.  ValueError with fused_llr and on the
+        # other encodings; the plots show the untracked symbols.
+        self.phase_tracking = False
+        self.last_phase_track = None
+        self.last_phase_measured = None
         self._engines = {}
 
     def __repr__(self):
@@ -159,7 +170,8 @@ class CamG:
         """The coding attributes as they are at this call; codes come from this module's `_qcldpc_code`, looked up late."""
         return CodedChain(self.encoding, self.ldpc_n, self.ldpc_max_iter, self.llr_weighting, self.interleave, self.fused_llr,
                           self.outer_code, per_packet=self.packet_length * self.data_bits_per_symbol,
-                          make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc))
+                          make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc),
+                          phase_tracking=bool(self.phase_tracking))
 
     def _qcldpc_rate(self):
         """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
@@ -474,8 +486,9 @@ class receiver(transmitter):
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
         bits = bits_t.cpu().numpy().astype(np.int64) if rate is not None else bits_t.numpy()
         self._last_slope = got["slope"]
-        for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only
-            setattr(self, name, got[name])
+        self.last_phase_track = self.last_phase_measured = None
+        for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only;
+            setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
         if rate is not None:
             self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
         print("Number of received bits:            " + str(len(bits)))

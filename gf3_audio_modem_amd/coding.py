@@ -66,6 +66,7 @@ class CodedChain:
     per_packet: int                         # coded bits a packet carries
     make_code: object                       # (rate, device[, Z=Z]) -> QCLDPC: the façade's `_qcldpc_code`
     codeword_crc: bool = False              # the last 32 message bits of every codeword are the CRC of the others (crc.py)
+    phase_tracking: bool = False            # receive(): Engine.track_phase on the equalised symbols, before the weights
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
@@ -75,6 +76,8 @@ class CodedChain:
             raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
         if self.codeword_crc and rate is None:
             raise ValueError(f"codeword_crc needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        if self.phase_tracking and rate is None:
+            raise ValueError(f"phase_tracking needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
         if rate is None:
             self.outer()                        # (ValueError: the outer code exists on these encodings only)
         return rate
@@ -113,6 +116,9 @@ class CodedChain:
         if fused and self.llr_weighting != "csi":
             raise ValueError(f"fused_llr needs llr_weighting 'csi': {self.llr_weighting!r} weights by the whole packet's "
                              "residuals, which the fused kernel does not have")
+        if fused and self.phase_tracking:
+            raise ValueError("phase_tracking needs fused_llr = False: the fused kernel never materialises the equalised "
+                             "symbols the tracker works on")
         return rate, fused
 
     # ---- transmit side ---------------------------------------------------------------------------------------------------
@@ -147,9 +153,14 @@ class CodedChain:
         return eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
 
     def llrs(self, eng, o, points):
-        """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: SNR rows in dB} of the noise
-        weightings: 10 log10(Es / v') with the demapper's floor, `last_snr_db` [F, C], `last_symbol_snr_db` [F, D])."""
+        """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: rows for the host}: the SNR in dB
+        of the noise weightings, 10 log10(Es / v') with the demapper's floor, `last_snr_db` [F, C], `last_symbol_snr_db`
+        [F, D]; the tracker's `last_phase_track` [F, D, 2] and `last_phase_measured` [F, D] under `phase_tracking`)."""
         snr = {}
+        if self.phase_tracking:
+            # (a copy: the plots keep the untracked symbols)  `last_phase_track` [F, D, 2], `last_phase_measured` [F, D]
+            o = dict(o)
+            o["eq"], snr["last_phase_track"], snr["last_phase_measured"] = eng.track_phase(o["eq"], want_track=True)
         if self.llr_weighting == "csi":
             llr = o["llr"] if "llr" in o else eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
         else:

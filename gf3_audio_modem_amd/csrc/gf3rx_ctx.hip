@@ -262,6 +262,13 @@ extern "C" int gf3_ctx_create(const gf3_config* cfg, gf3_ctx** out) {
     CK(dev_new(c->owned, &c->d_known, known));
     CK(dev_new(c->owned, &c->d_pos, pos));
     CK(dev_new(c->owned, &c->d_clab, clab));
+    {
+        const std::vector<int> bins(cfg->data_bins, cfg->data_bins + cfg->C);
+        int64_t sum = 0;
+        for (int b : bins) sum += b;
+        c->bin_mean = (double)sum / (double)cfg->C;
+        CK(dev_new(c->owned, &c->d_bins, bins));
+    }
     std::vector<int> inv(1 << cfg->mu, 0);
     for (int m = cfg->M - 1; m >= 0; --m) inv[clab[m]] = m;
     CK(dev_new(c->owned, &c->d_idx_of_label, inv));

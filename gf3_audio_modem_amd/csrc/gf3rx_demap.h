@@ -26,6 +26,22 @@ inline bool sep_is_binary(const SepTab& sp, int mu, int& hI, int& hQ) {
     return true;
 }
 
+// binary-indexed grid up to 64-QAM -> its HI, anything else -> 0 (as run_demap chooses its kernels)
+inline int grid_bits(const gf3_ctx* c) {
+    int hI = 0, hQ = 0;
+    return (c->sep.nI > 0 && sep_is_binary(c->sep, c->cfg.mu, hI, hQ) && hI <= 3) ? hI : 0;
+}
+
+// HI > 0: binary-indexed 2^HI x 2^HI grid (levels in registers); HI == 0: any table (literal scan).
+template <int HI>
+struct Levels {
+    double lvI[1 << HI], lvQ[1 << HI];
+    GF3_DEV explicit Levels(const DemapTab& t) {
+#pragma unroll
+        for (int k = 0; k < (1 << HI); ++k) { lvI[k] = t.sep.lvI[k]; lvQ[k] = t.sep.lvQ[k]; }
+    }
+};
+
 // squared distances of one component to the N levels of its axis
 template <int N>
 GF3_DEV void axis_d2(double x, const double (&lv)[N], double (&d)[N]) {

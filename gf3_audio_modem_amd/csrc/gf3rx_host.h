@@ -15,6 +15,7 @@
 //   gf3rx_noise.hip          noise_estimate_kernel, soft_demap_nw_kernel + gf3_noise_estimate, gf3_soft_demap_nw; their
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
 //                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
+//   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
@@ -183,6 +184,8 @@ struct gf3_ctx {
     cplx *d_tw_x[2] = {nullptr, nullptr}, *d_twn_x[2] = {nullptr, nullptr};   // twiddles of plans whose FFT size != N
     int nc_x[2] = {0, 0};
     int *d_pos = nullptr, *d_clab = nullptr;
+    int* d_bins = nullptr;              // [C] data_bins as given (1-based FFT bins in output order): gf3_track_phase's carrier offsets
+    double bin_mean = 0.0;              // their mean
     double *d_cre = nullptr, *d_cim = nullptr;
     CorrPlan frames_plan, stream_plan;
     double qpsk_q = 0.0;

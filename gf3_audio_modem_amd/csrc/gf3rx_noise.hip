@@ -29,16 +29,6 @@ struct NoiseArgs {
     DemapTab t;
 };
 
-// HI > 0: binary-indexed 2^HI x 2^HI grid (levels in registers); HI == 0: any table (literal scan).
-template <int HI>
-struct Levels {
-    double lvI[1 << HI], lvQ[1 << HI];
-    GF3_DEV explicit Levels(const DemapTab& t) {
-#pragma unroll
-        for (int k = 0; k < (1 << HI); ++k) { lvI[k] = t.sep.lvI[k]; lvQ[k] = t.sep.lvQ[k]; }
-    }
-};
-
 // noise_estimate: a workgroup owns 64 consecutive carriers of one packet (lane = carrier: a wave reads 1 KB
 // contiguously per symbol); wave w adds up the symbols l = w, w + 8, w + 16, ... in ascending order, the 8 partial sums
 // meet in LDS and wave 0 adds them in the order w = 0 .. 7, then divides by D.
@@ -321,12 +311,6 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_cs_kernel(NwCsArgs a
         }
         if constexpr (DEINT) irow = addmod(irow, a.step_l, a.nbp);
     }
-}
-
-// binary-indexed grid up to 64-QAM -> its HI, anything else -> 0 (as run_demap chooses its kernels)
-int grid_bits(const gf3_ctx* c) {
-    int hI = 0, hQ = 0;
-    return (c->sep.nI > 0 && sep_is_binary(c->sep, c->cfg.mu, hI, hQ) && hI <= 3) ? hI : 0;
 }
 
 }  // namespace

@@ -512,6 +512,22 @@ class Engine:
                                                   _ptr(llr), self._stream()))
         return llr
 
+    def track_phase(self, eq, out=None, want_track=False):
+        """Per-symbol phase and timing tracking inside each packet (gf3_track_phase): a decision-directed loop with a
+        velocity term follows a common phase a and a phase slope b (rad per bin, around the centre of the data bins)
+        through the packet's D symbols of eq [F*D, C] and takes them out, out = eq exp(-i (a + b kappa_c)); a symbol whose
+        decision-directed error energy exceeds its signal energy (a click, a dropout) coasts.  out: optional contiguous
+        complex128 tensor of F*D*C elements to write into; `eq` itself is allowed (in place).  -> out, or with want_track
+        (out, phase float64 [F, D, 2] = (a, b) after each symbol, measured uint8 [F, D]).  Fixed summation order: two
+        calls give identical bits."""
+        eq, F = self._eq_packets(eq, "track_phase")
+        cfg = self.cfg
+        out = self._out(out, (F * cfg.D, cfg.C), torch.complex128, "F*D*C")
+        phase = self._new((F, cfg.D, 2), torch.float64) if want_track else None
+        measured = self._new((F, cfg.D), torch.uint8) if want_track else None
+        self._check(self.lib.gf3_track_phase(self._h, _ptr(eq), F, _ptr(out), _ptr(phase), _ptr(measured), self._stream()))
+        return (out, phase, measured) if want_track else out
+
     def interleave(self, x, inverse=False):
         """The packet interleaver on whole packets of nbp = D*C*mu elements (gf3_interleave): x is uint8 or float32 with a
         multiple of nbp elements; coded element i of a packet moves to position (i s) mod nbp, `inverse` moves it back.

@@ -455,6 +455,32 @@ int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32
                    void *stream);
 
 /*
+ * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
+ * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
+ * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
+ * decision-directed first-order loop with a velocity term: a common phase a (rad) and a phase slope b (rad per bin)
+ * around the centre of the data band, kappa_c = k_c - mean(k) with k_c = data_bins[c] (the bins, in whatever order).
+ *   state a = b = va = vb = 0 at the start of every packet; per symbol
+ *     pa = a + va, pb = b + vb;   z_c = eq[l, c] exp(-i (pa + pb kappa_c));
+ *     s_c = the point gf3_demap_hard picks for z_c (in-order scan, strict <); a z_c with a non-finite part is left out;
+ *     r_c = z_c conj(s_c);  S0 = sum r_c, S1 = sum kappa_c r_c, S2 = sum kappa_c^2 r_c, E = sum |z_c - s_c|^2,
+ *     P = sum |s_c|^2;   da = atan2(Im S0, Re S0) (0 for S0 = 0), u = exp(-i da), den = Re(u S2);
+ *     measured <=> all seven real sums finite, den > 0 and E <= P:  a' = pa + da, b' = pb + Im(u S1) / den;
+ *     else the symbol coasts: a' = pa, b' = pb;   va = a' - a, vb = b' - b, a = a', b = b';
+ *     out[l, c] = eq[l, c] exp(-i (a + b kappa_c))   (non-finite inputs stay non-finite).
+ *   No amplitude tracking, no cycle-slip detection (the model is anchored at the end pilots: phase[f, D-1] should be
+ *   near zero), no per-carrier tracking; the lock range is first order: the change of velocity per symbol at the band
+ *   edge must stay well inside the decision region.
+ *   d_eq_c128, d_out_c128 [F*D, C]; d_out == d_eq is allowed (in place).  d_phase_f64 [F, D, 2] = (a, b) after each
+ *   symbol, d_measured [F, D] = 0 / 1; both optional.  One workgroup per packet (the symbols depend on each other), a
+ *   thread owns carriers t, t + 512, ...; each sum is formed in fp64 in a fixed order (a thread's carriers ascending, an
+ *   xor butterfly 32, 16, .. 1 over the 64 lanes, the eight waves in order): two calls give identical bits.  No
+ *   workspace.  F == 0 is a no-op; C <= 4096 (GF3_ERANGE beyond).
+ */
+int gf3_track_phase(gf3_ctx *ctx, const void *d_eq_c128, int64_t F, void *d_out_c128, double *d_phase_f64_or_null,
+                    uint8_t *d_measured_or_null, void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64, 128
  * or 256; the shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, Z) for the
  * circulant whose row z has its one in column (z + s) mod Z.  Block columns 0 .. nb-mb-1 carry the message (systematic
