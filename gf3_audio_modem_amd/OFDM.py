@@ -130,6 +130,18 @@ class CamG:
         self.phase_tracking = False
         self.last_phase_track = None
         self.last_phase_measured = None
+        # every encoding: impulse_blanking = True replaces, between sync and demodulation, the few samples of each packet's
+        # body that stand more than blanking_threshold x the packet's own level above its baseline (and blanking_guard
+        # samples on each side of them) by the baseline (Engine.blank_impulses): a click of a few milliseconds then costs
+        # its own samples instead of the whole symbol, pilot symbols included.  receive() leaves the blanked samples per
+        # symbol [packets, 2P + D] in `last_blanked` and (baseline, level) [packets, 2] in `last_sample_level`; both are
+        # None otherwise.  It cannot see a click under the threshold, does not treat the chirp, and blanks a handful of
+        # samples of a clean packet too: opt-in.  NotImplementedError on the piece-wise host path.
+        self.impulse_blanking = False
+        self.blanking_threshold = 4.5
+        self.blanking_guard = 8
+        self.last_blanked = None
+        self.last_sample_level = None
         self._engines = {}
 
     def __repr__(self):
@@ -448,6 +460,7 @@ class receiver(transmitter):
         print(self)
         chain = self._chain()
         rate, fused = chain.check_receive()                     # (the refusals: before any GPU work)
+        blanking = Engine.check_blanking(self.blanking_threshold, self.blanking_guard) if self.impulse_blanking else None
         r = _as_samples(signal)
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
@@ -456,6 +469,9 @@ class receiver(transmitter):
         # stay on the one-shot path.
         chunk = getattr(self, "host_chunk_samples", None)
         if not graph_output and (chunk or len(r) > (1 << 27)):
+            if blanking:
+                raise NotImplementedError("impulse_blanking: the piece-wise host path of long recordings (or "
+                                          "host_chunk_samples) has no blanking pass; receive shorter recordings")
             if rate is not None:
                 raise NotImplementedError(f"encoding {self.encoding!r}: the piece-wise host path of long recordings (or "
                                           "host_chunk_samples) has no soft-decision decoding; receive shorter recordings")
@@ -467,7 +483,10 @@ class receiver(transmitter):
         self.no_packets = int(starts.numel())
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
-        # 2. demodulate
+        # 2. demodulate (under impulse_blanking: a copy of the samples with the clicks inside the packets' bodies blanked)
+        blanked = {}
+        if blanking:
+            x, blanked["last_blanked"], blanked["last_sample_level"], _ = eng.blank_impulses(x, starts, *blanking)
         o = chain.demodulate(eng, x, starts, rate, fused, graph_output)
         # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
         need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
@@ -480,13 +499,14 @@ class receiver(transmitter):
             bits_t = self._decode_packed(eng, o["bits"])
         # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
         # packet that runs past the recording: the reference's get_symbols fails on it)
-        got = fetch({**need, **snr, "ragged": o["status"]})
+        got = fetch({**need, **snr, **blanked, "ragged": o["status"]})
         if got["ragged"][0] != 0:                               # (before anything is printed: get_symbols fails first in the reference)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
         bits = bits_t.cpu().numpy().astype(np.int64) if rate is not None else bits_t.numpy()
         self._last_slope = got["slope"]
         self.last_phase_track = self.last_phase_measured = None
+        self.last_blanked, self.last_sample_level = got.get("last_blanked"), got.get("last_sample_level")
         for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only;
             setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
         if rate is not None:

@@ -16,6 +16,7 @@
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
 //                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
+//   gf3rx_blank.hip          blank_stats_kernel, blank_level_kernel, blank_write_kernel + gf3_blank_impulses (impulse blanking of the samples)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters

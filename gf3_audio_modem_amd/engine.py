@@ -528,6 +528,39 @@ class Engine:
         self._check(self.lib.gf3_track_phase(self._h, _ptr(eq), F, _ptr(out), _ptr(phase), _ptr(measured), self._stream()))
         return (out, phase, measured) if want_track else out
 
+    @staticmethod
+    def check_blanking(threshold, guard):
+        """ValueError for a blanking threshold that is not a finite number > 0 or a guard that is not an integer in [0, 64]."""
+        try:
+            ok = math.isfinite(float(threshold)) and float(threshold) > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"blanking threshold must be a finite number > 0, not {threshold!r}")
+        if isinstance(guard, bool) or not isinstance(guard, (int, np.integer)) or not 0 <= int(guard) <= 64:
+            raise ValueError(f"blanking guard must be an integer in [0, 64], not {guard!r}")
+        return float(threshold), int(guard)
+
+    def blank_impulses(self, x, frame_offsets, threshold=4.5, guard=8):
+        """Impulse blanking of the samples ahead of the demodulator (gf3_blank_impulses).  Per packet, the symbol at the
+        lower quartile of the per-symbol energies of its body (2P + D symbols from frame_offsets[f] on) gives a baseline mu
+        and a level sigma; a sample of the body is flagged if it is not finite or |v - mu| > threshold sigma, and every
+        sample within `guard` samples of a flagged one of the same body is replaced by mu.  The chirp and the gaps are
+        neither read nor written; a packet that runs past the stream is left alone (counts -1).
+        -> (out: a copy of x with the blanked samples replaced, counts int32 [F, M] blanked samples per symbol, level
+        float64 [F, 2] = (mu, sigma), energy float64 [F, M]).  Fixed summation order: two calls give identical bytes."""
+        threshold, guard = self.check_blanking(threshold, guard)
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F, M = off.numel(), self.cfg.M
+        out = x.clone()
+        counts = self._new((F, M), torch.int32)
+        level = self._new((F, 2), torch.float64)
+        energy = self._new((F, M), torch.float64)
+        self._check(self.lib.gf3_blank_impulses(self._h, _ptr(x), x.numel(), _ptr(off), F, threshold, guard, _ptr(out),
+                                                _ptr(energy), _ptr(level), _ptr(counts), self._stream()))
+        return out, counts, level, energy
+
     def interleave(self, x, inverse=False):
         """The packet interleaver on whole packets of nbp = D*C*mu elements (gf3_interleave): x is uint8 or float32 with a
         multiple of nbp elements; coded element i of a packet moves to position (i s) mod nbp, `inverse` moves it back.

@@ -481,6 +481,41 @@ int gf3_track_phase(gf3_ctx *ctx, const void *d_eq_c128, int64_t F, void *d_out_
                     uint8_t *d_measured_or_null, void *stream);
 
 /*
+ * Impulse blanking in the sample domain, between sync and demodulation (not in the reference).  Opt-in.  A click of a few
+ * milliseconds otherwise costs the whole OFDM symbol it falls into; here the few samples that stand far above the packet's
+ * own level are replaced by the baseline, and the symbol survives with a little less energy.
+ *   The body of packet f is its M = 2P + D symbols of S = N + CP samples, [s_f, s_f + M S), s_f = d_frame_offsets[f] (the
+ *   first pilot's cyclic prefix: what gf3_demod_frames takes).  Sample values are the stored ones widened to fp64 (u8 is
+ *   0 .. 255 with its baseline near 128).
+ *     per symbol m, over its n finite samples:  mean = sum v / n,  energy[f, m] = max(sum v^2 / n - mean^2, 0);
+ *       n = 0: energy = +Inf, mean = 0;
+ *     level: the symbol of 0-based rank (M - 1) / 4 among the packet's energies in ascending order (ties to the lower
+ *       index) gives sigma_f = sqrt(its energy) and the baseline mu_f = its mean (0 if that is not finite);
+ *       level[f] = (mu_f, sigma_f), T_f = kappa sigma_f;
+ *     a sample of the body is flagged if it is not finite or |v - mu_f| > T_f (fp64, strict: T_f = 0 flags every sample
+ *       that differs from mu_f, T_f = Inf only the non-finite ones);
+ *     it is blanked if a flagged sample of the SAME body lies within `guard` samples of it (across symbol boundaries,
+ *       never beyond the body: the chirp and the gaps are neither read nor written);
+ *     a blanked sample of d_out becomes mu_f in the storage type (u8, i16: rint, half to even, clamped; f32: a cast);
+ *     counts[f, m] = blanked samples of symbol m.
+ *   A packet whose body is not inside [0, n_in) writes no sample: counts[f, :] = -1, energy[f, :] = 0, level[f] = (0, 0);
+ *   the demodulator flags it as before.  Bodies are expected not to overlap; if they do, which packet's value lands in the
+ *   shared samples is unspecified, and nothing outside the bodies is touched in any case.
+ *   It cannot see a click that stays under kappa sigma, does not treat clicks on the chirp, and its level is wrong once
+ *   more than about three quarters of a packet's symbols are hit or a quarter have faded.  On clean Gaussian-like samples
+ *   kappa = 4.5 still blanks a few samples per packet.
+ *   d_out is a second buffer of n_in samples that the caller has filled with a copy of d_in: the kernels read d_in only
+ *   and write blanked samples of d_out only (a blanked neighbour cannot change a flag; two runs give identical bytes: every
+ *   sum is formed in a fixed order, no floating-point atomics).  d_out == d_in, a null pointer, F < 0, kappa not finite or
+ *   <= 0 and guard outside [0, 64] are GF3_EINVAL (the text names gf3_blank_impulses); F == 0 is a no-op.  The three
+ *   report arrays d_energy_f64 [F, M], d_level_f64 [F, 2], d_counts_i32 [F, M] are required: they are the call's
+ *   workspace too.  No allocation, no host synchronisation; asynchronous on `stream`.
+ */
+int gf3_blank_impulses(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                       double kappa, int32_t guard, void *d_out, double *d_energy_f64, double *d_level_f64,
+                       int32_t *d_counts_i32, void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64, 128
  * or 256; the shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, Z) for the
  * circulant whose row z has its one in column (z + s) mod Z.  Block columns 0 .. nb-mb-1 carry the message (systematic

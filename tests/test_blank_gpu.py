@@ -1,0 +1,513 @@
+"""Impulse blanking on the GPU: gf3_blank_impulses against the NumPy restatement (tests/blank_ref.py) at the smallest sizes
+at which the kernels can go wrong, its refusals, and `impulse_blanking` end to end through the façade on a packet under
+frequent clicks.
+
+What is compared and why it may be.  `out` must be byte-equal and `counts` equal, under preconditions that are asserted on
+the restatement before the GPU is looked at:
+  (a) no |v - mu| of a finite sample lies within 1e-9 T of T (a flag cannot depend on the last bits of mu or T);
+  (b) integer storage: mu is at least 1e-9 from a half-integer (the rounding of the replacement cannot either);
+  (c) the energy at the chosen rank is further than twice the tolerance below from its neighbours in the sorted order, or
+      the neighbour's symbol holds the very same samples (the two sides then tie exactly and break the tie alike);
+  (d) floating-point storage, where `out` carries mu itself: every sample is a multiple of 2^-10 below 64 in magnitude, so
+      that both sums of a symbol (S terms under 2^32 units of 2^-20 each: exact while S 2^32 < 2^53, which is asserted) are
+      exact in any order and mu has the same bits on both sides; where the samples are arbitrary doubles instead (the façade test), `out` is not compared.
+Tolerance of the report arrays.  Both sums of a symbol have at most S terms in fp64; summed in any order each carries a
+relative error of at most (S - 1) 2^-53 of the sum of its terms' magnitudes, in the kernel and in NumPy alike.  With
+q = sum v^2 / n:  |d(sum v^2 / n)| <= S 2^-52 q between the two sides;  |mean| <= sqrt(q) and |d mean| <= S 2^-52 sqrt(q), so
+|d mean^2| <= 2 S 2^-52 q (1 + small);  the subtraction and a fused multiply-add add one rounding of a number <= q.  Together
+|d energy| <= 4 S 2^-52 q = tol_e.  mu: |d mu| <= S 2^-52 sqrt(q) <= tol_e / sqrt(q).  sigma = sqrt(energy):
+|d sigma| = |d energy| / (sigma + sigma') <= tol_e / sigma, and <= sqrt(tol_e) in any case."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import gf3_oracle as orc
+from tests import blank_ref as BR
+from tests import impulse_ref as IR
+from tests import ldpc_ref as R
+from tests.util import load, modeA2_params, params_of
+
+pytestmark = pytest.mark.gpu
+TORCH_OF = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32, np.dtype("int16"): torch.int16,
+            np.dtype("uint8"): torch.uint8}
+ENGINES = {}
+
+
+def engine_of(N, CP, P, D, dtype=np.float64):
+    from gf3_audio_modem_amd import Engine, RxConfig
+    key = (N, CP, P, D, np.dtype(dtype))
+    if key not in ENGINES:
+        pts, bits = orc.qpsk_table()
+        ENGINES[key] = Engine(RxConfig(N=N, CP=CP, P=P, D=D, data_bins=np.arange(10, 200), const_points=pts, const_bits=bits,
+                                       known_bits=np.zeros((N // 2 - 1) * 2, np.uint8), in_dtype=TORCH_OF[np.dtype(dtype)],
+                                       fit_lo=10, fit_hi=100))
+    return ENGINES[key]
+
+
+def tol_energy(S, meansq):
+    return 4.0 * S * 2.0 ** -52 * meansq
+
+
+def preconditions(case, x, starts, M, S, ref, exact):
+    """(a) - (d) of the module's docstring, on the restatement."""
+    _, counts, level, energy, det = ref
+    assert det["margin"] > 1e-9, f"{case}: a sample within 1e-9 T of the threshold"
+    if x.dtype.kind in "iu":
+        assert det["half"] > 1e-9, f"{case}: a baseline within 1e-9 of a half-integer"
+    elif exact:
+        fin = x[np.isfinite(x)].astype(np.float64)
+        assert np.array_equal(fin * 1024, np.rint(fin * 1024)) and np.abs(fin).max(initial=0) < 64 and S * 2.0 ** 32 < 2.0 ** 53, f"{case}: sums not exact"
+    for f, s in enumerate(np.asarray(starts)):
+        if counts[f, 0] < 0:
+            continue
+        order = np.argsort(energy[f], kind="stable")
+        r = BR.rank_of(M)
+        body = x[s: s + M * S].reshape(M, S)
+        for nb in (r - 1, r + 1):
+            if 0 <= nb < M:
+                a, b = order[r], order[nb]
+                with np.errstate(invalid="ignore"):
+                    gap = abs(energy[f, a] - energy[f, b])
+                same = np.array_equal(body[a], body[b], equal_nan=x.dtype.kind == "f")
+                both_inf = np.isinf(energy[f, a]) and np.isinf(energy[f, b])
+                assert same or both_inf or gap > 2 * tol_energy(S, max(det["meansq"][f, a], det["meansq"][f, b])), \
+                    f"{case}: packet {f}: the ranked energy has a near tie"
+
+
+def compare(case, eng, x, starts, kappa=4.5, guard=8, exact=True):
+    """Preconditions on the restatement, then Engine.blank_impulses == restatement: `out` bytes (exact: see (d)), counts,
+    energy and level to the derived tolerances.  -> (out, counts, level, energy) of the GPU as NumPy arrays"""
+    M, S = eng.cfg.M, eng.cfg.S
+    ref = BR.blank(x, starts, M, S, kappa, guard, details=True)
+    preconditions(case, x, starts, M, S, ref, exact)
+    r_out, r_counts, r_level, r_energy, det = ref
+    xt = torch.from_numpy(x).cuda()
+    out, counts, level, energy = eng.blank_impulses(xt, starts, kappa, guard)
+    F = len(starts)
+    assert out.dtype == xt.dtype and out.shape == xt.shape and out.data_ptr() != xt.data_ptr()
+    assert counts.dtype == torch.int32 and tuple(counts.shape) == (F, M)
+    assert level.dtype == torch.float64 and tuple(level.shape) == (F, 2)
+    assert energy.dtype == torch.float64 and tuple(energy.shape) == (F, M)
+    assert np.array_equal(xt.cpu().numpy().view(np.uint8), x.view(np.uint8))          # the input is not written
+    out, counts, level, energy = out.cpu().numpy(), counts.cpu().numpy(), level.cpu().numpy(), energy.cpu().numpy()
+    tol_e = tol_energy(S, det["meansq"])
+    inf = np.isinf(r_energy)
+    assert np.array_equal(np.isinf(energy), inf) and not np.isnan(energy).any()
+    e_err = np.abs(energy[~inf] - r_energy[~inf])
+    worst = float((e_err / np.maximum(tol_e[~inf], 1e-300)).max(initial=0.0))
+    print(f"{case}: S {S} M {M} F {F} guard {guard}: blanked {int(np.maximum(r_counts, 0).sum())}, "
+          f"largest energy error / tolerance {worst:.3e}; level of packet 0 {level[:1].tolist()}")
+    assert (e_err <= tol_e[~inf]).all()
+    for f in range(F):
+        if r_counts[f, 0] < 0:
+            assert not level[f].any()
+            continue
+        m0 = BR.pick(r_energy[f])
+        q, t = det["meansq"][f, m0], tol_e[f, m0]
+        if np.isinf(r_level[f, 1]):
+            assert level[f].tolist() == r_level[f].tolist()
+            continue
+        assert abs(level[f, 0] - r_level[f, 0]) <= (t / np.sqrt(q) if q > 0 else 0.0)
+        assert abs(level[f, 1] - r_level[f, 1]) <= (min(t / r_level[f, 1], np.sqrt(t)) if r_level[f, 1] > 0 else np.sqrt(t))
+    assert np.array_equal(counts, r_counts)
+    if exact:
+        assert np.array_equal(out.view(np.uint8), r_out.view(np.uint8))
+    return out, counts, level, energy
+
+
+def synth(dtype, S, M, F, seed, lead=5, gap=7):
+    """F packets in one stream, a different baseline and level in every packet, the loud one first.  A symbol's samples are
+    baseline + amplitude x uniform(-1, 1), the amplitude 1 .. 1.5 x the packet's, shuffled over the symbols: sigma of the
+    ranked symbol is at least level / sqrt(3), so T = 4.5 sigma >= 2.6 level and no sample is flagged by itself.  Everything
+    outside the bodies is LOUD (far above every T).  Floats sit on the 2^-10 grid.
+    -> (x, starts, base [F], plant [F]: a deviation from the baseline that is flagged for certain)"""
+    dtype = np.dtype(dtype)
+    rng = np.random.default_rng(seed)
+    kinds = {"f": ([20.0, -3.0, 0.5], [8.0, 0.25, 1.0], [40.0, 10.0, 10.0], 63.0),
+             "i": ([-3000.0, 2000.0, 0.0], [1000.0, 40.0, 200.0], [20000.0, 9000.0, 9000.0], 32767.0),
+             "u": ([128.0, 100.0, 140.0], [20.0, 4.0, 10.0], [110.0, 90.0, 110.0], 255.0)}
+    base, lvl, plant, loud = kinds[dtype.kind]
+    n = lead + F * (M * S + gap)
+    x = np.full(n, loud)
+    starts = []
+    for f in range(F):
+        s = lead + f * (M * S + gap)
+        starts.append(s)
+        amp = lvl[f % 3] * (1.0 + 0.5 * rng.permutation(M) / M)
+        x[s: s + M * S] = (base[f % 3] + amp[:, None] * rng.uniform(-1, 1, size=(M, S))).reshape(-1)
+    x = np.rint(x) if dtype.kind in "iu" else np.rint(x * 1024) / 1024
+    return x.astype(dtype), np.array(starts), [base[f % 3] for f in range(F)], [plant[f % 3] for f in range(F)]
+
+
+def put(x, starts, base, plant, f, positions, sign=1):
+    for i in positions:
+        x[starts[f] + i] = np.asarray(base[f] + sign * plant[f]).astype(x.dtype)
+
+
+# ---- geometry, guards, edges ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("CP", [0, 37, 128])
+@pytest.mark.parametrize("guard", [0, 1, 63, 64])
+def test_guards_at_word_and_symbol_edges(CP, guard):
+    """S = 1024, 1061, 1152 (a multiple of 64, odd, a multiple of 64 but not of 256), M = 5.  One packet per planted
+    pattern, all in one call: a single flagged sample at position 0, 1, 62, 63, 64, 65 of symbol 1; at S - 1 of symbol 1, at
+    the first sample of symbol 2, and both; the body's first and last sample (everything around the bodies is above T and
+    must come back untouched); two flagged samples 2 g apart (one run) and 2 g + 2 apart (two runs) across a word edge."""
+    eng = engine_of(1024, CP, 2, 1)
+    S, M = eng.cfg.S, 5
+    a = 2 * S + 40
+    plans = [[S + k] for k in (0, 1, 62, 63, 64, 65)] + [[2 * S - 1], [2 * S], [2 * S - 1, 2 * S], [0, M * S - 1],
+                                                       [a, a + 2 * guard], [a, a + 2 * guard + 2]]
+    x, starts, base, plant = synth(np.float64, S, M, len(plans), seed=100 * CP + guard)
+    for f, positions in enumerate(plans):
+        put(x, starts, base, plant, f, positions, sign=1 if f % 2 else -1)
+    before = x.copy()
+    out, counts, _, _ = compare(f"guards_CP{CP}_g{guard}", eng, x, starts, guard=guard)
+    # what the restatement already holds, spelt out: the count lands in the right symbol, the guard stays in the body
+    g = guard
+    assert counts[0].tolist() == [min(g, S), 1 + g, 0, 0, 0] and counts[6].tolist() == [0, 1 + g, g, 0, 0]
+    assert counts[7].tolist() == [0, g, 1 + g, 0, 0] and counts[8].tolist() == [0, 1 + g, 1 + g, 0, 0]
+    assert counts[9].tolist() == [1 + g, 0, 0, 0, 1 + g]
+    assert counts[10].sum() == (4 * g + 1 if g else 1) and counts[11].sum() == (4 * g + 2 if g else 2)
+    outside = np.ones(len(x), dtype=bool)
+    for s in starts:
+        outside[s: s + M * S] = False
+    assert np.array_equal(out[outside], before[outside]) and (before[outside] == 63.0).all()
+
+
+@pytest.mark.parametrize("P,D", [(1, 1), (1, 2), (2, 1), (2, 5)])
+@pytest.mark.parametrize("F", [1, 3])
+def test_packet_shapes_and_state_across_packets(P, D, F):
+    """M = 3, 4, 5, 9: one on each side of the steps of the rank (M - 1) // 4.  A loud packet before a quiet one: a level or
+    a baseline that leaked across packets would blank the quiet packet wrongly or not at all."""
+    eng = engine_of(1024, 37, P, D)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, base, plant = synth(np.float64, S, M, F, seed=10 * M + F)
+    rng = np.random.default_rng(M + F)
+    for f in range(F):
+        put(x, starts, base, plant, f, rng.integers(0, M * S, size=5))
+        put(x, starts, base, plant, f, rng.integers(0, M * S, size=5), sign=-1)
+    _, counts, level, _ = compare(f"shape_P{P}_D{D}_F{F}", eng, x, starts)
+    assert (counts.sum(axis=1) >= 17).all() and np.allclose(level[:, 0], base, atol=1.0)
+    if F == 3:
+        assert level[0, 1] > 3 * level[1, 1]                # (with M = 3 every symbol holds a planted sample: the levels rise)
+
+
+def test_real_symbol_length():
+    """N = 4096, CP = 224: S = 4320 = 67.5 words, so every other symbol starts in the middle of a word."""
+    eng = engine_of(4096, 224, 2, 5)
+    S, M = eng.cfg.S, eng.cfg.M
+    assert (S, M) == (4320, 9)
+    x, starts, base, plant = synth(np.float64, S, M, 3, seed=4320, lead=3, gap=11)
+    for f in range(3):
+        put(x, starts, base, plant, f, [0, S - 1, S, 3 * S + 31, 3 * S + 32, 3 * S + 33, 4 * S - 9, 7 * S + 2000, M * S - 1])
+    compare("real_S", eng, x, starts)
+    compare("real_S_g64", eng, x, starts, guard=64)
+
+
+# ---- storage types --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int16, np.uint8])
+def test_storage_types(dtype):
+    eng = engine_of(1024, 37, 2, 5, dtype)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, base, plant = synth(dtype, S, M, 3, seed=S + np.dtype(dtype).itemsize)
+    for f in range(3):
+        put(x, starts, base, plant, f, [0, 63, 64, S - 1, S, 5 * S + 100, M * S - 1], sign=-1 if f == 1 else 1)
+    out, counts, level, _ = compare(f"storage_{np.dtype(dtype).name}", eng, x, starts)
+    assert np.allclose(level[:, 0], base, atol=0.02 * np.abs(plant[0])) and (counts.sum(axis=1) >= 40).all()
+    if np.dtype(dtype).kind in "iu":
+        assert all(out[starts[f]] == np.rint(level[f, 0]) for f in range(3)) and level[1, 0] != 0
+
+
+def test_u8_baseline_next_to_a_half_integer_rounds_half_to_even_away_from_the_tie():
+    """Every symbol alternates 127 - k, 128 + k (k differs per symbol), which would put the baseline on 127.5 exactly; one
+    sample per symbol is moved across: packet 0 sits at 127.5 + (2 k + 1) / S and must be replaced by 128, packet 1 at
+    127.5 - (2 k + 1) / S by 127."""
+    eng = engine_of(1024, 128, 2, 5, np.uint8)
+    S, M = eng.cfg.S, eng.cfg.M
+    x = np.full(5 + 2 * (M * S + 7), 255, dtype=np.uint8)
+    starts = np.array([5, 5 + M * S + 7])
+    for f in range(2):
+        for m, k in enumerate(np.random.default_rng(f).permutation(M) + 1):
+            sym = np.where(np.arange(S) % 2 == 0, 127 - k, 128 + k)
+            sym[2 * m + 10 + f] = (128 + k) if f == 0 else (127 - k)     # (an even index in packet 0, an odd one in packet 1)
+            x[starts[f] + m * S: starts[f] + (m + 1) * S] = sym
+        x[starts[f] + 3 * S + 700] = 255 if f == 0 else 0
+    out, counts, level, _ = compare("u8_half", eng, x, starts, guard=2)
+    assert level[0, 0] > 127.5 and level[1, 0] < 127.5 and abs(level[:, 0] - 127.5).max() < 0.02
+    assert out[starts[0] + 3 * S + 700] == 128 and out[starts[1] + 3 * S + 700] == 127 and counts[:, 3].tolist() == [5, 5]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_non_finite_samples(dtype):
+    """Packet 0: NaN, +Inf and -Inf samples at word and symbol edges are blanked and left out of the sums.  Packet 1: one
+    symbol entirely NaN (energy +Inf: it sorts last and is blanked whole).  Packet 2: seven of nine symbols entirely NaN, so
+    the ranked symbol has no finite sample either: mu = 0, T = Inf, only the non-finite samples are flagged (and set to 0),
+    although the two finite symbols are far from 0."""
+    eng = engine_of(1024, 37, 2, 5, dtype)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, base, plant = synth(dtype, S, M, 3, seed=17)
+    s0, s1, s2 = starts
+    x[s0 + np.array([0, 63, S - 1, 4 * S + 64])] = np.nan
+    x[s0 + np.array([S, 2 * S + 65, M * S - 1])] = np.inf
+    x[s0 + np.array([1, 6 * S + 500])] = -np.inf
+    x[s1 + 4 * S: s1 + 5 * S] = np.nan
+    keep = x[s2 + 2 * S: s2 + 4 * S].copy()
+    x[s2: s2 + M * S] = np.nan
+    x[s2 + 2 * S: s2 + 4 * S] = keep
+    x[s2 + 3 * S + 5] = -np.inf
+    out, counts, level, energy = compare(f"non_finite_{np.dtype(dtype).name}", eng, x, starts, guard=3)
+    assert np.isfinite(out[s0: s0 + M * S]).all() and np.isfinite(energy[0]).all()
+    assert counts[1, 4] == S and np.isinf(energy[1, 4]) and (out[s1 + 4 * S: s1 + 5 * S] == np.dtype(dtype).type(level[1, 0])).all()
+    # (guard 3: the NaN symbols on both sides reach three samples into the finite ones; -Inf at 5 blanks 2 .. 8)
+    assert level[2].tolist() == [0.0, np.inf] and counts[2].tolist() == [S, S, 3, 3 + 7, S, S, S, S, S]
+    assert out[s2 + 3 * S + 5] == 0 and np.array_equal(out[s2 + 2 * S + 3: s2 + 3 * S], keep[3:S])
+
+
+def test_silent_body():
+    """All samples equal: sigma = 0, T = 0, and the one sample that differs (by one grid step) is flagged."""
+    eng = engine_of(1024, 0, 2, 1)
+    S, M = eng.cfg.S, eng.cfg.M
+    x = np.full(3 + M * S + 3, 9.0)
+    x[:3] = x[-3:] = 60.0
+    x[3 + 2 * S - 1] = 9.0 + 2.0 ** -10
+    out, counts, level, energy = compare("silent", eng, x, [3], guard=1)
+    assert level.tolist() == [[9.0, 0.0]] and counts.tolist() == [[0, 2, 1, 0, 0]] and (out[3:-3] == 9.0).all()
+
+
+def test_ragged_packets_among_good_ones():
+    eng = engine_of(1024, 37, 1, 2)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, base, plant = synth(np.float64, S, M, 2, seed=5, lead=9, gap=9)
+    n = len(x)
+    for f in range(2):
+        put(x, starts, base, plant, f, [10, 2 * S, M * S - 1])
+    offs = np.array([-1, starts[0], n - M * S + 1, starts[1], n, -(2 ** 40), 2 ** 40])
+    out, counts, level, energy = compare("ragged", eng, x, offs)
+    assert (counts[[0, 2, 4, 5, 6]] == -1).all() and (counts[[1, 3]] >= 0).all() and not energy[[0, 2, 4, 5, 6]].any()
+    # the last body that still fits
+    compare("ragged_fit", eng, x[: starts[1] + M * S], np.array([starts[1], starts[1] + 1]))
+
+
+# ---- behaviour of the call ------------------------------------------------------------------------------------------
+def call(eng, x, off, kappa, guard, out, F=None):
+    from gf3_audio_modem_amd import _lib
+    M = eng.cfg.M
+    F = off.numel() if F is None else F
+    counts = torch.full((max(F, 1), M), 77, dtype=torch.int32, device="cuda")
+    level = torch.full((max(F, 1), 2), 77.0, dtype=torch.float64, device="cuda")
+    energy = torch.full((max(F, 1), M), 77.0, dtype=torch.float64, device="cuda")
+    rc = eng.lib.gf3_blank_impulses(eng._h, _lib.ptr(x), x.numel(), _lib.ptr(off), F, kappa, guard, _lib.ptr(out),
+                                    _lib.ptr(energy), _lib.ptr(level), _lib.ptr(counts), eng._stream())
+    return rc, counts, level, energy
+
+
+def test_two_runs_byte_for_byte_a_foreign_pattern_in_out_and_no_packets():
+    eng = engine_of(4096, 224, 2, 5, np.float32)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, base, plant = synth(np.float32, S, M, 3, seed=99)
+    rng = np.random.default_rng(99)
+    for f in range(3):
+        put(x, starts, base, plant, f, rng.integers(0, M * S, size=40))
+    ref_out, ref_counts, _, _ = BR.blank(x, starts, M, S, 4.5, 8)
+    xt, off = torch.from_numpy(x).cuda(), torch.from_numpy(starts).cuda()
+    runs = [eng.blank_impulses(xt, off) for _ in range(2)]
+    for a, b in zip(*runs):
+        assert a is not b and np.array_equal(a.cpu().numpy().view(np.uint8), b.cpu().numpy().view(np.uint8))
+    assert np.array_equal(runs[0][0].cpu().numpy().view(np.uint8), ref_out.view(np.uint8))
+    # `out` filled with something else than `in`: that pattern comes back everywhere but at the blanked samples
+    pattern = torch.full_like(xt, -55.0)
+    rc, counts, level, _ = call(eng, xt, off, 4.5, 8, pattern)
+    assert rc == 0 and np.array_equal(counts.cpu().numpy(), ref_counts)
+    got = pattern.cpu().numpy()
+    changed = got != -55.0
+    assert np.array_equal(changed, ref_out != x) and np.array_equal(got[changed], ref_out[changed])
+    # F = 0: nothing is touched, with or without arrays
+    before = pattern.clone()
+    rc, counts, level, energy = call(eng, xt, off, 4.5, 8, pattern, F=0)
+    assert rc == 0 and torch.equal(pattern, before) and (counts == 77).all() and (level == 77).all() and (energy == 77).all()
+    o0, c0, l0, e0 = eng.blank_impulses(xt, torch.empty(0, dtype=torch.int64))
+    assert torch.equal(o0, xt) and tuple(c0.shape) == (0, M) and tuple(l0.shape) == (0, 2) and tuple(e0.shape) == (0, M)
+
+
+def test_refusals():
+    from gf3_audio_modem_amd import _lib
+    eng = engine_of(1024, 37, 1, 2)
+    S, M = eng.cfg.S, eng.cfg.M
+    x, starts, _, _ = synth(np.float64, S, M, 1, seed=1)
+    xt, off = torch.from_numpy(x).cuda(), torch.from_numpy(starts).cuda()
+    out = xt.clone()
+    for bad in (0.0, -4.5, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="threshold"):
+            eng.blank_impulses(xt, off, threshold=bad)
+    for bad in (-1, 65, 1.5):
+        with pytest.raises(ValueError, match="guard"):
+            eng.blank_impulses(xt, off, guard=bad)
+    lib, p = eng.lib, _lib.ptr
+    c, l, e = (torch.zeros((1, M), dtype=torch.int32, device="cuda"), torch.zeros((1, 2), dtype=torch.float64, device="cuda"),
+               torch.zeros((1, M), dtype=torch.float64, device="cuda"))
+    good = [eng._h, p(xt), xt.numel(), p(off), 1, 4.5, 8, p(out), p(e), p(l), p(c), None]
+    nulls = [(at, None) for at in (0, 1, 3, 7, 8, 9, 10)]
+    for at, value in nulls + [(4, -1), (5, 0.0), (5, -1.0), (5, float("nan")), (5, float("inf")), (6, -1), (6, 65), (7, p(xt))]:
+        args = list(good)
+        args[at] = value
+        assert lib.gf3_blank_impulses(*args) == _lib.GF3_EINVAL, (at, value)
+        assert b"gf3_blank_impulses" in lib.gf3_last_error(None)
+    args = list(good)
+    args[4], args[7] = 0, p(xt)                                    # refused even when there is nothing to do
+    assert lib.gf3_blank_impulses(*args) == _lib.GF3_EINVAL
+    torch.cuda.synchronize()
+    assert torch.equal(out, xt) and not c.any() and not l.any() and not e.any()        # no refusal wrote anything
+    assert lib.gf3_blank_impulses(*good) == 0
+    torch.cuda.synchronize()
+    assert (c >= 0).all() and l[0, 1] > 0
+
+
+@pytest.mark.parametrize("name", ["g2_n4096_qpsk", "g8_n4096_qpsk_gr5_drift"])
+def test_engine_samples_of_fixture_streams_with_planted_bursts(name):
+    """The sync's own, unaligned offsets.  The stream is put on the 2^-10 grid at 64 x its scale (precondition (d)) after a
+    40-sample burst at 20 x its rms has been planted across a symbol boundary and inside a pilot."""
+    from tests.util import engine_for
+    g = load(name)
+    p = params_of(g)
+    eng = engine_for(p)
+    r = g["r"].astype(np.float64)
+    starts = (eng.sync_stream(torch.from_numpy(r).cuda()) + 2)[:-1].cpu().numpy()
+    assert len(starts) >= 1 and (starts % 64 != 0).any()
+    rng = np.random.default_rng(len(name))
+    rms = np.sqrt(np.mean(r ** 2))
+    for s in starts:
+        for at in (s + 2 * p.S - 20, s + 100, s + (p.M - 1) * p.S + 1234):
+            r[at: at + 40] += rng.normal(0, 20 * rms, 40)
+    r = np.rint(r * (32.0 / np.abs(r).max()) * 1024) / 1024
+    out, counts, level, _ = compare(name, eng, r, starts)
+    assert (counts[:, [0, 1, 2, p.M - 1]] >= 20).all() and counts.sum() < len(starts) * 4 * 80
+
+
+# ---- end to end through the façade ----------------------------------------------------------------------------------
+def restated(noisy, start, cw, p, sh):
+    """The oracle's demodulation, the restated carrier x symbol weights, de-interleaver and decoder -> failed codewords"""
+    eq = orc.demod_frames(noisy, np.array([start]), p)["eq"]
+    v_c, v_s = IR.noise_estimate2(eq, p.const_points, p.D)
+    llr = IR.deinterleave(IR.soft_demap_nw2(eq, v_c, v_s, p.const_points, p.const_bits), p.D, p.C, 2)
+    bits, _, it = R.decode(sh, llr[: cw.size].reshape(cw.shape), 50)
+    return int(np.sum((bits != cw[:, : bits.shape[1]]).any(axis=1) | (it < 0)))
+
+
+def test_facade_impulse_blanking_decodes_a_packet_under_frequent_clicks():
+    """Mode A2, "QCLDPC-1/2", interleave, llr_weighting "noise2d", 150 000 payload bits (196 codewords in one packet) from the
+    façade's own transmit(), white noise 15 dB below the body, a 200-sample burst of white noise at 20 x the body's rms at a
+    random place in 60 % of the data symbols and in start pilots 3 and 11.
+
+    Restated on this test's own samples before the GPU is looked at, at x0.8 / x1.2 / x1 of the burst amplitude: the plain
+    stream fails codewords at each amplitude, the NumPy-blanked stream fails none.  Figures of the last run are printed.
+
+    The noise and the bursts come from seed 12.  What the clean symbols hold is a property of the samples and the definition,
+    not of the kernel (the kernel's counts must EQUAL the restatement's), so it is asserted on the restatement first, like
+    the other preconditions of this file.  It depends on how many samples of the noisy body pass 4.5 sigma by themselves, 17
+    blanked samples each: restated on this stream with noise seeds 11 .. 23 the clean symbols hold 51, 36, 17, 34, 51, 34, 17,
+    51, 0, 22, 0, 34, 34 samples, against the bound of 1 % of a symbol = 43.  Seed 11 has three such samples (51: it misses
+    the bound whatever computes the counts); seed 12, the next one, is used.  On an MI355X: hit symbols hold 212..233 blanked
+    samples, the clean ones 36, the level reads 1.0141 x the clean body's rms (the noise adds 1.6 %)."""
+    from gf3_audio_modem_amd.ldpc import shift_table
+    from gf3_audio_modem_amd.OFDM import receiver
+    rng = np.random.default_rng(7)
+    payload = rng.integers(0, 2, size=150_000)
+    tx = receiver("A2", encoding="QCLDPC-1/2")
+    np.random.seed(7)
+    coded = np.asarray(tx.encode(payload))                  # (coded order: the interleaver is still off)
+    tx.interleave = True
+    np.random.seed(7)
+    sig = np.concatenate([np.zeros(2000), tx.transmit(payload), np.zeros(2000)])
+    p = modeA2_params(np.asarray(tx.known_sequence[: tx.K * tx.mu], dtype=np.uint8))
+    sh = shift_table("1/2")
+    n_cw = -(-len(payload) // 768)
+    cw = coded[: n_cw * 1536].astype(np.uint8).reshape(n_cw, 1536)
+    start = 2000 + tx.chirp_length
+    body = sig[start: start + p.M * p.S]
+    rms = float(np.sqrt(np.mean(body ** 2)))
+    nrng = np.random.default_rng(12)
+    noise = nrng.normal(0.0, rms / 10 ** 0.75, sig.shape)
+    clicks, hit = BR.click_scenario(sig, start, p.M, p.S, p.P, p.D, 0.6, 20.0, nrng)
+    assert 3 in hit and 11 in hit and len(hit) == 110
+    for scale in (0.8, 1.2, 1.0):                           # (ends on the stream the GPU receives)
+        noisy = sig + noise + scale * clicks
+        ref = BR.blank(noisy, [start], p.M, p.S, 4.5, 8, details=True)
+        plain, blanked = restated(noisy, start, cw, p, sh), restated(ref[0], start, cw, p, sh)
+        print(f"bursts x{20 * scale:.0f}: restated failed codewords of {n_cw} without blanking {plain}, with {blanked}")
+        assert plain > 0 and blanked == 0
+    assert ref[4]["margin"] > 1e-9                          # precondition (a) for the counts
+    assert np.delete(ref[1][0], hit).sum() < 0.01 * p.S     # the stream itself meets the bound on the clean symbols (docstring)
+
+    rx = receiver("A2", encoding="QCLDPC-1/2")
+    rx.interleave, rx.llr_weighting = True, "noise2d"
+    assert rx.impulse_blanking is False
+    out, _, _ = rx.receive(noisy)
+    assert not np.array_equal(out[: len(payload)], payload)
+    assert rx.last_blanked is None and rx.last_sample_level is None
+    rx.impulse_blanking = True
+    out, Hs0, _ = rx.receive(noisy)
+    assert out.dtype == np.int64 and Hs0.shape == (2047,)
+    assert np.array_equal(out[: len(payload)], payload)
+    counts, level = rx.last_blanked, rx.last_sample_level
+    assert counts.dtype == np.int32 and counts.shape == (1, 220) and level.dtype == np.float64 and level.shape == (1, 2)
+    assert np.array_equal(counts, ref[1])
+    clean = np.delete(counts[0], hit)
+    print(f"hit symbols hold {counts[0, hit].min()}..{counts[0, hit].max()} blanked samples, the clean ones {clean.sum()} in all; "
+          f"level {level[0, 1] / rms:.4f} x the body's rms, baseline {level[0, 0]:.3e}")
+    assert counts[0, hit].min() >= 200 and counts[0, hit].max() <= 200 + 2 * 8 + 40
+    assert clean.sum() < 0.01 * p.S
+    assert abs(level[0, 1] / rms - 1) < 0.05
+    # it sits below the other opt-in stages: the fused sample-to-LLR path takes the blanked samples too (what it decodes
+    # with the |H^|^2 weights, which do not mark the hit symbols, is not the subject)
+    rx.fused_llr, rx.llr_weighting = True, "csi"
+    rx.receive(noisy)
+    assert rx.last_blanked is not None and np.array_equal(rx.last_blanked, counts)
+    rx.fused_llr, rx.llr_weighting = False, "noise2d"
+    # off again: the attributes are cleared
+    rx.impulse_blanking = False
+    rx.receive(sig + noise)
+    assert rx.last_blanked is None and rx.last_sample_level is None
+    # the refusals
+    rx.impulse_blanking, rx.blanking_guard = True, 65
+    with pytest.raises(ValueError, match="guard"):
+        rx.receive(noisy)
+    rx.blanking_guard, rx.blanking_threshold = 8, float("nan")
+    with pytest.raises(ValueError, match="threshold"):
+        rx.receive(noisy)
+    rx.blanking_threshold, rx.host_chunk_samples = 4.5, 1 << 22
+    with pytest.raises(NotImplementedError, match="impulse_blanking.*piece-wise host path"):
+        rx.receive(noisy)
+
+
+def test_facade_defaults_unchanged_and_hard_decisions_gain():
+    """"XOR": with the feature off, receive() of a clean stream returns the bits of the direct engine calls; on a clicked
+    stream the bit error count with blanking is lower than without."""
+    from gf3_audio_modem_amd.OFDM import receiver
+    rng = np.random.default_rng(8)
+    rx = receiver("A2", encoding="XOR")
+    payload = rng.integers(0, 2, size=rx.packet_length * rx.data_bits_per_symbol)
+    np.random.seed(8)
+    sig = np.concatenate([np.zeros(1500), rx.transmit(payload), np.zeros(1500)])
+    out, _, _ = rx.receive(sig)
+    assert rx.last_blanked is None and rx.last_sample_level is None and np.array_equal(out, payload)
+    eng = rx._engine(np.dtype("float64"))
+    x = eng._samples(sig)
+    starts = (eng.sync_stream(x) + 2)[:-1]
+    mask = np.asarray(rx.known_sequence[: rx.data_bits_per_symbol], dtype=np.uint8)
+    direct = eng.unpack_decode(eng.demod_frames(x, starts)["bits"], mask)
+    torch.cuda.synchronize()
+    assert np.array_equal(out, direct.numpy())
+    start = 1500 + rx.chirp_length
+    M, S = 220, 4320
+    rms = float(np.sqrt(np.mean(sig[start: start + M * S] ** 2)))
+    nrng = np.random.default_rng(12)
+    noisy = sig + nrng.normal(0.0, rms / 10 ** 0.75, sig.shape)
+    noisy = noisy + BR.click_scenario(sig, start, M, S, 20, 180, 0.6, 20.0, nrng)[0]
+    errors = []
+    for on in (False, True):
+        rx.impulse_blanking = on
+        out, _, _ = rx.receive(noisy)
+        errors.append(int(np.sum(out != payload)))
+        assert (rx.last_blanked is not None) == on
+    print(f"XOR, 60 % of the symbols clicked: bit errors of {len(payload)} without blanking {errors[0]}, with {errors[1]}")
+    assert errors[1] < errors[0]
