@@ -24,28 +24,94 @@ static DemodArgs demod_args(const gf3_ctx* c) {
     return a;
 }
 
-extern "C" int gf3_demod_frames_ex(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
-                                   uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
-                                   int32_t* d_status, void* d_work, int32_t mode, void* stream) {
+// What the calling thread's last demodulation did (gf3_demod_frames_last): kept per host thread like every other diagnostic.
+static thread_local struct { const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0; } g_demod_last;
+
+// Whether precision -1 (auto: plain gf3_demod_frames, gf3_demod_frames_ex) takes the screened path where it applies.
+// Decided by the same-box A/B of DESIGN 3.5 / 4; precision 1 asks for the screen explicitly either way.
+#define GF3_DEMOD_AUTO_SCREEN 1
+
+extern "C" int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx* c, int64_t F) {
+    if (!c || F < 0) return 0;
+    return (int64_t)((size_t)F * sizeof(int) + 64);           // [count | pad | listed packet numbers]
+}
+
+// precision 0: all fp64 (the reference of the screened path's tests).  1: the fp32 screen of the data symbols under a
+// proven bound (gf3rx_dscreen.h), then the fp64 kernel on the packets it listed, whenever that applies -- the reference
+// QPSK table, bits only (no eq, no Hest), the one-launch form, f32 / i16 / u8 storage, F <= INT_MAX and a list workspace
+// to be had (the caller's `d_list` of gf3_demod_screen_workspace_bytes(F), else the context's per stream and host thread;
+// none while the stream is being captured and nothing exists yet) -- and all fp64 otherwise.  -1 (auto): as 1 when
+// GF3_DEMOD_AUTO_SCREEN, else as 0.  The outputs are the same every way.
+static int demod_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                             uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
+                             int32_t* d_status, void* d_work, int32_t mode, int32_t precision, void* d_list,
+                             cf* dbg_ep, float* dbg_E, int32_t* dbg_cls, bool screen_only, void* stream) {
     DeviceGuard dg(c);
     if (c && F == 0) return GF3_OK;
-    if (!c || !d_in || !d_off || !d_bits || F < 0 || mode < 0 || mode > 2) return fail(c, GF3_EINVAL, "gf3_demod_frames: bad argument");
+    if (!c || !d_in || !d_off || !d_bits || F < 0 || mode < 0 || mode > 2 || precision < -1 || precision > 1)
+        return fail(c, GF3_EINVAL, "gf3_demod_frames: bad argument");
+    hipStream_t st = (hipStream_t)stream;
     DemodArgs a = demod_args(c);
     a.in = d_in; a.n_in = n_in; a.off = d_off; a.bits = d_bits; a.stamps = c->stamps;
     a.eq = (cplx*)d_eq; a.Hs = (cplx*)d_Hs; a.He = (cplx*)d_He; a.slope = d_slope; a.Hest = (cplx*)d_Hest; a.status = d_status;
+    g_demod_last.ctx = c; g_demod_last.stream = stream; g_demod_last.path = 2; g_demod_last.cap = 0;
     // long packets, few at a time: pilot sums, estimate and data symbols as three launches (gf3rx_demod_split.hip)
-    if (d_work && demod_wants_split(c, F, mode)) return demod_split(c, a, F, d_work, (hipStream_t)stream);
+    if (d_work && demod_wants_split(c, F, mode)) {
+        if (screen_only) return fail(c, GF3_EINVAL, "gf3_debug_demod_screen: the two-phase form is not screened");
+        return demod_split(c, a, F, d_work, st);
+    }
+    const bool want_screen = precision == 1 || (precision == -1 && GF3_DEMOD_AUTO_SCREEN);
+    void* list_ws = nullptr;
+    if (want_screen && demod_screen_applies(c) && !d_eq && !d_Hest && F <= 0x7fffffff)
+        list_ws = d_list ? d_list : ctx_workspace(c, st, gf3_ctx::WS_DEMOD, gf3_demod_screen_workspace_bytes(c, F));
+    if (screen_only && !list_ws) return fail(c, GF3_EINVAL, "gf3_debug_demod_screen: the screen does not apply to this context");
+    if (list_ws) {
+        a.tw32 = c->d_tw32; a.dwork = (int*)list_ws; a.dbg_ep = dbg_ep; a.dbg_E = dbg_E;
+        g_demod_last.path = 0; g_demod_last.cap = (int32_t)F;
+        HIPCHK(c, hipMemsetAsync(a.dwork, 0, 64, st));
+        HIPCHK(c, launch_demod_screen(c, a, F, st));
+        if (dbg_cls) HIPCHK(c, launch_demod_verdicts(a.dwork, dbg_cls, F, st));
+        if (screen_only) return GF3_OK;
+        HIPCHK(c, launch_demod_listed(c, a, F, st));
+        return GF3_OK;
+    }
     hipError_t e = hipSuccess;
-    if (d_eq || d_Hest) e = launch_demod_full(c, a, F, (hipStream_t)stream);
-    else if (c->qpsk_q > 0.0) e = launch_demod_qpsk(c, a, F, (hipStream_t)stream);
-    else e = launch_demod_scan(c, a, F, (hipStream_t)stream);
+    if (d_eq || d_Hest) e = launch_demod_full(c, a, F, st);
+    else if (c->qpsk_q > 0.0) e = launch_demod_qpsk(c, a, F, st);
+    else e = launch_demod_scan(c, a, F, st);
     HIPCHK(c, e);
     return GF3_OK;
+}
+extern "C" int gf3_demod_frames_px(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                                   uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
+                                   int32_t* d_status, void* d_work, int32_t mode, int32_t precision, void* stream) {
+    return demod_frames_impl(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, d_work, mode, precision,
+                             nullptr, nullptr, nullptr, nullptr, false, stream);
+}
+extern "C" int gf3_demod_frames_ex(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                                   uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
+                                   int32_t* d_status, void* d_work, int32_t mode, void* stream) {
+    return gf3_demod_frames_px(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, d_work, mode, -1, stream);
 }
 extern "C" int gf3_demod_frames(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
                                 uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
                                 int32_t* d_status, void* stream) {
-    return gf3_demod_frames_ex(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, nullptr, 1, stream);
+    return gf3_demod_frames_px(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, nullptr, 1, -1, stream);
+}
+extern "C" int gf3_demod_frames_last(const gf3_ctx* c, void* stream, int32_t* path, int32_t* listed_capacity) {
+    if (!c || !path) return fail(c, GF3_EINVAL, "gf3_demod_frames_last: null argument");
+    const bool mine = g_demod_last.ctx == c && g_demod_last.stream == stream;
+    *path = mine ? g_demod_last.path : -1;
+    if (listed_capacity) *listed_capacity = mine ? g_demod_last.cap : 0;
+    return GF3_OK;
+}
+// tests: the screening pass alone -- the fp32 rotated symbols of the data carriers [F][D][C] (data_bins order), the bound
+// per symbol [F][D], the verdict per packet (0 decided, 1 listed), the listed packets in d_list; d_bits gets the screen's rows
+extern "C" int gf3_debug_demod_screen(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                                      uint8_t* d_bits, void* d_ep32, float* d_E, int32_t* d_cls, void* d_list, void* stream) {
+    if (!d_list) return fail(c, GF3_EINVAL, "gf3_debug_demod_screen: null workspace");
+    return demod_frames_impl(c, d_in, n_in, d_off, F, d_bits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1,
+                             d_list, (cf*)d_ep32, d_E, d_cls, true, stream);
 }
 
 // Samples to weighted max-log LLRs in one launch (MODE_SOFT of demod_kernel): what gf3_demod_frames(eq, Hs, He) +

@@ -259,6 +259,12 @@ extern "C" int gf3_ctx_create(const gf3_config* cfg, gf3_ctx** out) {
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { int rc_ = fail(nullptr, GF3_EHIP, "%s: %s", #x, hipGetErrorString(e_)); gf3_ctx_destroy(c); return rc_; } } while (0)
     CK(dev_new(c->owned, &c->d_tw, tw.tw));
     CK(dev_new(c->owned, &c->d_twn, tw.twn));
+    {
+        std::vector<cf> tw32;                                           // the fp64 tables rounded once (gf3rx_dscreen.h)
+        for (const cplx& w : tw.tw) tw32.push_back(make_float2((float)w.x, (float)w.y));
+        for (const cplx& w : tw.twn) tw32.push_back(make_float2((float)w.x, (float)w.y));
+        CK(dev_new(c->owned, &c->d_tw32, tw32));
+    }
     CK(dev_new(c->owned, &c->d_known, known));
     CK(dev_new(c->owned, &c->d_pos, pos));
     CK(dev_new(c->owned, &c->d_clab, clab));
@@ -320,11 +326,33 @@ extern "C" void gf3_ctx_destroy(gf3_ctx* c) {
     if (!c) return;
     DeviceGuard dg(c);
     for (void* p : c->owned) (void)hipFree(p);
-    // the frames sync's workspaces, current and outgrown: kernels queued by earlier calls may still read them
-    if (!c->fs_work.empty() || !c->fs_retired.empty()) (void)hipDeviceSynchronize();
-    for (auto& w : c->fs_work) if (w.d) (void)hipFree(w.d);
-    for (void* p : c->fs_retired) if (p) (void)hipFree(p);
+    // the screened paths' list workspaces, current and outgrown: kernels queued by earlier calls may still read them
+    if (!c->ws_work.empty() || !c->ws_retired.empty()) (void)hipDeviceSynchronize();
+    for (auto& w : c->ws_work) for (void* p : w.d) if (p) (void)hipFree(p);
+    for (void* p : c->ws_retired) if (p) (void)hipFree(p);
     delete c;
+}
+
+#define GF3_MAX_WORKSPACES 64
+// An outgrown buffer is retired, not freed: a queued kernel may still read it.
+void* ctx_workspace(gf3_ctx* c, hipStream_t st, int slot, int64_t bytes) {
+    const std::thread::id me = std::this_thread::get_id();
+    std::lock_guard<std::mutex> lock(c->ws_mu);
+    gf3_ctx::Work* e = nullptr;
+    for (auto& w : c->ws_work) if (w.stream == st && w.thread == me) { e = &w; break; }
+    if (e && e->d[slot] && e->bytes[slot] >= bytes) return e->d[slot];
+    if (!e && c->ws_work.size() >= GF3_MAX_WORKSPACES) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (cap != hipStreamCaptureStatusNone) return nullptr;               // an allocation would break the capture
+    int64_t want = bytes;
+    if (e && want < e->bytes[slot] + e->bytes[slot] / 2) want = e->bytes[slot] + e->bytes[slot] / 2;   // (a slowly growing F: few retired buffers)
+    void* d = nullptr;
+    if (hipMalloc(&d, (size_t)want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (!e) { c->ws_work.push_back(gf3_ctx::Work{st, me}); e = &c->ws_work.back(); }
+    if (e->d[slot]) c->ws_retired.push_back(e->d[slot]);
+    e->d[slot] = d; e->bytes[slot] = want;
+    return d;
 }
 
 // diagnostic builds only: device buffer [F][8] of uint64 that receives per-phase s_memtime stamps

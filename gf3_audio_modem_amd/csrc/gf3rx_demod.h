@@ -5,6 +5,7 @@
 #pragma once
 #include "gf3rx_host.h"
 #include "gf3rx_demap.h"
+#include "gf3rx_dscreen.h"
 
 // ============================================================================
 // fused demodulation of one packet per workgroup
@@ -150,14 +151,24 @@ template <int NC, int MODE> struct DemodOcc {
 // data symbols [chunk Dc, (chunk + 1) Dc) of packet blockIdx.x / nchunk.  The discarded branches vanish: STAGE_ALL is
 // the kernel it was.
 enum { STAGE_ALL = 0, STAGE_EST = 1, STAGE_DATA = 2 };
-template <int NC, int DT, bool SPECTRA, int MODE, int STAGE = STAGE_ALL>
+// VAR: two forms of the one-launch QPSK kernel that serve the screened demodulation (gf3rx_dscreen.h, gf3rx_demod_screen.hip).
+// VAR_LISTED: packet = dwork[16 + blockIdx.x] for blockIdx.x < dwork[0], and nothing else differs -- the fp64 pass over the packets
+// the screen could not decide.  VAR_SCREEN (demod_screen_kernel): the data symbols' transforms, rotations and decisions
+// in fp32 under a bound; everything up to the first data symbol is the code below, unchanged.
+enum { VAR_PLAIN = 0, VAR_LISTED = 1, VAR_SCREEN = 2 };
+template <int NC, int DT, bool SPECTRA, int MODE, int STAGE = STAGE_ALL, int VAR = VAR_PLAIN>
 __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kernel(DemodArgs a) {
     constexpr bool FULL = (MODE == MODE_FULL);
+    constexpr bool SCREEN = (VAR == VAR_SCREEN);
+    static_assert(VAR == VAR_PLAIN || (MODE == MODE_QPSK && STAGE == STAGE_ALL && !SPECTRA), "the screen and its fp64 pass are forms of the one-launch QPSK kernel");
+    static_assert(!SCREEN || DT != DT_F64, "only storages that fp32 holds exactly are screened");
     static_assert(STAGE == STAGE_ALL || !SPECTRA, "the two-phase form takes time-domain input");
     static_assert(STAGE != STAGE_EST || DT == DT_F64, "the estimate stage reads the fp64 pilot sums");
     extern __shared__ double2 smem[];
     constexpr int T = NC / 8;
     // LDS: [scratch 32 doubles | start-up rotation tables | FFT buffer | decision bytes | (fit-range overflow)]
+    // scratch: doubles [16, 32) are block_sum's (the slope fit); VAR_SCREEN also keeps the per-wave l1 sums of the data symbols
+    // in doubles [0, 8) (as float [2][8]) and the packet's "listed" flag in double 8
     double* scratch = (double*)smem;
     cplx* rtab = (cplx*)(scratch + 32);                                   // [2][64 + NC/64 + 1]
     cplx* lds = rtab + 2 * (64 + NC / 64 + 1);                            // FFT buffer, DemodOcc::LDS_ELEMS points
@@ -167,6 +178,10 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     double2* mags = (double2*)(labs + ((a.ring * a.C + 15) & ~15));
     const int tid = threadIdx.x;
     int64_t f = blockIdx.x;
+    if constexpr (VAR == VAR_LISTED) {
+        if ((int)blockIdx.x >= a.dwork[0]) return;                        // (the grid is the list's capacity)
+        f = a.dwork[16 + blockIdx.x];
+    }
     const int K = a.K, P = a.P, D = a.D, S = a.S;
     int l_lo = 0, l_hi = D;                                               // data symbols this workgroup demodulates
     if constexpr (STAGE == STAGE_DATA) {
@@ -228,6 +243,28 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     auto load_spectra = [&](const cplx* sp) {         // SPECTRA mode: slots straight from memory
 #pragma unroll
         for (int s2 = 0; s2 < 8; ++s2) v[s2] = sp[bin_of(s2) - 1];
+    };
+    // VAR_SCREEN: nxt -> fp32 spectrum slots in v32, the same passes on float2 points in the first half of the FFT buffer.
+    // The symbol's l1 norm is summed while the samples are converted; the per-wave sums go to l1s[parity][wave] ahead of
+    // the transform's barriers and are read back after them (two parities: symbol i + 1 writes before every wave has read
+    // symbol i's; i + 2 writes only after the barriers of transform i + 1).
+    cf v32[8], z032, wb32;
+    FftTw<NC, cf> ft32;
+    float* l1s = (float*)scratch;                                         // [2][8]; scratch[8]: the packet's "listed" flag
+    int* unsafe_flag = (int*)(scratch + 8);
+    auto transform32 = [&](int i) {
+        float s1 = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            v32[r] = make_float2((float)nxt[r].v.a, (float)nxt[r].v.b);
+            s1 += fabsf(v32[r].x) + fabsf(v32[r].y);
+        }
+        if (i + 1 < Msym) fetch(i + 1);
+        s1 = scr_wave_reduce<false>(s1);
+        if ((tid & 63) == 0) l1s[(i & 1) * 8 + (tid >> 6)] = s1;
+        ft32.refresh();
+        asm volatile("" : "+v"(wb32.x), "+v"(wb32.y));
+        rfft_regs<NC, DemodOcc<NC, MODE>::PP, true>(v32, (cf*)lds, ft32, wb32, tq, z032, i & 1);
     };
     GF3_STAMP(0);
     GF3_STAMP_RT(6);
@@ -301,6 +338,11 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     constexpr double XS = SPECTRA ? 1.0 : 2.0;
     const double invP = (1.0 / (double)P) / XS;
     // (a) straight-line over the 8 slots (independent chains overlap): H = mean/known, unit phasor, magnitudes
+    // (VAR_SCREEN) the packet goes to the fp64 pass: a part the bound does not back in any data symbol -- or a non-finite
+    // end-pilot estimate: the sign mode reads He only through the fit's angles, where atan2_fast turns a NaN into 0, so
+    // such a packet could come out decidable; with this every packet that holds a non-finite sample is listed (a data
+    // symbol's makes E_l non-finite, a start pilot's makes u and with it every rotated symbol NaN)
+    bool unsafe = false;
     cplx ik[8];                                       // 1/known (L2 latency covered by the other resident workgroup)
     if constexpr (STAGE != STAGE_DATA) {
 #pragma unroll
@@ -311,6 +353,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
         if constexpr (STAGE != STAGE_DATA) {
             Hs[s] = cmul(cscale(Hs[s], invP), ik[s]);
             He[s] = cmul(cscale(He[s], invP), ik[s]);
+            if constexpr (SCREEN) unsafe = unsafe || !(fabs(He[s].x) + fabs(He[s].y) < INFINITY);
         }
         const double m2 = Hs[s].x * Hs[s].x + Hs[s].y * Hs[s].y;
         const double ia = rsq_nr(m2);                                 // 1/|Hs|
@@ -441,6 +484,11 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
             rtab[NRT + i] = cis_fast(dphi * nn);
         }
     }
+    if constexpr (SCREEN) {
+        if (tid == 0) *unsafe_flag = 0;
+        ft32.init(tid, a.tw32);
+        wb32 = a.tw32[NC + tid];
+    }
     lds_barrier();
     cplx gstep[8];
 #pragma unroll
@@ -462,11 +510,32 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     }
     for (int l = l_lo; l < l_hi; ++l) {
         if constexpr (SPECTRA) { lds_barrier(); load_spectra(a.sp_data + ((int64_t)f * D + l) * K); }
+        else if constexpr (SCREEN) transform32(2 * P + l);
         else transform(2 * P + l);
         if constexpr (MODE != MODE_SOFT) { if (l > l_lo) pack_words(l - 1, false); }
         const double fl = ((double)l + 0.5 * (double)P) / denom;          // (l + P/2)/(D+P)
         uint8_t* lab_l = labs + (l & (a.ring - 1)) * C;
-        if constexpr (MODE == MODE_QPSK) {
+        if constexpr (SCREEN) {
+            float l1 = 0.0f;
+#pragma unroll
+            for (int w = 0; w < (T + 63) / 64; ++w) l1 += l1s[((2 * P + l) & 1) * 8 + w];
+            const float El = dscr_bound<NC>(l1);
+            unsafe = unsafe || !(El < INFINITY);
+            if (a.dbg_E && tid == 0) a.dbg_E[f * D + l] = El;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const cplx g = u[s];
+                cf ep;
+                bool safe;
+                const uint32_t lab = dscr_decide(v32[s], g, El, ep, safe);
+                u[s] = cmul(g, gstep[s]);                                  // the fp64 recurrence, as below
+                if (psl[s] >= 0) {
+                    lab_l[psl[s]] = (uint8_t)lab;
+                    unsafe = unsafe || !safe;
+                    if (a.dbg_ep) a.dbg_ep[(f * D + l) * (int64_t)C + psl[s]] = ep;
+                }
+            }
+        } else if constexpr (MODE == MODE_QPSK) {
             // all eight carriers in one straight line: rotate, advance the phasors, take the sign bits; the exact
             // tie / NaN / Inf rule is one rarely taken branch for the whole group instead of one per carrier
             cplx ep[8];
@@ -585,9 +654,15 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
         }
     }
     GF3_STAMP(4);
+    if constexpr (SCREEN) { if (unsafe) *unsafe_flag = 1; }
     if constexpr (MODE != MODE_SOFT) {
         lds_barrier();
         pack_words(l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
+    }
+    if constexpr (SCREEN) {
+        if (tid == 0) {                                                    // (the row is written anyway: the fp64 pass overwrites it)
+            if (*unsafe_flag) a.dwork[16 + atomicAdd(a.dwork, 1)] = (int)f;
+        }
     }
     GF3_STAMP(5);
     GF3_STAMP_RT(7);

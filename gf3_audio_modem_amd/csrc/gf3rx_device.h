@@ -27,6 +27,23 @@ GF3_DEV cplx cmul_conj(cplx a, cplx b) { return cmk(a.x * b.x + a.y * b.y, a.y *
 GF3_DEV cplx mul_negi(cplx a) { return cmk(a.y, -a.x); }   // a * (-i)
 GF3_DEV cplx mul_posi(cplx a) { return cmk(-a.y, a.x); }   // a * (+i)
 
+// The same helpers on single-precision points (float2): the transform below is written once on the point type Cx and
+// instantiated for both (the fp32 form serves the screened QPSK demodulation, gf3rx_dscreen.h).  CxT<Cx>::R is the scalar
+// type, cx<Cx>(a, b) makes a point of either kind from constants.
+template <typename Cx> struct CxT;
+template <> struct CxT<double2> { typedef double R; };
+template <> struct CxT<float2> { typedef float R; };
+template <typename Cx> GF3_DEV Cx cx(typename CxT<Cx>::R a, typename CxT<Cx>::R b);
+template <> GF3_DEV double2 cx<double2>(double a, double b) { return make_double2(a, b); }
+template <> GF3_DEV float2 cx<float2>(float a, float b) { return make_float2(a, b); }
+GF3_DEV float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+GF3_DEV float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+GF3_DEV float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
+GF3_DEV float2 cscale(float2 a, float s) { return make_float2(a.x * s, a.y * s); }
+GF3_DEV float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+GF3_DEV float2 cmul_conj(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
+GF3_DEV float2 mul_negi(float2 a) { return make_float2(a.y, -a.x); }
+
 // complex division the way NumPy does it for complex128 (Smith's method)
 GF3_DEV cplx cdiv_np(cplx a, cplx b) {
     const double br = fabs(b.x), bi = fabs(b.y);
@@ -111,7 +128,10 @@ GF3_DEV double load_sample(const void* p, int64_t i, int dt) {
 // ---------------------------------------------------------------- butterflies
 #define GF3_SQRT1_2 0.70710678118654752440
 
-GF3_DEV void bfly8(cplx* v) {
+template <typename Cx> GF3_DEV void bfly8(Cx* v) {
+    typedef Cx cplx;
+    typedef typename CxT<Cx>::R R;
+    constexpr R S = (R)GF3_SQRT1_2;
     const cplx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]);
     const cplx a2 = cadd(v[2], v[6]), a3 = mul_negi(csub(v[2], v[6]));
     const cplx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]);
@@ -119,14 +139,14 @@ GF3_DEV void bfly8(cplx* v) {
     const cplx b0 = cadd(a0, a2), b1 = cadd(a1, a3), b2 = csub(a0, a2), b3 = csub(a1, a3);
     const cplx b4 = cadd(a4, a6), o1 = cadd(a5, a7), b6 = mul_negi(csub(a4, a6)), o3 = csub(a5, a7);
     // b5 = o1 (1-i)/sqrt2 and b7 = o3 (-1-i)/sqrt2 are never formed: the 1/sqrt2 rides on the fma of b +- b5, b +- b7
-    const double p1 = o1.x + o1.y, m1 = o1.y - o1.x;            // b5 = (p1, m1) / sqrt2
-    const double m3 = o3.y - o3.x, p3 = o3.x + o3.y;            // b7 = (m3, -p3) / sqrt2
+    const R p1 = o1.x + o1.y, m1 = o1.y - o1.x;                 // b5 = (p1, m1) / sqrt2
+    const R m3 = o3.y - o3.x, p3 = o3.x + o3.y;                 // b7 = (m3, -p3) / sqrt2
     v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-    v[1] = cmk(fma(GF3_SQRT1_2, p1, b1.x), fma(GF3_SQRT1_2, m1, b1.y));
-    v[5] = cmk(fma(-GF3_SQRT1_2, p1, b1.x), fma(-GF3_SQRT1_2, m1, b1.y));
+    v[1] = cx<Cx>(fma(S, p1, b1.x), fma(S, m1, b1.y));
+    v[5] = cx<Cx>(fma(-S, p1, b1.x), fma(-S, m1, b1.y));
     v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
-    v[3] = cmk(fma(GF3_SQRT1_2, m3, b3.x), fma(-GF3_SQRT1_2, p3, b3.y));
-    v[7] = cmk(fma(-GF3_SQRT1_2, m3, b3.x), fma(GF3_SQRT1_2, p3, b3.y));
+    v[3] = cx<Cx>(fma(S, m3, b3.x), fma(-S, p3, b3.y));
+    v[7] = cx<Cx>(fma(-S, m3, b3.x), fma(S, p3, b3.y));
 }
 
 // powers of a unit twiddle w = exp(-i t) by the three-term recurrence w^(k+1) = 2 cos(t) w^k - w^(k-1): two fma per
@@ -140,18 +160,28 @@ GF3_DEV cplx cfma(cplx a, cplx w, cplx c) {           // c + a w
     return cmk(fma(a.x, w.x, fma(-a.y, w.y, c.x)), fma(a.x, w.y, fma(a.y, w.x, c.y)));
 }
 GF3_DEV cplx twice_minus(cplx u, cplx s) { return cmk(fma(2.0, u.x, -s.x), fma(2.0, u.y, -s.y)); }   // 2u - s
-GF3_DEV void bfly4_tw(cplx* v, cplx w) {              // v[r] *= w^r, then the radix-4 butterfly
-    const double c2 = w.x + w.x;
-    const cplx w2 = cmk(fma(c2, w.x, -1.0), c2 * w.y);
+GF3_DEV float2 tw_next(float c2, float2 wk, float2 wkm1) { return make_float2(fmaf(c2, wk.x, -wkm1.x), fmaf(c2, wk.y, -wkm1.y)); }
+GF3_DEV float2 cfma(float2 a, float2 w, float2 c) {
+    return make_float2(fmaf(a.x, w.x, fmaf(-a.y, w.y, c.x)), fmaf(a.x, w.y, fmaf(a.y, w.x, c.y)));
+}
+GF3_DEV float2 twice_minus(float2 u, float2 s) { return make_float2(fmaf(2.0f, u.x, -s.x), fmaf(2.0f, u.y, -s.y)); }
+template <typename Cx> GF3_DEV void bfly4_tw(Cx* v, Cx w) {   // v[r] *= w^r, then the radix-4 butterfly
+    typedef Cx cplx;
+    typedef typename CxT<Cx>::R R;
+    const R c2 = w.x + w.x;
+    const cplx w2 = cx<Cx>(fma(c2, w.x, (R)-1.0), c2 * w.y);
     const cplx w3 = tw_next(c2, w2, w);
     const cplx s0 = cfma(v[2], w2, v[0]), s1 = twice_minus(v[0], s0);
     const cplx u1 = cmul(v[1], w);
     const cplx s2 = cfma(v[3], w3, u1), s3 = mul_negi(twice_minus(u1, s2));
     v[0] = cadd(s0, s2); v[1] = cadd(s1, s3); v[2] = csub(s0, s2); v[3] = csub(s1, s3);
 }
-GF3_DEV void bfly8_tw(cplx* v, cplx w) {              // v[r] *= w^r, then the radix-8 butterfly
-    const double c2 = w.x + w.x;
-    const cplx w2 = cmk(fma(c2, w.x, -1.0), c2 * w.y);
+template <typename Cx> GF3_DEV void bfly8_tw(Cx* v, Cx w) {   // v[r] *= w^r, then the radix-8 butterfly
+    typedef Cx cplx;
+    typedef typename CxT<Cx>::R R;
+    constexpr R S = (R)GF3_SQRT1_2;
+    const R c2 = w.x + w.x;
+    const cplx w2 = cx<Cx>(fma(c2, w.x, (R)-1.0), c2 * w.y);
     const cplx w3 = tw_next(c2, w2, w), w4 = tw_next(c2, w3, w2), w5 = tw_next(c2, w4, w3);
     const cplx w6 = tw_next(c2, w5, w4), w7 = tw_next(c2, w6, w5);
     const cplx a0 = cfma(v[4], w4, v[0]), a1 = twice_minus(v[0], a0);
@@ -163,16 +193,16 @@ GF3_DEV void bfly8_tw(cplx* v, cplx w) {              // v[r] *= w^r, then the r
     const cplx a6 = cfma(v[7], w7, u3), a7 = mul_negi(twice_minus(u3, a6));
     const cplx b0 = cadd(a0, a2), b1 = cadd(a1, a3), b2 = csub(a0, a2), b3 = csub(a1, a3);
     const cplx b4 = cadd(a4, a6), o1 = cadd(a5, a7), b6 = mul_negi(csub(a4, a6)), o3 = csub(a5, a7);
-    const double p1 = o1.x + o1.y, m1 = o1.y - o1.x;
-    const double m3 = o3.y - o3.x, p3 = o3.x + o3.y;
+    const R p1 = o1.x + o1.y, m1 = o1.y - o1.x;
+    const R m3 = o3.y - o3.x, p3 = o3.x + o3.y;
     v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-    v[1] = cmk(fma(GF3_SQRT1_2, p1, b1.x), fma(GF3_SQRT1_2, m1, b1.y));
-    v[5] = cmk(fma(-GF3_SQRT1_2, p1, b1.x), fma(-GF3_SQRT1_2, m1, b1.y));
+    v[1] = cx<Cx>(fma(S, p1, b1.x), fma(S, m1, b1.y));
+    v[5] = cx<Cx>(fma(-S, p1, b1.x), fma(-S, m1, b1.y));
     v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
-    v[3] = cmk(fma(GF3_SQRT1_2, m3, b3.x), fma(-GF3_SQRT1_2, p3, b3.y));
-    v[7] = cmk(fma(-GF3_SQRT1_2, m3, b3.x), fma(GF3_SQRT1_2, p3, b3.y));
+    v[3] = cx<Cx>(fma(S, m3, b3.x), fma(-S, p3, b3.y));
+    v[7] = cx<Cx>(fma(-S, m3, b3.x), fma(S, p3, b3.y));
 }
-template <int R> GF3_DEV void bfly_tw(cplx* v, cplx w) { if constexpr (R == 8) bfly8_tw(v, w); else bfly4_tw(v, w); }
+template <int R, typename Cx> GF3_DEV void bfly_tw(Cx* v, Cx w) { if constexpr (R == 8) bfly8_tw(v, w); else bfly4_tw(v, w); }
 
 // ---------------------------------------------------------------- LDS FFT
 // LDS footprint of one FFT buffer, in cplx elements (first exchange is padded
@@ -190,8 +220,8 @@ template <int NC> struct FftGeom {
 
 // Per-thread twiddle bases: the index k of every pass depends only on the thread,
 // so one unit twiddle per pass is loaded once per workgroup and kept in registers.
-template <int NC> struct FftTw {
-    cplx b2, b3, b4, c4;      // c4: step to the second butterfly of a 2-butterfly pass, or (fused sizes) the base
+template <int NC, typename Cx = cplx> struct FftTw {
+    Cx b2, b3, b4, c4;        // c4: step to the second butterfly of a 2-butterfly pass, or (fused sizes) the base
                               // twiddle of the mirrored butterfly of the last pass
     // Made opaque once per transform: without it LLVM hoists every twiddle POWER
     // (w^2..w^7 of each pass, ~80 VGPRs) out of the symbol loop and keeps them live across it.
@@ -200,11 +230,12 @@ template <int NC> struct FftTw {
         asm volatile("" : "+v"(b2.x), "+v"(b2.y), "+v"(b3.x), "+v"(b3.y));
         asm volatile("" : "+v"(b4.x), "+v"(b4.y), "+v"(c4.x), "+v"(c4.y));
     }
-    GF3_DEV void init(int tid, const cplx* __restrict__ tw);
+    GF3_DEV void init(int tid, const Cx* __restrict__ tw);
 };
 
-template <int NC, int R, int NS>
-GF3_DEV void fft_pass(cplx (&v)[8], const cplx* src, cplx* dst, cplx wbase, cplx wstep, int tid) {
+template <int NC, int R, int NS, typename Cx>
+GF3_DEV void fft_pass(Cx (&v)[8], const Cx* src, Cx* dst, Cx wbase, Cx wstep, int tid) {
+    typedef Cx cplx;
     constexpr int T = NC / 8, NB = 8 / R;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -249,22 +280,25 @@ template <int NC> struct Spec {
     }
     GF3_DEV static bool live(int t, int s) { return !(t == 0 && s == 1); }
     // exp(-2 pi i k_r / N), N = 2 NC, from wb = exp(-2 pi i t / N)
-    GF3_DEV static cplx pair_tw(int t, int r, cplx wb) {
-        const double c8 = 0.92387953251128675613, s8 = 0.38268343236508977173;
+    template <typename Cx> GF3_DEV static Cx pair_tw(int t, int r, Cx wb) {
+        typedef Cx cplx;
+        typedef typename CxT<Cx>::R R;
+        constexpr R S = (R)GF3_SQRT1_2;
+        const R c8 = (R)0.92387953251128675613, s8 = (R)0.38268343236508977173;
         if constexpr (FUSED) {          // k advances by N/8 per r
             cplx w = wb;
-            if (r == 1) w = cmk((wb.x + wb.y) * GF3_SQRT1_2, (wb.y - wb.x) * GF3_SQRT1_2);
+            if (r == 1) w = cx<Cx>((wb.x + wb.y) * S, (wb.y - wb.x) * S);
             if (r == 2) w = mul_negi(wb);
-            if (r == 3) w = cmk((wb.y - wb.x) * GF3_SQRT1_2, -(wb.x + wb.y) * GF3_SQRT1_2);
+            if (r == 3) w = cx<Cx>((wb.y - wb.x) * S, -(wb.x + wb.y) * S);
             if (t == 0) {
-                if (r == 0) w = cmk(0.0, -1.0);
-                if (r == 2) w = cmk(c8, -s8);
-                if (r == 3) w = cmk(s8, -c8);
+                if (r == 0) w = cx<Cx>(0.0, -1.0);
+                if (r == 2) w = cx<Cx>(c8, -s8);
+                if (r == 3) w = cx<Cx>(s8, -c8);
             }
             return w;
         } else {                        // k advances by N/16 per r
-            const cplx r16[4] = {cmk(1.0, 0.0), cmk(c8, -s8), cmk(GF3_SQRT1_2, -GF3_SQRT1_2), cmk(s8, -c8)};
-            if (r == 0) return t == 0 ? cmk(0.0, -1.0) : wb;
+            const cplx r16[4] = {cx<Cx>(1.0, 0.0), cx<Cx>(c8, -s8), cx<Cx>(S, -S), cx<Cx>(s8, -c8)};
+            if (r == 0) return t == 0 ? cx<Cx>(0.0, -1.0) : wb;
             return cmul(wb, r16[r]);
         }
     }
@@ -273,11 +307,13 @@ template <int NC> struct Spec {
 // packed-real split of one mirrored pair: A = Z[k], Bm = Z[NC-k], w = exp(-2 pi i k / N).
 // TWICE = true returns 2 X[k], 2 X[N/2-k]: the two halvings are dropped (four multiplies per pair); callers whose
 // results are ratios or signs of spectra fold the factor of two -- exact in binary -- into a constant they apply anyway.
-template <bool TWICE = false>
-GF3_DEV void real_split(cplx A, cplx Bm, cplx w, cplx& Xk, cplx& Xm) {
+template <bool TWICE = false, typename Cx>
+GF3_DEV void real_split(Cx A, Cx Bm, Cx w, Cx& Xk, Cx& Xm) {
+    typedef Cx cplx;
+    typedef typename CxT<Cx>::R R;
     const cplx B = cconj(Bm);
-    const cplx E = TWICE ? cadd(A, B) : cscale(cadd(A, B), 0.5);
-    const cplx D = TWICE ? csub(A, B) : cscale(csub(A, B), 0.5);
+    const cplx E = TWICE ? cadd(A, B) : cscale(cadd(A, B), (R)0.5);
+    const cplx D = TWICE ? csub(A, B) : cscale(csub(A, B), (R)0.5);
     Xk = cfma(mul_negi(D), w, E);                    // E + O,  O = -i D w
     Xm = cconj(twice_minus(E, Xk));                  // conj(E - O) = conj(2E - Xk)
 }
@@ -285,10 +321,11 @@ GF3_DEV void real_split(cplx A, cplx Bm, cplx w, cplx& Xk, cplx& Xm) {
 // Passes through LDS.  In: v[r] = z[tid + r*NC/8].  ALL = false stops before the last pass
 // (fused sizes).  `flip` selects which ping-pong buffer the first exchange uses; the caller
 // alternates it per transform.  Returns the buffer that holds the result.
-template <int NC, bool ALL, bool PP = FftGeom<NC>::PINGPONG>
-GF3_DEV cplx* fft_passes(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, int tid, int flip) {
+template <int NC, bool ALL, bool PP = FftGeom<NC>::PINGPONG, typename Cx>
+GF3_DEV Cx* fft_passes(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, int tid, int flip) {
+    typedef Cx cplx;
     constexpr int T = NC / 8;
-    const cplx w8 = cmk(GF3_SQRT1_2, -GF3_SQRT1_2);              // exp(-i pi/4): T steps of the last pass
+    const cplx w8 = cx<Cx>(GF3_SQRT1_2, -GF3_SQRT1_2);             // exp(-i pi/4): T steps of the last pass
     cplx* A = PP ? lds + (flip ? NC : 0) : lds;
     cplx* B = PP ? lds + (flip ? 0 : NC) : lds;
     bfly8(v);
@@ -339,16 +376,16 @@ GF3_DEV cplx* fft_passes(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, int tid, 
 // Forward complex FFT of NC points; returns the LDS buffer holding Z[0..NC) in natural order.
 // Ping-pong sizes: the caller must have a barrier between the last reads of both buffers by a
 // previous user and this call (this entry point is only used after such a barrier).
-template <int NC, bool PP = FftGeom<NC>::PINGPONG>
-GF3_DEV cplx* fft_core(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, int tid) {
+template <int NC, bool PP = FftGeom<NC>::PINGPONG, typename Cx>
+GF3_DEV Cx* fft_core(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, int tid) {
     return fft_passes<NC, true, PP>(v, lds, ft, tid, 0);
 }
 
-template <int NC> GF3_DEV void FftTw<NC>::init(int tid, const cplx* __restrict__ tw) {
+template <int NC, typename Cx> GF3_DEV void FftTw<NC, Cx>::init(int tid, const Cx* __restrict__ tw) {
     b2 = tw[(tid & 7) * (NC / 64)];                          // pass 2: radix 8, NS = 8
     if constexpr (NC == 1024) b3 = tw[(tid & 63) * (NC / 256)];      // radix 4, NS = 64
     else b3 = tw[(tid & 63) * (NC / 512)];                           // radix 8, NS = 64
-    b4 = cmk(1.0, 0.0); c4 = cmk(1.0, 0.0);
+    b4 = cx<Cx>(1.0, 0.0); c4 = cx<Cx>(1.0, 0.0);
     if constexpr (NC == 1024 || NC == 2048) {                // last pass radix 4, NS = NC/4: k = j
         b4 = tw[tid];
         c4 = tw[tid == 0 ? NC / 8 : NC / 4 - tid];           // mirrored butterfly j2 (fused split)
@@ -361,8 +398,9 @@ template <int NC> GF3_DEV void FftTw<NC>::init(int tid, const cplx* __restrict__
 // `flip` must alternate between consecutive calls in a workgroup (ping-pong hazard: the last
 // pass of call i reads buffer A_i with no barrier after it; call i+1 starts by storing into the
 // other buffer, which every wave finished reading before call i's final barrier).
-template <int NC, bool PP = FftGeom<NC>::PINGPONG, bool TWICE = false>
-GF3_DEV void rfft_regs(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, cplx wb, int t, cplx& z0, int flip) {
+template <int NC, bool PP = FftGeom<NC>::PINGPONG, bool TWICE = false, typename Cx>
+GF3_DEV void rfft_regs(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, Cx wb, int t, Cx& z0, int flip) {
+    typedef Cx cplx;
     if constexpr (Spec<NC>::FUSED) {
         constexpr int Q = NC / 4;
         const cplx* Z = fft_passes<NC, false, PP>(v, lds, ft, t, flip);
@@ -379,7 +417,7 @@ GF3_DEV void rfft_regs(cplx (&v)[8], cplx* lds, const FftTw<NC>& ft, cplx wb, in
         // that costs are confined to its wave by a scalar branch; the other waves run the plain pairing.
         if (__builtin_amdgcn_readfirstlane(t) < 64) {
             const bool t0 = (t == 0);
-            auto sel = [&](cplx x, cplx y) { return cmk(t0 ? x.x : y.x, t0 ? x.y : y.y); };
+            auto sel = [&](cplx x, cplx y) { return cx<Cx>(t0 ? x.x : y.x, t0 ? x.y : y.y); };
             const cplx A[4] = {sel(a[2], a[0]), a[1], sel(b[0], a[2]), sel(b[1], a[3])};
             const cplx Bm[4] = {sel(a[2], b[3]), sel(a[3], b[2]), sel(b[3], b[1]), sel(b[2], b[0])};
 #pragma unroll

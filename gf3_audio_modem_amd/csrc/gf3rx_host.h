@@ -4,6 +4,7 @@
 //   gf3rx_fft.hip            rfft_kernel, tx_kernel
 //   gf3rx_demod_{qpsk,scan,full,soft}.hip   the four modes of demod_kernel (gf3rx_demod.h)
 //   gf3rx_demod_split.hip, gf3rx_dsplit_{qpsk,scan,full,soft}.hip   the two-phase demodulation of long packets
+//   gf3rx_demod_screen.hip   demod_screen_kernel (fp32 data-symbol transforms under a bound, gf3rx_dscreen.h) and the LISTED fp64 pass
 //   gf3rx_corr.hip           corr_kernel, spec_kernel, ols_kernel
 //   gf3rx_screen.hip         scr_ring_kernel, scr_ols_kernel, scr_refine_kernel (gf3rx_screen.h)
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
@@ -83,11 +84,23 @@ struct DemodArgs {
     double xbar, inv_sxx;
     uint8_t* bits; int row_bytes;
     cplx* eq; cplx* Hs; cplx* He; double* slope; cplx* Hest; int* status;
-    // spectra mode (receiver.equalise as a stand-alone stage): frequency-domain inputs
-    const cplx* sp_data;      // [F, D, K]
-    const cplx* sp_start;     // [F, P, K]
-    const cplx* sp_end;       // [F, P, K]
-    cplx* eq_all;             // [F*D, K] equalised symbols on all carriers
+    union {
+        // spectra mode (receiver.equalise as a stand-alone stage): frequency-domain inputs
+        struct {
+            const cplx* sp_data;      // [F, D, K]
+            const cplx* sp_start;     // [F, P, K]
+            const cplx* sp_end;       // [F, P, K]
+            cplx* eq_all;             // [F*D, K] equalised symbols on all carriers
+        };
+        // the screened QPSK demodulation (gf3rx_dscreen.h: time-domain input, bits only) keeps its pointers in the same
+        // four slots, so that the block -- which the soft mode copies to its stack -- is the size it was
+        struct {
+            const cf* tw32;           // [NC | NC/2+1] the two twiddle tables rounded once to fp32, one after the other
+            int* dwork;               // [count | pad to 16 ints | packet numbers]: the screen appends the packets it cannot
+                                      // decide; the LISTED fp64 pass reads them: packet = dwork[16 + blockIdx.x], blockIdx.x < dwork[0]
+            cf* dbg_ep; float* dbg_E; // optional (tests): [F][D][C] fp32 rotated symbols, [F][D] the bound
+        };
+    };
     double qpsk_q;            // >0: table is the reference QPSK table (+-q +-qj): decide by signs away from ties
     UniGrid ug;
     unsigned long long* stamps;   // diagnostic build only (-DGF3_STAMPS): [F][8] s_memtime per phase
@@ -182,6 +195,7 @@ struct gf3_ctx {
     int fit_lo, fit_hi;
     double xbar, inv_sxx;
     cplx *d_tw = nullptr, *d_twn = nullptr, *d_known = nullptr;
+    cf* d_tw32 = nullptr;               // d_tw, then d_twn, rounded once to fp32: the screened demodulation's data-symbol transforms (gf3rx_dscreen.h)
     cplx *d_tw_x[2] = {nullptr, nullptr}, *d_twn_x[2] = {nullptr, nullptr};   // twiddles of plans whose FFT size != N
     int nc_x[2] = {0, 0};
     int *d_pos = nullptr, *d_clab = nullptr;
@@ -211,15 +225,18 @@ struct gf3_ctx {
     // gf3_sync_stream (gf3_sync_stream_mode sets it; gf3_sync_stream_ex takes the mode per call and never reads it).
     // 0: by stream length (screen from GF3_SCR_MIN_SAMPLES on); 1: fp64 only; 2: screen whenever a plan exists; 3: as 2 with the general kernel
     std::atomic<int> default_stream_mode{0};
-    // (ii) The workspaces of the frames-mode sync in auto mode (gf3_sync_frames; sync_frames_impl), under fs_mu: one
-    // [count | pad | F window numbers] buffer per (stream, host thread), created on first use and grow-only.  Calls of one
-    // thread on one stream share a buffer through stream order; other streams and other threads have their own.  A buffer
-    // that is outgrown may still be read by a queued kernel: it goes to fs_retired, which gf3_ctx_destroy frees after a
-    // device synchronise.
-    struct FsWork { hipStream_t stream; std::thread::id thread; void* d = nullptr; int64_t bytes = 0; };
-    std::mutex fs_mu;
-    std::vector<FsWork> fs_work;
-    std::vector<void*> fs_retired;
+    // (ii) The list workspaces of the screened paths in auto mode, under ws_mu: per (stream, host thread) one
+    // [count | pad | F numbers] buffer for the frames-mode sync's unresolved windows (slot WS_SYNC: gf3_sync_frames;
+    // sync_frames_impl) and one for the QPSK demodulation's listed packets (slot WS_DEMOD: gf3_demod_frames_px) -- two
+    // slots, because a demodulation queued behind a sync on the same stream must not overwrite the list the sync's fp64 pass
+    // still reads.  Created on first use and grow-only.  Calls of one thread on one stream share a buffer through stream
+    // order; other streams and other threads have their own.  A buffer that is outgrown may still be read by a queued
+    // kernel: it goes to ws_retired, which gf3_ctx_destroy frees after a device synchronise.
+    enum { WS_SYNC = 0, WS_DEMOD = 1, WS_SLOTS = 2 };
+    struct Work { hipStream_t stream; std::thread::id thread; void* d[WS_SLOTS] = {nullptr, nullptr}; int64_t bytes[WS_SLOTS] = {0, 0}; };
+    std::mutex ws_mu;
+    std::vector<Work> ws_work;
+    std::vector<void*> ws_retired;
     std::vector<double> chirp;
     std::vector<cplx> known_pts;
     std::vector<void*> owned;           // every device allocation that lives as long as the context (gf3rx_ctx.hip)
@@ -299,6 +316,15 @@ inline hipError_t run_rfft(const gf3_ctx* c, const void* d_in, int64_t n_in, int
     return run_rfft_nc(c->NC, FftTables{c->d_tw, c->d_twn}, d_in, n_in, dt, d_off, n_sym, d_out, st);
 }
 int tx_launch(gf3_ctx* c, const TxArgs& a, int64_t F, hipStream_t st);
+// gf3rx_ctx.hip: the context's list workspace of the calling thread on this stream (slot: gf3_ctx::WS_*), at least `bytes`;
+// nullptr: none can be had now (the stream is being captured and nothing large enough exists, the table is full, the
+// allocation failed) -- the caller then runs its fp64 path
+void* ctx_workspace(gf3_ctx* c, hipStream_t st, int slot, int64_t bytes);
+// gf3rx_demod_screen.hip: the screened QPSK demodulation (gf3rx_dscreen.h) and the fp64 kernel on the packets it listed
+bool demod_screen_applies(const gf3_ctx* c);
+hipError_t launch_demod_screen(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
+hipError_t launch_demod_listed(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
+hipError_t launch_demod_verdicts(const int* dwork, int* cls, int64_t F, hipStream_t st);     // tests: cls[f] = 1 for listed f, else 0
 // gf3rx_demod_{qpsk,scan,full}.hip: one packet per workgroup (time-domain input); `full` also serves the spectra mode
 hipError_t launch_demod_qpsk(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);
 hipError_t launch_demod_scan(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);

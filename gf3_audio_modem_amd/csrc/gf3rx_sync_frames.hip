@@ -1,5 +1,5 @@
 // libgf3rx -- the frames-mode chirp sync: gf3_sync_frames* and the dispatch between the all-fp64 corr_kernel and the fp32
-// screen with a proven bound (gf3rx_fscreen.h), with the workspaces the context keeps for the screen's unresolved list.
+// screen with a proven bound (gf3rx_fscreen.h), in a list workspace the context keeps per stream and host thread (ctx_workspace, gf3rx_ctx.hip).
 #include "gf3rx_host.h"
 #include "gf3rx_fscreen.h"
 
@@ -10,29 +10,6 @@ extern "C" int64_t gf3_sync_frames_workspace_bytes(const gf3_ctx* c, int64_t F) 
 
 // What the calling thread's last frames sync did (gf3_sync_frames_last): kept per host thread like every other diagnostic.
 static thread_local struct { const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0; } g_fs_last;
-#define GF3_FS_MAX_WORKSPACES 64
-
-// The context's workspace of the calling thread on this stream, holding at least `bytes`; nullptr: none can be had now (the
-// stream is being captured and nothing large enough exists, the table is full, the allocation failed) -- the caller
-// then runs the fp64 kernel.  An outgrown buffer is retired, not freed: a queued kernel may still read it.
-static void* fs_workspace(gf3_ctx* c, hipStream_t st, int64_t bytes) {
-    const std::thread::id me = std::this_thread::get_id();
-    std::lock_guard<std::mutex> lock(c->fs_mu);
-    gf3_ctx::FsWork* e = nullptr;
-    for (auto& w : c->fs_work) if (w.stream == st && w.thread == me) { e = &w; break; }
-    if (e && e->bytes >= bytes) return e->d;
-    if (!e && c->fs_work.size() >= GF3_FS_MAX_WORKSPACES) return nullptr;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (cap != hipStreamCaptureStatusNone) return nullptr;               // an allocation would break the capture
-    int64_t want = bytes;
-    if (e && want < e->bytes + e->bytes / 2) want = e->bytes + e->bytes / 2;   // (a slowly growing F: few retired buffers)
-    void* d = nullptr;
-    if (hipMalloc(&d, (size_t)want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (e) { c->fs_retired.push_back(e->d); e->d = d; e->bytes = want; }
-    else c->fs_work.push_back(gf3_ctx::FsWork{st, me, d, want});
-    return d;
-}
 
 // mode 0: all fp64 (corr_kernel on every window).  mode 1: fp32 screen with a proven bound per window (gf3rx_fscreen.h) in
 // the caller's workspace; the windows it cannot decide are listed and corr_kernel runs on those.  mode -1 (auto, what plain
@@ -57,7 +34,7 @@ static int sync_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t 
     const bool can_screen = fp.ok && W <= fp.wmax && !d_peak && F <= 0x7fffffff;
     if (mode == 1 && !d_work) mode = 0;
     void* work = mode == 1 ? d_work : nullptr;
-    if (mode == -1 && can_screen) work = fs_workspace(c, st, gf3_sync_frames_workspace_bytes(c, F));
+    if (mode == -1 && can_screen) work = ctx_workspace(c, st, gf3_ctx::WS_SYNC, gf3_sync_frames_workspace_bytes(c, F));
     const bool screened = can_screen && work;
     if (screen_only && !screened) return fail(c, GF3_EINVAL, "gf3_debug_frames_screen: no screening plan for this window (max_window %d)", fp.wmax);
     g_fs_last.ctx = c; g_fs_last.stream = stream; g_fs_last.path = screened ? 0 : 2; g_fs_last.cap = screened ? (int32_t)F : 0;

@@ -225,22 +225,66 @@ class Engine:
         self._check(self.lib.gf3_rfft_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
         return out
 
-    def demod_frames(self, x, frame_offsets, want=(), out_bits=None, split=None):
+    def demod_frames(self, x, frame_offsets, want=(), out_bits=None, split=None, precision=None):
         """Fused a3-a10.  Returns dict with 'bits' (packed uint8
         [F, bytes_per_frame]) plus any of 'eq','Hs','He','slope','Hest','status'.
         split: None -- the library chooses between one packet per workgroup and the two-phase form for long packets,
         few at a time (gf3_demod_frames_ex: pilot sums, estimate, data symbols spread over the chip; the reference's own
-        geometry of 3 packets x 220 symbols); False / True force the one or the other."""
+        geometry of 3 packets x 220 symbols); False / True force the one or the other.
+        precision: None -- the library decides (gf3_demod_frames_px precision -1): with the reference QPSK table, bits-only
+        output and f32 / i16 / u8 samples the data symbols are transformed in fp32 under a proven bound and the fp64 kernel
+        runs only on the packets the bound cannot decide -- the all-fp64 outputs, bit for bit.  "fp64": the all-fp64 kernel
+        on every packet.  "screen": ask for the screened path (it still runs all fp64 where it does not apply).
+        demod_frames_last() tells which way a call went."""
+        if precision not in (None, "fp64", "screen"):
+            raise ValueError(f"precision must be None, 'fp64' or 'screen', not {precision!r}")
         x = self._samples(x)
         off = self._dev(frame_offsets, torch.int64)
         F = off.numel()
         bits = out_bits if out_bits is not None else self._new((F, self.bytes_per_frame), torch.uint8)
         o = {"bits": bits, **self._wanted(want, F, ("eq", "Hs", "He", "slope", "Hest", "status"))}
         work, mode = self._split_work(F, split)
-        self._check(self.lib.gf3_demod_frames_ex(
+        self._check(self.lib.gf3_demod_frames_px(
             self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(bits), _ptr(o.get("eq")), _ptr(o.get("Hs")),
             _ptr(o.get("He")), _ptr(o.get("slope")), _ptr(o.get("Hest")), _ptr(o.get("status")),
-            _ptr(work), mode, self._stream()))
+            _ptr(work), mode, {None: -1, "fp64": 0, "screen": 1}[precision], self._stream()))
+        return o
+
+    def demod_frames_last(self):
+        """Of the calling thread's last demod_frames call on the current stream: dict(path = 0 screened | 2 all fp64 | -1 no
+        such call, listed_capacity = packets its fp64 pass could take).  No device read."""
+        path, cap = C.c_int32(-1), C.c_int32(0)
+        self._check(self.lib.gf3_demod_frames_last(self._h, self._stream(), C.byref(path), C.byref(cap)))
+        return dict(path=int(path.value), listed_capacity=int(cap.value))
+
+    def debug_rfft32_batch(self, x, offsets):
+        """The screened demodulation's fp32 transform alone (tests): [n_sym, N/2+1] complex64 spectra of the N samples
+        starting at each offset; f32 / i16 / u8 samples."""
+        x = self._samples(x)
+        offsets = self._dev(offsets, torch.int64)
+        n = offsets.numel()
+        out = self._new((n, self.cfg.N // 2 + 1), torch.complex64)
+        self._check(self.lib.gf3_debug_rfft_sp_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
+        return out
+
+    def debug_demod_screen(self, x, frame_offsets):
+        """The fp32 screening pass of the QPSK demodulation alone (tests): dict(bits: the screen's own rows, ep32 [F, D, C]
+        complex64 -- the rotated fp32 symbols 2 X conj(g) of the data carriers --, E [F, D] float32 -- the bound on
+        |ep32 - exact| of each symbol's transform --, cls int32 [F] (0 decided, 1 listed), listed: sorted packet numbers
+        the fp64 kernel would be run on)."""
+        cfg = self.cfg
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F = off.numel()
+        o = dict(bits=self._new((F, self.bytes_per_frame), torch.uint8),
+                 ep32=torch.zeros((F, cfg.D, cfg.C), dtype=torch.complex64, device=self.device),
+                 E=torch.zeros((F, cfg.D), dtype=torch.float32, device=self.device),
+                 cls=torch.full((F,), -1, dtype=torch.int32, device=self.device))
+        work = self._new((int(self.lib.gf3_demod_screen_workspace_bytes(self._h, F)),), torch.uint8)
+        self._check(self.lib.gf3_debug_demod_screen(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(o["bits"]), _ptr(o["ep32"]),
+                                                    _ptr(o["E"]), _ptr(o["cls"]), _ptr(work), self._stream()))
+        n = int(work[:4].view(torch.int32).item())
+        o["listed"] = torch.sort(work[64: 64 + 4 * n].view(torch.int32)).values
         return o
 
     def demod_frames_llr(self, x, frame_offsets, weight="csi", want=(), split=None, out=None):

@@ -165,6 +165,52 @@ int gf3_demod_frames_ex(gf3_ctx *ctx, const void *d_in, int64_t n_in,
                         void *d_work, int32_t mode, void *stream);
 
 /*
+ * The same call with the PRECISION of the QPSK data-symbol transforms chosen per call.  With the reference QPSK table and
+ * bits-only output, what the caller receives from a data symbol is two sign bits per carrier, and on a usable signal
+ * those sit orders of magnitude above the rounding of an fp32 transform.  The screened path keeps the whole pilot stage
+ * (channel estimate, slope fit, phasors) in fp64 -- Hs, He and slope are bit for bit the fp64 kernel's --, transforms the
+ * data symbols in fp32 with a proven error bound per symbol, and lists every packet in which a sign is not backed by the
+ * bound; the fp64 kernel then runs on the listed packets.  The outputs are the all-fp64 outputs, bit for bit.
+ *   precision  -1: auto (what gf3_demod_frames and gf3_demod_frames_ex mean): screened whenever the screen applies
+ *               0: all fp64 on every packet (the reference the screened path is tested against)
+ *               1: the explicit request for the screen: screened whenever the screen applies, whatever auto means in this
+ *                  build (auto takes the screen because the A/B recorded in profiles/demod_screen_ab.json showed a clear gain)
+ * The screen applies when the constellation is the reference QPSK table, neither d_eq nor d_Hest is asked for, the
+ * one-launch form is chosen (the two-phase form is never screened), the samples are stored as f32, i16 or u8 (f64 is not:
+ * fp32 does not hold it exactly), F <= 2^31 - 1, and a list workspace can be had.  The library keeps one such workspace per
+ * (stream, calling host thread), created on first use and grow-only, next to the frames sync's and under the same rules:
+ * nothing is allocated while the stream is being captured into a graph (call once with the largest F before capturing),
+ * a failed allocation or a full table (64 per context) means the all-fp64 path, not an error.
+ * COST ON NOISY INPUT: a listed packet is demodulated twice, and one unbacked sign among a packet's tens of thousands lists
+ * it.  The bound is rigorous and therefore loose (about 1/230 of a QPSK part): nothing is listed on clean input and at 20 dB
+ * of SNR, but at 10 dB and below MOST packets are, and the call then costs the fp32 pass plus nearly a whole fp64 pass --
+ * slower than the all-fp64 path (DESIGN 3.5 has the measured shares and times).  precision = 0 is the way out for input
+ * known to be that poor.
+ *
+ * gf3_demod_frames_last: what the CALLING THREAD's last gf3_demod_frames / _ex / _px call did, if that call was on this
+ * context and stream, without a device read: *path = 0 screened, 2 all fp64, -1 no such call; *listed_capacity (optional)
+ * = packets the fp64 pass of a screened call could take (F), 0 otherwise.
+ */
+int gf3_demod_frames_px(gf3_ctx *ctx, const void *d_in, int64_t n_in,
+                        const int64_t *d_frame_offsets, int64_t F,
+                        uint8_t *d_bits_packed, void *d_eq, void *d_Hs, void *d_He,
+                        double *d_slope, void *d_Hest, int32_t *d_status,
+                        void *d_work, int32_t mode, int32_t precision, void *stream);
+int gf3_demod_frames_last(const gf3_ctx *ctx, void *stream, int32_t *path, int32_t *listed_capacity);
+/* tests: the screening pass alone.  d_ep32 [F][D][C] complex64: the rotated fp32 symbols (2 X conj(g)) of the data carriers
+ * in data_bins order; d_E [F][D] float32: the bound of each symbol; d_cls [F] int32: 0 decided, 1 listed; d_list: AT LEAST
+ * gf3_demod_screen_workspace_bytes(ctx, F) bytes, [count | pad to 64 bytes | listed packet numbers]; d_bits_packed gets the
+ * screen's own rows.  Fails where the screen does not apply. */
+int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx *ctx, int64_t F);
+/* tests: the fp32 transform of the screened demodulation alone (the same passes on single-precision points, the context's
+ * twiddles rounded once): d_out_c64 [n_sym, N/2+1] complex64 spectra of the N samples at each offset, as gf3_rfft_batch
+ * gives them in fp64.  f32 / i16 / u8 samples only. */
+int gf3_debug_rfft_sp_batch(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_offsets, int64_t n_sym,
+                           void *d_out_c64, void *stream);
+int gf3_debug_demod_screen(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                           uint8_t *d_bits_packed, void *d_ep32, float *d_E, int32_t *d_cls, void *d_list, void *stream);
+
+/*
  * receiver.equalise as a stand-alone stage (OFDM.py:422-480): the same kernel
  * as gf3_demod_frames, fed with frequency-domain symbols instead of samples.
  *   d_data [F, D, K], d_start [F, P, K], d_end [F, P, K] complex128 (get_data's outputs)
