@@ -167,8 +167,8 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     extern __shared__ double2 smem[];
     constexpr int T = NC / 8;
     // LDS: [scratch 32 doubles | start-up rotation tables | FFT buffer | decision bytes | (fit-range overflow)]
-    // scratch: doubles [16, 32) are block_sum's (the slope fit); VAR_SCREEN also keeps the per-wave l1 sums of the data symbols
-    // in doubles [0, 8) (as float [2][8]) and the packet's "listed" flag in double 8
+    // scratch: doubles [16, 32) are block_sum's (the slope fit); once that is done VAR_SCREEN keeps the per-wave l1 sums of the
+    // data symbols there (as float [2][2][8]), and the packet's "listed" flag in double 8
     double* scratch = (double*)smem;
     cplx* rtab = (cplx*)(scratch + 32);                                   // [2][64 + NC/64 + 1]
     cplx* lds = rtab + 2 * (64 + NC / 64 + 1);                            // FFT buffer, DemodOcc::LDS_ELEMS points
@@ -244,27 +244,46 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
 #pragma unroll
         for (int s2 = 0; s2 < 8; ++s2) v[s2] = sp[bin_of(s2) - 1];
     };
-    // VAR_SCREEN: nxt -> fp32 spectrum slots in v32, the same passes on float2 points in the first half of the FFT buffer.
-    // The symbol's l1 norm is summed while the samples are converted; the per-wave sums go to l1s[parity][wave] ahead of
-    // the transform's barriers and are read back after them (two parities: symbol i + 1 writes before every wave has read
-    // symbol i's; i + 2 writes only after the barriers of transform i + 1).
-    cf v32[8], z032, wb32;
+    // VAR_SCREEN: the data symbols go through the transform two at a time, as the halves of cf2 points (gf3rx_device.h) in
+    // the whole FFT buffer: symbols (l, l + 1) from nxt and nxb -> fp32 spectrum slots in vp, the next pair prefetched (its
+    // first symbol under the transform, its second under the decisions).  An odd last symbol runs the same code with an
+    // absent second half: no loads, zeros, no decisions.
+    // Each symbol's l1 norm is summed while its samples are converted; the per-wave sums go to l1s[parity][half][wave] ahead
+    // of the transform's barriers and are read back after them (two parities: pair i + 1 writes before every wave has read
+    // pair i's; i + 2 writes only after the barriers of transform i + 1).
+    cf2 vp[8], z0p;
+    int tp = tid;                                     // the pair transform's thread index, made opaque ahead of the data loop
+    cf wb32;
     FftTw<NC, cf> ft32;
-    float* l1s = (float*)scratch;                                         // [2][8]; scratch[8]: the packet's "listed" flag
+    RawPair<DT> nxb[8];
+    float* l1s = (float*)(scratch + 16);                                  // [2][2][8]; scratch[8]: the packet's "listed" flag
     int* unsafe_flag = (int*)(scratch + 8);
-    auto transform32 = [&](int i) {
-        float s1 = 0.0f;
+    auto fetch_b = [&](int i) {
+        typedef typename RawT<DT>::E E;
+        const E* base = (const E*)a.in + (off + (int64_t)sym_pos(i) * S + a.CP);      // wave-uniform
+        const unsigned t2 = 2u * (unsigned)launder(tid);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) nxb[r].load_u(base, t2 + 2u * (unsigned)(r * T));
+    };
+    auto transform_pair = [&](int l) {                // l: the pair's first data symbol
+        const bool hb = l + 1 < D;
+        float sa = 0.0f, sb = 0.0f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            v32[r] = make_float2((float)nxt[r].v.a, (float)nxt[r].v.b);
-            s1 += fabsf(v32[r].x) + fabsf(v32[r].y);
+            const cf pa = make_float2((float)nxt[r].v.a, (float)nxt[r].v.b);
+            const cf pb = make_float2(hb ? (float)nxb[r].v.a : 0.0f, hb ? (float)nxb[r].v.b : 0.0f);
+            sa += fabsf(pa.x) + fabsf(pa.y);
+            sb += fabsf(pb.x) + fabsf(pb.y);
+            vp[r] = pair_of(pa, pb);
         }
-        if (i + 1 < Msym) fetch(i + 1);
-        s1 = scr_wave_reduce<false>(s1);
-        if ((tid & 63) == 0) l1s[(i & 1) * 8 + (tid >> 6)] = s1;
+        if (l + 2 < D) fetch(2 * P + l + 2);
+        sa = scr_wave_reduce<false>(sa);
+        sb = scr_wave_reduce<false>(sb);
+        const int par = (l >> 1) & 1;
+        if ((tid & 63) == 0) { l1s[par * 16 + (tid >> 6)] = sa; l1s[par * 16 + 8 + (tid >> 6)] = sb; }
         ft32.refresh();
         asm volatile("" : "+v"(wb32.x), "+v"(wb32.y));
-        rfft_regs<NC, DemodOcc<NC, MODE>::PP, true>(v32, (cf*)lds, ft32, wb32, tq, z032, i & 1);
+        rfft_regs<NC, DemodOcc<NC, MODE>::PP, true>(vp, (cf2*)lds, ft32, wb32, tp, z0p, par);
     };
     GF3_STAMP(0);
     GF3_STAMP_RT(6);
@@ -303,7 +322,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
             for (int i = side * Pl; i < (side + 1) * Pl; ++i) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) sum[r] = cadd(sum[r], nxt[r].get());
-                if (i + 1 < Msym) fetch(i + 1);                    // next pilot, or the first data symbol
+                if (i + 1 < (SCREEN ? 2 * P : Msym)) fetch(i + 1); // next pilot, or the first data symbol (VAR_SCREEN: ahead of the data loop)
             }
             if (side == 0) GF3_STAMP(1);
 #pragma unroll
@@ -503,39 +522,93 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     // (QPSK mode; the table modes have no registers to spare for it -- even packed two to a register the positions push
     //  the kernel from 240 VGPRs to 256 and into spills -- and recompute the position per symbol: plain arithmetic for a
     //  contiguous band)
+    // VAR_SCREEN: g_0 and gstep rounded once; the recurrence runs in fp32 from here on (gf3rx_dscreen.h, "The rotation") and
+    // the 64 registers of fp64 state are free inside the data loop
+    cf g32[8], gs32[8];
+    if constexpr (SCREEN) {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            g32[s] = make_float2((float)u[s].x, (float)u[s].y);
+            gs32[s] = make_float2((float)gstep[s].x, (float)gstep[s].y);
+        }
+    }
     int psl[8];
-    if constexpr (MODE == MODE_QPSK) {
+    uint32_t psp[4];                                  // VAR_SCREEN: the same, two to a register (C < 65535; 0xffff: no data carrier)
+    if constexpr (SCREEN) {
+#pragma unroll
+        for (int s = 0; s < 8; s += 2) psp[s >> 1] = ((uint32_t)pos_of(s) & 0xffffu) | ((uint32_t)pos_of(s + 1) << 16);
+    } else if constexpr (MODE == MODE_QPSK) {
 #pragma unroll
         for (int s = 0; s < 8; ++s) psl[s] = pos_of(s);
     }
+    if constexpr (SCREEN) {
+        // cf2 points are as large as fp64 points, so the pair transform's LDS addresses are the pilot transforms': derived from
+        // tid they would be computed once at the top of the kernel and held (or spilled) across the fit
+        tp = launder(tid);
+        // The first pair of data symbols, held behind the fp64 start-up by the scheduling barrier.  Fetched earlier (with the
+        // last pilot, as the one-symbol loops do, or under the rotation tables) the f32 instantiations of the fused sizes
+        // spill 8-11 VGPRs: the start-up has the 32 table reads of its rotations in flight next to u and gstep.  (One exposed
+        // fetch per packet; the CU's other workgroup runs under it.)
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(2 * P);
+        if (D > 1) fetch_b(2 * P + 1);
+        // Two symbols decided and two packed per turn.  The ring (demod_ring): while pack_words(l - 2) and (l - 1) read slots
+        // l - 2 - ceil(32 / (C mu)) .. l - 1, NO slot is written -- the barrier below stands between the packing and the
+        // decisions of symbols l, l + 1, whose slots may then be any the coming packs no longer need: they overwrite l - ring
+        // and l + 1 - ring, and the oldest slot still to be read is l - ceil(32 / (C mu)) (the turn after), so
+        // ring >= ceil(32 / (C mu)) + 2 as for one symbol per turn.  (Without the barrier five slots would be in use at
+        // C mu = 4092 and the ring would have to double, which two workgroups per CU have no LDS for.)
+        for (int l = 0; l < D; l += 2) {
+            const bool hb = l + 1 < D;
+            transform_pair(l);
+            // the next pair's second symbol is fetched under the packing and the decisions, its first under the transform: two
+            // symbols in flight across the transform do not fit the register file (f32 storage: 16 VGPRs each)
+            if (l + 3 < D) fetch_b(2 * P + l + 3);
+            if (l > 0) { pack_words(l - 2, false); pack_words(l - 1, false); }
+            lds_barrier();
+            const int par = (l >> 1) & 1;
+            float l1a = 0.0f, l1b = 0.0f;
+#pragma unroll
+            for (int w = 0; w < (T + 63) / 64; ++w) { l1a += l1s[par * 16 + w]; l1b += l1s[par * 16 + 8 + w]; }
+            const float Ea = dscr_bound<NC>(l1a), Eb = dscr_bound<NC>(l1b);  // (an absent half: l1b = 0, Eb finite)
+            unsafe = unsafe || !(Ea < INFINITY) || !(Eb < INFINITY);
+            if (a.dbg_E && tid == 0) {
+                a.dbg_E[f * D + l] = Ea;
+                if (hb) a.dbg_E[f * D + l + 1] = Eb;
+            }
+            uint8_t* lab_a = labs + (l & (a.ring - 1)) * C;
+            uint8_t* lab_b = labs + ((l + 1) & (a.ring - 1)) * C;
+            const float Ca = dscr_rot(l), Cb = dscr_rot(l + 1);
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const cf ga = g32[s];
+                const cf gb = cmul(ga, gs32[s]);                           // the recurrence of the modes below, in fp32
+                g32[s] = cmul(gb, gs32[s]);
+                cf epa, epb;
+                bool safe_a, safe_b;
+                const uint32_t la = dscr_decide(half_a(vp[s]), ga, Ea, Ca, epa, safe_a);
+                const uint32_t lb = dscr_decide(half_b(vp[s]), gb, Eb, Cb, epb, safe_b);
+                const int ps = (int)((psp[s >> 1] >> (16 * (s & 1))) & 0xffffu);
+                if (ps != 0xffff) {
+                    lab_a[ps] = (uint8_t)la;
+                    unsafe = unsafe || !safe_a;
+                    if (a.dbg_ep) a.dbg_ep[(f * D + l) * (int64_t)C + ps] = epa;
+                    if (hb) {
+                        lab_b[ps] = (uint8_t)lb;
+                        unsafe = unsafe || !safe_b;
+                        if (a.dbg_ep) a.dbg_ep[(f * D + l + 1) * (int64_t)C + ps] = epb;
+                    }
+                }
+            }
+        }
+    } else
     for (int l = l_lo; l < l_hi; ++l) {
         if constexpr (SPECTRA) { lds_barrier(); load_spectra(a.sp_data + ((int64_t)f * D + l) * K); }
-        else if constexpr (SCREEN) transform32(2 * P + l);
         else transform(2 * P + l);
         if constexpr (MODE != MODE_SOFT) { if (l > l_lo) pack_words(l - 1, false); }
         const double fl = ((double)l + 0.5 * (double)P) / denom;          // (l + P/2)/(D+P)
         uint8_t* lab_l = labs + (l & (a.ring - 1)) * C;
-        if constexpr (SCREEN) {
-            float l1 = 0.0f;
-#pragma unroll
-            for (int w = 0; w < (T + 63) / 64; ++w) l1 += l1s[((2 * P + l) & 1) * 8 + w];
-            const float El = dscr_bound<NC>(l1);
-            unsafe = unsafe || !(El < INFINITY);
-            if (a.dbg_E && tid == 0) a.dbg_E[f * D + l] = El;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const cplx g = u[s];
-                cf ep;
-                bool safe;
-                const uint32_t lab = dscr_decide(v32[s], g, El, ep, safe);
-                u[s] = cmul(g, gstep[s]);                                  // the fp64 recurrence, as below
-                if (psl[s] >= 0) {
-                    lab_l[psl[s]] = (uint8_t)lab;
-                    unsafe = unsafe || !safe;
-                    if (a.dbg_ep) a.dbg_ep[(f * D + l) * (int64_t)C + psl[s]] = ep;
-                }
-            }
-        } else if constexpr (MODE == MODE_QPSK) {
+        if constexpr (MODE == MODE_QPSK) {
             // all eight carriers in one straight line: rotate, advance the phasors, take the sign bits; the exact
             // tie / NaN / Inf rule is one rarely taken branch for the whole group instead of one per carrier
             cplx ep[8];
@@ -657,6 +730,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     if constexpr (SCREEN) { if (unsafe) *unsafe_flag = 1; }
     if constexpr (MODE != MODE_SOFT) {
         lds_barrier();
+        if constexpr (SCREEN) { if ((D & 1) == 0) pack_words(D - 2, false); }       // the last pair's first symbol
         pack_words(l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
     }
     if constexpr (SCREEN) {
@@ -673,6 +747,11 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
 // ============================================================================
 // symbols in the decision-byte ring of demod_kernel: ceil(32 / (C mu)) + 2, rounded up to a power of two
 // (>= 4: the QPSK packer reads the ring one aligned dword at a time, so ring * C must be a multiple of 4)
+// Invariant: no slot is written while a thread may still read it, and a slot is overwritten only once every word that
+// touches it is packed.  One symbol per turn (fp64 forms): symbol l is written while pack_words(l - 1) reads back to slot
+// l - 1 - ceil(32 / (C mu)) between the same barriers, hence the + 2.  VAR_SCREEN decides two symbols per turn and keeps
+// this ring: a barrier separates its packing from its decisions (see its data loop), so reads and writes never share an
+// interval and only the second half of the invariant is left, which ring >= ceil(32 / (C mu)) + 2 also covers.
 inline int demod_ring(const gf3_ctx* c) {
     const int Bs = c->cfg.C * c->cfg.mu;
     const int need = (32 + Bs - 1) / Bs + 2;

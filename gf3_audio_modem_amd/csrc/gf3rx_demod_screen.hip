@@ -106,3 +106,60 @@ extern "C" int gf3_debug_rfft_sp_batch(gf3_ctx* c, const void* d_in, int64_t n_i
     HIPCHK(c, e);
     return GF3_OK;
 }
+
+// tests (gf3_debug_rfft_sp_pair_batch): the transform the screen runs on its data symbols -- rfft_regs<NC, PP, TWICE, cf2>,
+// two symbols as the halves of one point -- workgroup w on symbols 2w and 2w + 1 (an odd n_sym: the last second half is
+// absent, zeros in and nothing out); output as rfft32_kernel's
+struct Rfft32PairArgs { Rfft32Args r; int64_t n_sym; };
+template <int NC, int DT>
+__global__ __launch_bounds__(NC / 8, 2) void rfft32_pair_kernel(Rfft32PairArgs pa) {
+    extern __shared__ double2 smem[];
+    const RfftArgs& a = pa.r.r;
+    const cf* tw32 = pa.r.tw32;
+    constexpr int T = NC / 8;
+    const int tid = threadIdx.x;
+    const int64_t sa = 2 * (int64_t)blockIdx.x, sb = sa + 1;
+    const bool hb = sb < pa.n_sym;
+    const int64_t offa = a.off[sa], offb = hb ? a.off[sb] : -1;
+    FftTw<NC, cf> ft;
+    ft.init(tid, tw32);
+    const cf wb = tw32[NC + tid];
+    cf2 v[8], z0;
+    const bool oka = offa >= 0 && offa + 2 * NC <= a.n_in, okb = hb && offb >= 0 && offb + 2 * NC <= a.n_in;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        RawPair<DT> ra, rb;
+        if (oka) ra.load(a.in, offa + 2 * (int64_t)(tid + r * T)); else ra.zero();
+        if (okb) rb.load(a.in, offb + 2 * (int64_t)(tid + r * T)); else rb.zero();
+        v[r] = pair_of(make_float2((float)ra.v.a, (float)ra.v.b), make_float2((float)rb.v.a, (float)rb.v.b));
+    }
+    rfft_regs<NC, DemodOcc<NC, MODE_QPSK>::PP, true>(v, (cf2*)smem, ft, wb, tid, z0, 0);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h == 1 && !hb) break;
+        cf* out = pa.r.out32 + (sa + h) * (int64_t)(NC + 1);
+#pragma unroll
+        for (int s2 = 0; s2 < 8; ++s2) {
+            const cf x = h ? half_b(v[s2]) : half_a(v[s2]);
+            if (Spec<NC>::live(tid, s2)) out[Spec<NC>::bin(tid, s2)] = make_float2(0.5f * x.x, 0.5f * x.y);
+        }
+        if (tid == 0) {
+            const cf z = h ? half_b(z0) : half_a(z0);
+            out[0] = make_float2(z.x + z.y, 0.0f);
+            out[NC] = make_float2(z.x - z.y, 0.0f);
+        }
+    }
+}
+extern "C" int gf3_debug_rfft_sp_pair_batch(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_offsets, int64_t n_sym,
+                                           void* d_out_c64, void* stream) {
+    DeviceGuard dg(c);
+    if (c && n_sym == 0) return GF3_OK;
+    if (!c || !d_in || !d_offsets || !d_out_c64 || n_sym < 0) return fail(c, GF3_EINVAL, "gf3_debug_rfft_sp_pair_batch: bad argument");
+    if (c->cfg.in_dtype == DT_F64) return fail(c, GF3_EINVAL, "gf3_debug_rfft_sp_pair_batch: f64 samples are not transformed in fp32");
+    Rfft32PairArgs a{Rfft32Args{RfftArgs{FftTables{c->d_tw, c->d_twn}, d_in, n_in, d_offsets, c->cfg.in_dtype, nullptr}, c->d_tw32, (cf*)d_out_c64}, n_sym};
+    const size_t lds = (size_t)(demod_pp_size(c->NC) ? 2 * c->NC : c->NC + c->NC / 8) * sizeof(cf2);
+    hipError_t e = hipSuccess;
+    DISPATCH_NC32(c->NC, a.r.r.dt, e = launch((rfft32_pair_kernel<NCC, DTC>), (n_sym + 1) / 2, NCC / 8, lds, (hipStream_t)stream, a));
+    HIPCHK(c, e);
+    return GF3_OK;
+}

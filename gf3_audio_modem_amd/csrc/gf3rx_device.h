@@ -30,9 +30,16 @@ GF3_DEV cplx mul_posi(cplx a) { return cmk(-a.y, a.x); }   // a * (+i)
 // The same helpers on single-precision points (float2): the transform below is written once on the point type Cx and
 // instantiated for both (the fp32 form serves the screened QPSK demodulation, gf3rx_dscreen.h).  CxT<Cx>::R is the scalar
 // type, cx<Cx>(a, b) makes a point of either kind from constants.
+// A third point type, cf2, carries the same complex point of TWO symbols ({re_a, re_b}, {im_a, im_b}: 16 bytes, the size of
+// an fp64 point): two fp32 transforms go through one set of passes -- one set of addresses, barriers and LDS instructions,
+// and ONE copy of the twiddles, which stay plain float2 and apply to both halves.  Per half the arithmetic is the float2
+// instantiation's, operation for operation.  CxT<Cx>::T is the twiddles' scalar type and CxT<Cx>::W their point type.
+struct fp2 { float a, b; };
+struct __attribute__((aligned(16))) cf2 { fp2 x, y; };
 template <typename Cx> struct CxT;
-template <> struct CxT<double2> { typedef double R; };
-template <> struct CxT<float2> { typedef float R; };
+template <> struct CxT<double2> { typedef double R; typedef double T; typedef double2 W; };
+template <> struct CxT<float2> { typedef float R; typedef float T; typedef float2 W; };
+template <> struct CxT<cf2> { typedef fp2 R; typedef float T; typedef float2 W; };
 template <typename Cx> GF3_DEV Cx cx(typename CxT<Cx>::R a, typename CxT<Cx>::R b);
 template <> GF3_DEV double2 cx<double2>(double a, double b) { return make_double2(a, b); }
 template <> GF3_DEV float2 cx<float2>(float a, float b) { return make_float2(a, b); }
@@ -43,6 +50,22 @@ GF3_DEV float2 cscale(float2 a, float s) { return make_float2(a.x * s, a.y * s);
 GF3_DEV float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 GF3_DEV float2 cmul_conj(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
 GF3_DEV float2 mul_negi(float2 a) { return make_float2(a.y, -a.x); }
+GF3_DEV fp2 operator+(fp2 p, fp2 q) { return fp2{p.a + q.a, p.b + q.b}; }
+GF3_DEV fp2 operator-(fp2 p, fp2 q) { return fp2{p.a - q.a, p.b - q.b}; }
+GF3_DEV fp2 operator-(fp2 p) { return fp2{-p.a, -p.b}; }
+GF3_DEV fp2 fma(float s, fp2 p, fp2 q) { return fp2{fmaf(s, p.a, q.a), fmaf(s, p.b, q.b)}; }
+template <> GF3_DEV cf2 cx<cf2>(fp2 a, fp2 b) { return cf2{a, b}; }
+// one half of a pair as a plain point, and a pair from two points
+GF3_DEV float2 half_a(cf2 v) { return make_float2(v.x.a, v.y.a); }
+GF3_DEV float2 half_b(cf2 v) { return make_float2(v.x.b, v.y.b); }
+GF3_DEV cf2 pair_of(float2 a, float2 b) { return cf2{fp2{a.x, b.x}, fp2{a.y, b.y}}; }
+GF3_DEV cf2 cadd(cf2 a, cf2 b) { return cf2{a.x + b.x, a.y + b.y}; }
+GF3_DEV cf2 csub(cf2 a, cf2 b) { return cf2{a.x - b.x, a.y - b.y}; }
+GF3_DEV cf2 cconj(cf2 a) { return cf2{a.x, -a.y}; }
+GF3_DEV cf2 mul_negi(cf2 a) { return cf2{a.y, -a.x}; }
+GF3_DEV cf2 cscale(cf2 a, float s) { return pair_of(cscale(half_a(a), s), cscale(half_b(a), s)); }
+GF3_DEV cf2 cmul(cf2 a, float2 w) { return pair_of(cmul(half_a(a), w), cmul(half_b(a), w)); }
+GF3_DEV cf2 cmul_conj(cf2 a, float2 w) { return pair_of(cmul_conj(half_a(a), w), cmul_conj(half_b(a), w)); }
 
 // complex division the way NumPy does it for complex128 (Smith's method)
 GF3_DEV cplx cdiv_np(cplx a, cplx b) {
@@ -131,7 +154,8 @@ GF3_DEV double load_sample(const void* p, int64_t i, int dt) {
 template <typename Cx> GF3_DEV void bfly8(Cx* v) {
     typedef Cx cplx;
     typedef typename CxT<Cx>::R R;
-    constexpr R S = (R)GF3_SQRT1_2;
+    typedef typename CxT<Cx>::T T;
+    constexpr T S = (T)GF3_SQRT1_2;
     const cplx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]);
     const cplx a2 = cadd(v[2], v[6]), a3 = mul_negi(csub(v[2], v[6]));
     const cplx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]);
@@ -165,25 +189,30 @@ GF3_DEV float2 cfma(float2 a, float2 w, float2 c) {
     return make_float2(fmaf(a.x, w.x, fmaf(-a.y, w.y, c.x)), fmaf(a.x, w.y, fmaf(a.y, w.x, c.y)));
 }
 GF3_DEV float2 twice_minus(float2 u, float2 s) { return make_float2(fmaf(2.0f, u.x, -s.x), fmaf(2.0f, u.y, -s.y)); }
-template <typename Cx> GF3_DEV void bfly4_tw(Cx* v, Cx w) {   // v[r] *= w^r, then the radix-4 butterfly
+GF3_DEV cf2 cfma(cf2 a, float2 w, cf2 c) { return pair_of(cfma(half_a(a), w, half_a(c)), cfma(half_b(a), w, half_b(c))); }
+GF3_DEV cf2 twice_minus(cf2 u, cf2 s) { return pair_of(twice_minus(half_a(u), half_a(s)), twice_minus(half_b(u), half_b(s))); }
+template <typename Cx> GF3_DEV void bfly4_tw(Cx* v, typename CxT<Cx>::W w) {   // v[r] *= w^r, then the radix-4 butterfly
     typedef Cx cplx;
-    typedef typename CxT<Cx>::R R;
-    const R c2 = w.x + w.x;
-    const cplx w2 = cx<Cx>(fma(c2, w.x, (R)-1.0), c2 * w.y);
-    const cplx w3 = tw_next(c2, w2, w);
+    typedef typename CxT<Cx>::T T;
+    typedef typename CxT<Cx>::W W;
+    const T c2 = w.x + w.x;
+    const W w2 = cx<W>(fma(c2, w.x, (T)-1.0), c2 * w.y);
+    const W w3 = tw_next(c2, w2, w);
     const cplx s0 = cfma(v[2], w2, v[0]), s1 = twice_minus(v[0], s0);
     const cplx u1 = cmul(v[1], w);
     const cplx s2 = cfma(v[3], w3, u1), s3 = mul_negi(twice_minus(u1, s2));
     v[0] = cadd(s0, s2); v[1] = cadd(s1, s3); v[2] = csub(s0, s2); v[3] = csub(s1, s3);
 }
-template <typename Cx> GF3_DEV void bfly8_tw(Cx* v, Cx w) {   // v[r] *= w^r, then the radix-8 butterfly
+template <typename Cx> GF3_DEV void bfly8_tw(Cx* v, typename CxT<Cx>::W w) {   // v[r] *= w^r, then the radix-8 butterfly
     typedef Cx cplx;
     typedef typename CxT<Cx>::R R;
-    constexpr R S = (R)GF3_SQRT1_2;
-    const R c2 = w.x + w.x;
-    const cplx w2 = cx<Cx>(fma(c2, w.x, (R)-1.0), c2 * w.y);
-    const cplx w3 = tw_next(c2, w2, w), w4 = tw_next(c2, w3, w2), w5 = tw_next(c2, w4, w3);
-    const cplx w6 = tw_next(c2, w5, w4), w7 = tw_next(c2, w6, w5);
+    typedef typename CxT<Cx>::T T;
+    typedef typename CxT<Cx>::W W;
+    constexpr T S = (T)GF3_SQRT1_2;
+    const T c2 = w.x + w.x;
+    const W w2 = cx<W>(fma(c2, w.x, (T)-1.0), c2 * w.y);
+    const W w3 = tw_next(c2, w2, w), w4 = tw_next(c2, w3, w2), w5 = tw_next(c2, w4, w3);
+    const W w6 = tw_next(c2, w5, w4), w7 = tw_next(c2, w6, w5);
     const cplx a0 = cfma(v[4], w4, v[0]), a1 = twice_minus(v[0], a0);
     const cplx u2 = cmul(v[2], w2);
     const cplx a2 = cfma(v[6], w6, u2), a3 = mul_negi(twice_minus(u2, a2));
@@ -202,7 +231,7 @@ template <typename Cx> GF3_DEV void bfly8_tw(Cx* v, Cx w) {   // v[r] *= w^r, th
     v[3] = cx<Cx>(fma(S, m3, b3.x), fma(-S, p3, b3.y));
     v[7] = cx<Cx>(fma(-S, m3, b3.x), fma(S, p3, b3.y));
 }
-template <int R, typename Cx> GF3_DEV void bfly_tw(Cx* v, Cx w) { if constexpr (R == 8) bfly8_tw(v, w); else bfly4_tw(v, w); }
+template <int R, typename Cx> GF3_DEV void bfly_tw(Cx* v, typename CxT<Cx>::W w) { if constexpr (R == 8) bfly8_tw(v, w); else bfly4_tw(v, w); }
 
 // ---------------------------------------------------------------- LDS FFT
 // LDS footprint of one FFT buffer, in cplx elements (first exchange is padded
@@ -234,7 +263,7 @@ template <int NC, typename Cx = cplx> struct FftTw {
 };
 
 template <int NC, int R, int NS, typename Cx>
-GF3_DEV void fft_pass(Cx (&v)[8], const Cx* src, Cx* dst, Cx wbase, Cx wstep, int tid) {
+GF3_DEV void fft_pass(Cx (&v)[8], const Cx* src, Cx* dst, typename CxT<Cx>::W wbase, typename CxT<Cx>::W wstep, int tid) {
     typedef Cx cplx;
     constexpr int T = NC / 8, NB = 8 / R;
 #pragma unroll
@@ -248,7 +277,7 @@ GF3_DEV void fft_pass(Cx (&v)[8], const Cx* src, Cx* dst, Cx wbase, Cx wstep, in
     for (int b = 0; b < NB; ++b) {
         const int j = tid + b * T;
         const int k = j & (NS - 1);
-        cplx w = wbase;
+        typename CxT<Cx>::W w = wbase;
         if (b == 1 && NS > T) w = cmul(wbase, wstep);      // k advances by T for the second butterfly
         bfly_tw<R>(&v[b * R], w);
         const int base = (j - k) * R + k;
@@ -308,12 +337,12 @@ template <int NC> struct Spec {
 // TWICE = true returns 2 X[k], 2 X[N/2-k]: the two halvings are dropped (four multiplies per pair); callers whose
 // results are ratios or signs of spectra fold the factor of two -- exact in binary -- into a constant they apply anyway.
 template <bool TWICE = false, typename Cx>
-GF3_DEV void real_split(Cx A, Cx Bm, Cx w, Cx& Xk, Cx& Xm) {
+GF3_DEV void real_split(Cx A, Cx Bm, typename CxT<Cx>::W w, Cx& Xk, Cx& Xm) {
     typedef Cx cplx;
-    typedef typename CxT<Cx>::R R;
+    typedef typename CxT<Cx>::T T;
     const cplx B = cconj(Bm);
-    const cplx E = TWICE ? cadd(A, B) : cscale(cadd(A, B), (R)0.5);
-    const cplx D = TWICE ? csub(A, B) : cscale(csub(A, B), (R)0.5);
+    const cplx E = TWICE ? cadd(A, B) : cscale(cadd(A, B), (T)0.5);
+    const cplx D = TWICE ? csub(A, B) : cscale(csub(A, B), (T)0.5);
     Xk = cfma(mul_negi(D), w, E);                    // E + O,  O = -i D w
     Xm = cconj(twice_minus(E, Xk));                  // conj(E - O) = conj(2E - Xk)
 }
@@ -322,10 +351,11 @@ GF3_DEV void real_split(Cx A, Cx Bm, Cx w, Cx& Xk, Cx& Xm) {
 // (fused sizes).  `flip` selects which ping-pong buffer the first exchange uses; the caller
 // alternates it per transform.  Returns the buffer that holds the result.
 template <int NC, bool ALL, bool PP = FftGeom<NC>::PINGPONG, typename Cx>
-GF3_DEV Cx* fft_passes(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, int tid, int flip) {
+GF3_DEV Cx* fft_passes(Cx (&v)[8], Cx* lds, const FftTw<NC, typename CxT<Cx>::W>& ft, int tid, int flip) {
     typedef Cx cplx;
+    typedef typename CxT<Cx>::W W;
     constexpr int T = NC / 8;
-    const cplx w8 = cx<Cx>(GF3_SQRT1_2, -GF3_SQRT1_2);             // exp(-i pi/4): T steps of the last pass
+    const W w8 = cx<W>(GF3_SQRT1_2, -GF3_SQRT1_2);                 // exp(-i pi/4): T steps of the last pass
     cplx* A = PP ? lds + (flip ? NC : 0) : lds;
     cplx* B = PP ? lds + (flip ? 0 : NC) : lds;
     bfly8(v);
@@ -377,7 +407,7 @@ GF3_DEV Cx* fft_passes(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, int tid, in
 // Ping-pong sizes: the caller must have a barrier between the last reads of both buffers by a
 // previous user and this call (this entry point is only used after such a barrier).
 template <int NC, bool PP = FftGeom<NC>::PINGPONG, typename Cx>
-GF3_DEV Cx* fft_core(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, int tid) {
+GF3_DEV Cx* fft_core(Cx (&v)[8], Cx* lds, const FftTw<NC, typename CxT<Cx>::W>& ft, int tid) {
     return fft_passes<NC, true, PP>(v, lds, ft, tid, 0);
 }
 
@@ -398,8 +428,11 @@ template <int NC, typename Cx> GF3_DEV void FftTw<NC, Cx>::init(int tid, const C
 // `flip` must alternate between consecutive calls in a workgroup (ping-pong hazard: the last
 // pass of call i reads buffer A_i with no barrier after it; call i+1 starts by storing into the
 // other buffer, which every wave finished reading before call i's final barrier).
+// Cx = cf2 transforms two symbols at once (the twiddles ft, wb are float2: one copy for both halves); its points are
+// 16 bytes, so it takes the buffers of an fp64 transform, and consecutive calls must be of ONE point size: a float2
+// transform's two buffers lie inside one of a cf2 transform's, which the rule above does not cover.
 template <int NC, bool PP = FftGeom<NC>::PINGPONG, bool TWICE = false, typename Cx>
-GF3_DEV void rfft_regs(Cx (&v)[8], Cx* lds, const FftTw<NC, Cx>& ft, Cx wb, int t, Cx& z0, int flip) {
+GF3_DEV void rfft_regs(Cx (&v)[8], Cx* lds, const FftTw<NC, typename CxT<Cx>::W>& ft, typename CxT<Cx>::W wb, int t, Cx& z0, int flip) {
     typedef Cx cplx;
     if constexpr (Spec<NC>::FUSED) {
         constexpr int Q = NC / 4;

@@ -267,6 +267,16 @@ class Engine:
         self._check(self.lib.gf3_debug_rfft_sp_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
         return out
 
+    def debug_rfft32_pair_batch(self, x, offsets):
+        """debug_rfft32_batch through the transform the screened demodulation runs: symbols 2w, 2w + 1 as the two halves of
+        one pair transform (tests); same output."""
+        x = self._samples(x)
+        offsets = self._dev(offsets, torch.int64)
+        n = offsets.numel()
+        out = self._new((n, self.cfg.N // 2 + 1), torch.complex64)
+        self._check(self.lib.gf3_debug_rfft_sp_pair_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
+        return out
+
     def debug_demod_screen(self, x, frame_offsets):
         """The fp32 screening pass of the QPSK demodulation alone (tests): dict(bits: the screen's own rows, ep32 [F, D, C]
         complex64 -- the rotated fp32 symbols 2 X conj(g) of the data carriers --, E [F, D] float32 -- the bound on

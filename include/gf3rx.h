@@ -207,6 +207,11 @@ int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx *ctx, int64_t F);
  * gives them in fp64.  f32 / i16 / u8 samples only. */
 int gf3_debug_rfft_sp_batch(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_offsets, int64_t n_sym,
                            void *d_out_c64, void *stream);
+/* tests: the same of the instantiation the screened demodulation runs since it transforms two data symbols at a time:
+ * workgroup w takes symbols 2w and 2w + 1 as the halves of one pair transform (an odd n_sym: the last pair's second half is
+ * absent); output as above. */
+int gf3_debug_rfft_sp_pair_batch(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_offsets, int64_t n_sym,
+                                void *d_out_c64, void *stream);
 int gf3_debug_demod_screen(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
                            uint8_t *d_bits_packed, void *d_ep32, float *d_E, int32_t *d_cls, void *d_list, void *stream);
 
