@@ -137,6 +137,21 @@ class CamG:
         # symbol [packets, 2P + D] in `last_blanked` and (baseline, level) [packets, 2] in `last_sample_level`; both are
         # None otherwise.  It cannot see a click under the threshold, does not treat the chirp, and blanks a handful of
         # samples of a clean packet too: opt-in.  NotImplementedError on the piece-wise host path.
+        # "QCLDPC-*", staged path: decoder_feedback = n > 0 lets receive() decode up to n more times.  The codewords that
+        # decoded (and, under codeword_crc, whose CRC matches) are re-encoded; the residual channel measured on their symbols,
+        # smoothed over +-feedback_window[0] symbols x +-feedback_window[1] bins wherever at least feedback_min_known known
+        # symbols lie in the window, is divided out of the packet's equalised symbols (Engine.feedback_equalise); the weights
+        # are formed again and the codewords still untrusted are decoded again: the recovered region grows from the pilot
+        # blocks towards the middle of a packet whose channel moved, per carrier, in amplitude and phase.  It needs trusted
+        # codewords NEXT to the failed ones: under `interleave` every codeword of a packet sees the same statistics, they
+        # pass or fail together, and feedback helps only near the threshold.  A miscorrected codeword feeds it wrong
+        # reference symbols: use it with codeword_crc.  Each pass costs one small read-back; a receive whose first decode
+        # trusts every codeword launches nothing more.  `last_decode_report` then also holds "feedback_passes" and
+        # "feedback_recovered" (codewords the extra passes came to trust).  ValueError with fused_llr and on the other
+        # encodings.
+        self.decoder_feedback = 0
+        self.feedback_window = (2, 8)
+        self.feedback_min_known = 4
         self.impulse_blanking = False
         self.blanking_threshold = 4.5
         self.blanking_guard = 8
@@ -183,7 +198,8 @@ class CamG:
         return CodedChain(self.encoding, self.ldpc_n, self.ldpc_max_iter, self.llr_weighting, self.interleave, self.fused_llr,
                           self.outer_code, per_packet=self.packet_length * self.data_bits_per_symbol,
                           make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc),
-                          phase_tracking=bool(self.phase_tracking))
+                          phase_tracking=bool(self.phase_tracking), decoder_feedback=self.decoder_feedback,
+                          feedback_window=self.feedback_window, feedback_min_known=self.feedback_min_known)
 
     def _qcldpc_rate(self):
         """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
@@ -491,8 +507,13 @@ class receiver(transmitter):
         # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
         need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
         if rate is not None:
-            llr, snr = chain.llrs(eng, o, self._tables()[0])
-            bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
+            feedback = None
+            if chain.decoder_feedback:
+                bits_t, need["iters"], need["status"], bad, snr, feedback = chain.decode_feedback(
+                    eng, chain.code(rate, eng.device), o, self._tables()[0])
+            else:
+                llr, snr = chain.llrs(eng, o, self._tables()[0])
+                bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
             if bad is not None:                                 # (codeword_crc: the flags ride in the same copy)
                 need["crc_bad"] = bad
         else:
@@ -511,6 +532,8 @@ class receiver(transmitter):
             setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
         if rate is not None:
             self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
+            if feedback is not None:                            # (under decoder_feedback only)
+                self.last_decode_report.update(feedback)
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())

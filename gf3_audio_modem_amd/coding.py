@@ -67,6 +67,9 @@ class CodedChain:
     make_code: object                       # (rate, device[, Z=Z]) -> QCLDPC: the façade's `_qcldpc_code`
     codeword_crc: bool = False              # the last 32 message bits of every codeword are the CRC of the others (crc.py)
     phase_tracking: bool = False            # receive(): Engine.track_phase on the equalised symbols, before the weights
+    decoder_feedback: int = 0               # receive(): extra decoding passes at most, each re-equalised from the trusted codewords
+    feedback_window: tuple = (2, 8)         # (half_symbols, half_bins) of Engine.feedback_equalise
+    feedback_min_known: int = 4             # known symbols a window needs before its gain is used
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
@@ -119,7 +122,28 @@ class CodedChain:
         if fused and self.phase_tracking:
             raise ValueError("phase_tracking needs fused_llr = False: the fused kernel never materialises the equalised "
                              "symbols the tracker works on")
+        self.feedback()
+        if self.decoder_feedback and rate is None:
+            raise ValueError(f"decoder_feedback needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
+        if self.decoder_feedback and fused:
+            raise ValueError("decoder_feedback needs fused_llr = False: the fused kernel never materialises the equalised "
+                             "symbols the feedback corrects")
         return rate, fused
+
+    def feedback(self):
+        """(passes, half_symbols, half_bins, min_known) of the decoder feedback; ValueError for a count that is not an
+        integer >= 0 and, with a count > 0, for a window outside the ranges of Engine.feedback_equalise."""
+        n = self.decoder_feedback
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"decoder_feedback must be an integer >= 0 (the extra passes at most), not {n!r}")
+        if not n:
+            return 0, 0, 0, 1
+        from .engine import Engine
+        try:
+            hs, hb = self.feedback_window
+        except (TypeError, ValueError):
+            raise ValueError(f"feedback_window must be (half_symbols, half_bins), not {self.feedback_window!r}")
+        return (int(n),) + Engine.check_feedback_window(hs, hb, self.feedback_min_known)
 
     # ---- transmit side ---------------------------------------------------------------------------------------------------
     def encode(self, bits, rate):
@@ -156,11 +180,23 @@ class CodedChain:
         """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: rows for the host}: the SNR in dB
         of the noise weightings, 10 log10(Es / v') with the demapper's floor, `last_snr_db` [F, C], `last_symbol_snr_db`
         [F, D]; the tracker's `last_phase_track` [F, D, 2] and `last_phase_measured` [F, D] under `phase_tracking`)."""
-        snr = {}
+        o, rows = self.track(eng, o)
+        llr, snr = self.weigh(eng, o, points)
+        rows.update(snr)
+        return llr, rows
+
+    def track(self, eng, o):
+        """The tracker's part of `llrs`: -> (the outputs with the tracked symbols under `phase_tracking`, its rows)."""
+        rows = {}
         if self.phase_tracking:
             # (a copy: the plots keep the untracked symbols)  `last_phase_track` [F, D, 2], `last_phase_measured` [F, D]
             o = dict(o)
-            o["eq"], snr["last_phase_track"], snr["last_phase_measured"] = eng.track_phase(o["eq"], want_track=True)
+            o["eq"], rows["last_phase_track"], rows["last_phase_measured"] = eng.track_phase(o["eq"], want_track=True)
+        return o, rows
+
+    def weigh(self, eng, o, points):
+        """The weights' part of `llrs`, on o["eq"] as it is: -> (LLRs in coded order, the SNR rows)."""
+        snr = {}
         if self.llr_weighting == "csi":
             llr = o["llr"] if "llr" in o else eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
         else:
@@ -194,17 +230,76 @@ class CodedChain:
         (no statuses without one).  `codeword_crc`: the CRC of every codeword is checked in between, the message bits are
         the payloads, and the outer code also rewrites the members that converged on something whose CRC does not match;
         the iteration counts returned are the decoder's own."""
-        n_cw = llr.numel() // code.n
-        dec, iters = code.decode(llr[: n_cw * code.n], max_iter=self.ldpc_max_iter, want_iters=True)
-        bad, erase = None, iters
-        if self.codeword_crc:
-            dec, bad, erase = CodewordCRC(code.k, dec.device).check(dec, iters.clone())
+        _, dec, iters, bad, erase = self.inner(code, llr[: llr.numel() // code.n * code.n])
+        return self.outer_recover(dec, iters, bad, erase, llr.numel())
+
+    def inner(self, code, llr):
+        """Whole codewords' LLRs -> (the decoder's message rows [n_cw, code.k], the message bits they carry (the payloads
+        under `codeword_crc`, else the rows themselves), iters, CRC flags or None, the counts the outer code erases by)."""
+        full, iters = code.decode(llr, max_iter=self.ldpc_max_iter, want_iters=True)
+        if not self.codeword_crc:
+            return full, full, iters, None, iters
+        dec, bad, erase = CodewordCRC(code.k, full.device).check(full, iters.clone())
+        return full, dec, iters, bad, erase
+
+    def outer_recover(self, dec, iters, bad, erase, n_llr):
+        """`decode`'s second half: the outer code on the inner decoder's results for n_llr LLRs."""
         gr = self.outer()
         if gr is None:
             return dec.reshape(-1), iters, torch.empty(0, dtype=torch.int32, device=dec.device), bad
-        if llr.numel() % self.per_packet:
+        if n_llr % self.per_packet:
             raise ValueError("outer_code: need whole packets of packet_length * data_bits_per_symbol bits")
-        NG = self.outer_layout(llr.numel() // self.per_packet)[1]
+        NG = self.outer_layout(n_llr // self.per_packet)[1]
         rows = NG * sum(gr)
         fixed, status = OuterRS(*gr, dec.shape[1], dec.device).recover(dec[:rows], erase[:rows])
         return from_transmitted(fixed, NG, gr[0]).reshape(-1), iters, status, bad
+
+    def decode_feedback(self, eng, code, o, points):
+        """receive() under `decoder_feedback`: tracker, weights and the first decode as without it; then up to
+        `decoder_feedback` passes, each of which re-encodes the TRUSTED codewords (converged, and under `codeword_crc` with
+        a matching CRC; their message rows are frozen from then on; every row goes through the encoder, the untrusted
+        ones zeroed and masked rather than compacted), lays their coded bits and a per-bit mask out over the packets in
+        transmitted order, has Engine.feedback_equalise measure the residual channel on those symbols of the
+        ORIGINAL tracked `eq` and divide it out, weighs the result again and decodes the untrusted codewords alone.
+        Passes are not cumulative (each starts from the same `eq` with more known symbols).  The loop ends when nothing
+        is untrusted or a pass trusts nothing new; every pass, and the first decode, costs one small read-back (the
+        numbers of the untrusted codewords).  The outer code then sees the final bits and erasures.
+        -> (message bits, iters, group statuses, CRC flags or None, the host rows of `llrs`, {"feedback_passes",
+        "feedback_recovered"})."""
+        passes, hs, hb, min_known = self.feedback()
+        o, rows = self.track(eng, o)
+        llr, snr = self.weigh(eng, o, points)
+        n_llr = llr.numel()
+        n_cw = n_llr // code.n
+        full, dec, iters, bad, erase = self.inner(code, llr[: n_cw * code.n])
+        F = n_llr // self.per_packet
+        first = None
+        done = 0
+        while True:
+            untrusted = torch.nonzero(erase <= 0).reshape(-1)   # (the read-back: a codeword is trusted once erase > 0)
+            left = int(untrusted.numel())
+            first = left if first is None else first
+            if done and left == last:
+                break
+            last = left
+            if done == passes or left == 0:
+                break
+            trusted = (erase > 0).to(torch.uint8)
+            planes = []
+            for rows_u8 in (code.encode(full * trusted[:, None]), trusted[:, None].expand(n_cw, code.n)):
+                plane = torch.zeros((F, self.per_packet), dtype=torch.uint8, device=full.device)
+                plane.view(-1)[: n_cw * code.n] = rows_u8.reshape(-1)
+                planes.append(eng.interleave(plane, inverse=False) if self.interleave else plane)
+            fb = dict(o)
+            fb["eq"] = eng.feedback_equalise(o["eq"], planes[0], planes[1], hs, hb, min_known)
+            llr, snr = self.weigh(eng, fb, points)
+            sub = llr[: n_cw * code.n].reshape(n_cw, code.n)[untrusted]
+            full_u, dec_u, iters_u, bad_u, erase_u = self.inner(code, sub)
+            full[untrusted] = full_u
+            iters[untrusted] = iters_u
+            if self.codeword_crc:
+                dec[untrusted], bad[untrusted], erase[untrusted] = dec_u, bad_u, erase_u
+            done += 1
+        rows.update(snr)
+        bits, iters, status, bad = self.outer_recover(dec, iters, bad, erase, n_llr)
+        return bits, iters, status, bad, rows, {"feedback_passes": done, "feedback_recovered": first - last}

@@ -274,6 +274,13 @@ extern "C" int gf3_ctx_create(const gf3_config* cfg, gf3_ctx** out) {
         for (int b : bins) sum += b;
         c->bin_mean = (double)sum / (double)cfg->C;
         CK(dev_new(c->owned, &c->d_bins, bins));
+        // the carriers in ascending bin order (bins are distinct): gf3_feedback_equalise's bin window is a range of it
+        std::vector<int> order(cfg->C), sorted(cfg->C);
+        for (int i = 0; i < cfg->C; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return bins[x] < bins[y]; });
+        for (int i = 0; i < cfg->C; ++i) sorted[i] = bins[order[i]];
+        CK(dev_new(c->owned, &c->d_bin_order, order));
+        CK(dev_new(c->owned, &c->d_bins_sorted, sorted));
     }
     std::vector<int> inv(1 << cfg->mu, 0);
     for (int m = cfg->M - 1; m >= 0; --m) inv[clab[m]] = m;

@@ -17,6 +17,7 @@
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
 //                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
+//   gf3rx_feedback.hip       feedback_kernel + gf3_feedback_equalise (residual channel from re-encoded codewords, divided out)
 //   gf3rx_blank.hip          blank_stats_kernel, blank_level_kernel, blank_write_kernel + gf3_blank_impulses (impulse blanking of the samples)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
@@ -29,6 +30,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <thread>
@@ -201,6 +203,8 @@ struct gf3_ctx {
     int *d_pos = nullptr, *d_clab = nullptr;
     int* d_bins = nullptr;              // [C] data_bins as given (1-based FFT bins in output order): gf3_track_phase's carrier offsets
     double bin_mean = 0.0;              // their mean
+    int* d_bin_order = nullptr;         // [C] carrier index at each position of the ascending-bin order (gf3_feedback_equalise)
+    int* d_bins_sorted = nullptr;       // [C] data_bins[d_bin_order[p]]
     double *d_cre = nullptr, *d_cim = nullptr;
     CorrPlan frames_plan, stream_plan;
     double qpsk_q = 0.0;

@@ -583,6 +583,47 @@ class Engine:
         return (out, phase, measured) if want_track else out
 
     @staticmethod
+    def check_feedback_window(half_symbols, half_bins, min_known):
+        """ValueError unless half_symbols is an integer in [0, 8], half_bins one in [0, 64] and min_known one >= 1 (the
+        ranges of gf3_feedback_equalise) -> the three as ints."""
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not integer(half_symbols) or not 0 <= int(half_symbols) <= 8:
+            raise ValueError(f"feedback window: half_symbols must be an integer in [0, 8], not {half_symbols!r}")
+        if not integer(half_bins) or not 0 <= int(half_bins) <= 64:
+            raise ValueError(f"feedback window: half_bins must be an integer in [0, 64], not {half_bins!r}")
+        if not integer(min_known) or int(min_known) < 1 or int(min_known) > 0x7fffffff:
+            raise ValueError(f"feedback: min_known must be an integer >= 1, not {min_known!r}")
+        return int(half_symbols), int(half_bins), int(min_known)
+
+    def feedback_equalise(self, eq, bits, known, half_symbols=2, half_bins=8, min_known=4, out=None, want_gain=False):
+        """Decoder feedback (gf3_feedback_equalise): the residual channel g measured on the KNOWN symbols of eq [F*D, C] --
+        those whose mu bytes of `known` are all non-zero, whose value is finite and whose mu `bits` are a label of the
+        table -- as sum(eq conj(s)) / sum(|s|^2) over the known symbols within half_symbols symbols and half_bins BINS of
+        each symbol (same packet), 1 where fewer than min_known are; out = eq / g.  bits, known: uint8 with F*D*C*mu
+        elements, in transmitted order (packet -> symbol -> carrier -> bit: the order of soft_demap_csi's LLRs).  out:
+        optional contiguous complex128 tensor of F*D*C elements, NOT eq itself.  -> out, or with want_gain (out, g
+        complex128 [F*D, C]).  Fixed summation order: two calls give identical bytes."""
+        hs, hb, mk = self.check_feedback_window(half_symbols, half_bins, min_known)
+        eq, F = self._eq_packets(eq, "feedback_equalise")
+        cfg = self.cfg
+        planes = []
+        for name, x in (("bits", bits), ("known", known)):
+            x = torch.as_tensor(x)
+            if x.dtype != torch.uint8 or x.numel() != eq.numel() * cfg.mu:
+                raise ValueError(f"feedback_equalise: {name} must be uint8 with F*D*C*mu = {eq.numel() * cfg.mu} elements")
+            planes.append(x.to(self.device).contiguous())
+        out = self._out(out, (F * cfg.D, cfg.C), torch.complex128, "F*D*C")
+        if F and out.data_ptr() == eq.data_ptr():
+            raise ValueError("feedback_equalise: out must not be eq (a symbol's neighbours are still being read)")
+        gain = self._new((F * cfg.D, cfg.C), torch.complex128) if want_gain else None
+        ws = int(self.lib.gf3_feedback_workspace_bytes(self._h, F))
+        work = self._new((ws,), torch.uint8) if ws else None
+        self._check(self.lib.gf3_feedback_equalise(self._h, _ptr(eq), _ptr(planes[0]), _ptr(planes[1]), F, hs, hb, mk, _ptr(out),
+                                                   _ptr(gain), _ptr(work), ws, self._stream()))
+        return (out, gain) if want_gain else out
+
+    @staticmethod
     def check_blanking(threshold, guard):
         """ValueError for a blanking threshold that is not a finite number > 0 or a guard that is not an integer in [0, 64]."""
         try:

@@ -532,6 +532,35 @@ int gf3_track_phase(gf3_ctx *ctx, const void *d_eq_c128, int64_t F, void *d_out_
                     uint8_t *d_measured_or_null, void *stream);
 
 /*
+ * Decoder feedback: re-equalise from decoded codewords (not in the reference).  Opt-in; a stage of its own on the
+ * equalised symbols (after gf3_track_phase where that runs), before any of the weights above.  The symbols of codewords
+ * that decoded and can be trusted are known; the residual channel measured on them is smoothed over a small time x
+ * frequency window and divided out of every symbol of the packet, the unknown ones included.  Per packet f, with
+ * eq [F*D, C] as gf3_demod_frames returns it:
+ *   d_bits_u8, d_known_u8 [F, D C mu]: one byte per coded bit (non-zero = 1) and per-bit mask, in TRANSMITTED order, packet ->
+ *     symbol -> carrier -> bit: the order of gf3_soft_demap_csi's LLRs, before the interleaver is undone.
+ *   symbol (l, c) is known <=> all mu of its known bytes are non-zero, both parts of eq[l, c] are finite and some table
+ *     entry's label equals its mu bits; s[l, c] is then the first such entry in table order.
+ *   r = eq conj(s), q = |s|^2 on known symbols, both 0 elsewhere.
+ *   W(l, c) = the (l', c') of the same packet with |l' - l| <= half_symbols and |k_c' - k_c| <= half_bins, k_c =
+ *     data_bins[c]: distance in BINS, whatever the order of the carriers.
+ *   A = sum over W of r, B = sum over W of q, n = the known symbols in W: fp64 direct sums (no running add / subtract).
+ *   g[l, c] = A / B when n >= min_known and A != 0, else 1;   out[l, c] = eq[l, c] / g[l, c]  (out = eq bit for bit where
+ *     g = 1; non-finite inputs stay non-finite; a symbol that is itself unknown is corrected from its neighbours).
+ *   0 <= half_symbols <= 8, 0 <= half_bins <= 64, min_known >= 1, C <= 4096.
+ *   d_eq_c128, d_out_c128, d_gain_c128 (optional: g) [F*D, C]; d_out must not be d_eq (neighbours are still being read).
+ *   GF3_EINVAL for null pointers, F < 0, arguments out of range, d_out == d_eq, work_bytes below
+ *   gf3_feedback_workspace_bytes (which is 0: d_work may be null).  F == 0 is a no-op.  No allocation, no host
+ *   synchronisation, asynchronous on `stream`.  One launch: a workgroup owns 8 symbols x 128 carriers in ascending-bin
+ *   order, sums each column over the symbols (rows ascending), then the columns of a carrier's bin window (bins
+ *   ascending) from LDS: a fixed order, no atomics -- two calls give identical bytes.
+ */
+int gf3_feedback_equalise(gf3_ctx *ctx, const void *d_eq_c128, const uint8_t *d_bits_u8, const uint8_t *d_known_u8,
+                          int64_t F, int32_t half_symbols, int32_t half_bins, int32_t min_known,
+                          void *d_out_c128, void *d_gain_c128_or_null, void *d_work, int64_t work_bytes, void *stream);
+int64_t gf3_feedback_workspace_bytes(const gf3_ctx *ctx, int64_t F);
+
+/*
  * Impulse blanking in the sample domain, between sync and demodulation (not in the reference).  Opt-in.  A click of a few
  * milliseconds otherwise costs the whole OFDM symbol it falls into; here the few samples that stand far above the packet's
  * own level are replaced by the baseline, and the symbol survives with a little less energy.
