@@ -1,7 +1,9 @@
 // demod_kernel: the fused demodulation of one packet per workgroup, and the decision helpers it shares with the
 // stand-alone demappers.  A header because its four modes are compiled in four translation units
 // (gf3rx_demod_qpsk.hip, gf3rx_demod_scan.hip, gf3rx_demod_full.hip, gf3rx_demod_soft.hip) and the two-phase kernels of
-// long packets (gf3rx_demod_split.h) reuse its pieces.
+// long packets (gf3rx_demod_split.hip, gf3rx_dsplit_*.hip) and the screened form (gf3rx_demod_screen.hip) are instantiations
+// of it.  Order: decision helpers; the LDS layout; the stages that are free functions (demod_fetch, demod_startup,
+// demod_pack_words); the kernel.
 #pragma once
 #include "gf3rx_host.h"
 #include "gf3rx_demap.h"
@@ -128,6 +130,8 @@ GF3_DEV void soft_llr(cplx e, const DemodArgs& a, double w, float* dst) {
         maxlog_table(e, DemapTab{a.M, a.mu, a.cre, a.cim, a.clab, a.sep}, w, dst);
     }
 }
+// sizes whose lean layout holds two FFT buffers: the transform's own ping-pong sizes, and 4096 (DemodOcc::PP_SIZE below)
+constexpr bool demod_pp_size(int NC) { return NC == 1024 || NC == 2048 || NC == 4096; }
 // Every mode runs at two waves per SIMD.  MODE_QPSK keeps the two ping-pong FFT buffers.  The table modes carry two more
 // doubles of state per carrier (the magnitude model a0 + da f_l), which do not fit the register file next to the
 // transform at two workgroups per CU; they live in LDS ([8][T] pairs, one conflict-free 16-byte read per carrier per
@@ -139,11 +143,100 @@ template <int NC, int MODE> struct DemodOcc {
     // 64 KB buffers fit beside the decision ring (148 KB of 160) -- one barrier per exchange instead of two, with no other
     // workgroup on the CU to run under a barrier.  Four passes end in the second buffer and the next transform starts in
     // the first, so the buffers need not be flipped (rfft_regs passes flip = 0 for the unfused sizes).
-    static constexpr bool PP_SIZE = FftGeom<NC>::PINGPONG || NC == 4096;
+    static constexpr bool PP_SIZE = demod_pp_size(NC);
     static constexpr bool PP = PP_SIZE && !MAG_LDS;
     static constexpr int LDS_ELEMS = PP ? 2 * NC : FftGeom<NC>::LDS_ELEMS_INPLACE;
-    static constexpr int MAG_ELEMS = MAG_LDS ? NC : 0;             // double2 (a0, da) per slot per thread: 8 * NC/8
 };
+
+// ============================================================================
+// LDS layout, stated once: the kernels take their pointers from it, the host its totals
+// ============================================================================
+// symbols in the decision-byte ring: ceil(32 / (C mu)) + 2, rounded up to a power of two
+// (>= 4: the QPSK packer reads the ring one aligned dword at a time, so ring * C must be a multiple of 4)
+// Invariant: no slot is written while a thread may still read it, and a slot is overwritten only once every word that
+// touches it is packed.  One symbol per turn (fp64 kernels): symbol l is written while demod_pack_words(l - 1) reads back
+// to slot l - 1 - ceil(32 / (C mu)) between the same barriers, hence the + 2.  demod_screen_kernel decides two symbols per
+// turn and keeps this ring: a barrier separates its packing from its decisions (see its data loop), so reads and writes
+// never share an interval and only the second half of the invariant is left, which ring >= ceil(32 / (C mu)) + 2 also covers.
+inline int demod_ring(const gf3_ctx* c) {
+    const int Bs = c->cfg.C * c->cfg.mu;
+    const int need = (32 + Bs - 1) / Bs + 2;
+    int r = 4;
+    while (r < need) r <<= 1;
+    return r;
+}
+// LDS_LEAN (MODE_QPSK): ping-pong FFT buffers where the size has them.  LDS_TABLE (the table modes): the in-place buffer
+// and NC (a0, da) pairs.  MODE_SOFT is the table layout with no decision ring (ring = 0): a symbol's LLRs are staged IN the
+// FFT buffer (demod_soft_stages).
+enum { LDS_LEAN = 0, LDS_TABLE = 1 };
+constexpr int demod_lds_kind(int mode) { return mode == MODE_QPSK ? LDS_LEAN : LDS_TABLE; }
+// [scratch 32 doubles | start-up rotation tables [2][64 + NC/64 + 1] | FFT buffer | decision bytes [ring][C], padded to 16 |
+//  (a0, da) pairs [8][T]]; offsets in bytes.  Everything from the FFT buffer on is overlaid by Hs, He of the fit range
+// ([2][fit_len] points) during the channel-estimate stage, which may need more: `total` covers it.
+// scratch: doubles [16, 32) are block_sum's (the slope fit); demod_screen_kernel keeps more there once that is done.
+struct DemodLds { size_t scratch, rtab, fft, labs, mags, total; };
+constexpr DemodLds demod_lds_layout(int NC, int kind, size_t ring_bytes, int fit_len) {
+    const bool pp = kind == LDS_LEAN && demod_pp_size(NC);
+    const size_t rtab = 32 * sizeof(double);
+    const size_t fft = rtab + (size_t)2 * (64 + NC / 64 + 1) * sizeof(cplx);
+    const size_t labs = fft + (size_t)(pp ? 2 * NC : NC + NC / 8) * sizeof(cplx);
+    const size_t mags = labs + ((ring_bytes + 15) & ~(size_t)15);
+    const size_t end = mags + (kind == LDS_LEAN ? 0 : (size_t)NC * sizeof(double2));
+    const size_t fit = fft + (size_t)2 * fit_len * sizeof(cplx);
+    return DemodLds{0, rtab, fft, labs, mags, fit > end ? fit : end};
+}
+// The totals are the ones this layout had when it was written out three times.  By hand, in bytes: head = 256 + rotation
+// tables 2 (64 + NC/64 + 1) 16 = 2592, 2848, 3360, 4384 for NC = 512 ... 4096; FFT buffer, lean: 576 x 16 = 9216 (512 has
+// no ping-pong), then 2 NC 16 = 32768, 65536, 131072; in place (NC + NC/8) 16 = 9216, 18432, 36864, 73728; pairs NC 16 =
+// 8192 ... 65536; ring bytes: C = 1, mu = 2 -> ring 32 -> 32; C = 1638, mu = 2 -> ring 4 -> 6552 -> 6560; a fit of 500
+// carriers overlays 16000 bytes, which only the lean layout of NC = 512 does not already have behind its head.
+#define GF3_LDS_IS(NC, KIND, C, RING, FIT, BYTES) static_assert(demod_lds_layout(NC, KIND, (size_t)(RING) * (C), FIT).total == BYTES, "LDS total changed")
+GF3_LDS_IS(512, LDS_LEAN, 1, 32, 0, 11840);      GF3_LDS_IS(512, LDS_LEAN, 1, 32, 500, 18592);
+GF3_LDS_IS(512, LDS_LEAN, 1638, 4, 0, 18368);    GF3_LDS_IS(512, LDS_LEAN, 1638, 4, 500, 18592);
+GF3_LDS_IS(1024, LDS_LEAN, 1, 32, 0, 35648);     GF3_LDS_IS(1024, LDS_LEAN, 1, 32, 500, 35648);
+GF3_LDS_IS(1024, LDS_LEAN, 1638, 4, 0, 42176);   GF3_LDS_IS(1024, LDS_LEAN, 1638, 4, 500, 42176);
+GF3_LDS_IS(2048, LDS_LEAN, 1, 32, 0, 68928);     GF3_LDS_IS(2048, LDS_LEAN, 1, 32, 500, 68928);
+GF3_LDS_IS(2048, LDS_LEAN, 1638, 4, 0, 75456);   GF3_LDS_IS(2048, LDS_LEAN, 1638, 4, 500, 75456);
+GF3_LDS_IS(4096, LDS_LEAN, 1, 32, 0, 135488);    GF3_LDS_IS(4096, LDS_LEAN, 1, 32, 500, 135488);
+GF3_LDS_IS(4096, LDS_LEAN, 1638, 4, 0, 142016);  GF3_LDS_IS(4096, LDS_LEAN, 1638, 4, 500, 142016);
+GF3_LDS_IS(512, LDS_TABLE, 1, 32, 0, 20032);     GF3_LDS_IS(512, LDS_TABLE, 1, 32, 500, 20032);
+GF3_LDS_IS(512, LDS_TABLE, 1638, 4, 0, 26560);   GF3_LDS_IS(512, LDS_TABLE, 1638, 4, 500, 26560);
+GF3_LDS_IS(1024, LDS_TABLE, 1, 32, 0, 37696);    GF3_LDS_IS(1024, LDS_TABLE, 1, 32, 500, 37696);
+GF3_LDS_IS(1024, LDS_TABLE, 1638, 4, 0, 44224);  GF3_LDS_IS(1024, LDS_TABLE, 1638, 4, 500, 44224);
+GF3_LDS_IS(2048, LDS_TABLE, 1, 32, 0, 73024);    GF3_LDS_IS(2048, LDS_TABLE, 1, 32, 500, 73024);
+GF3_LDS_IS(2048, LDS_TABLE, 1638, 4, 0, 79552);  GF3_LDS_IS(2048, LDS_TABLE, 1638, 4, 500, 79552);
+GF3_LDS_IS(4096, LDS_TABLE, 1, 32, 0, 143680);   GF3_LDS_IS(4096, LDS_TABLE, 1, 32, 500, 143680);
+GF3_LDS_IS(4096, LDS_TABLE, 1638, 4, 0, 150208); GF3_LDS_IS(4096, LDS_TABLE, 1638, 4, 500, 150208);
+GF3_LDS_IS(2048, LDS_TABLE, 1638, 0, 0, 72992);  // (MODE_SOFT, no ring: 3360 + 36864 + 32768)
+#undef GF3_LDS_IS
+inline size_t demod_lds_bytes(const gf3_ctx* c, bool lean = false) {
+    return demod_lds_layout(c->NC, lean ? LDS_LEAN : LDS_TABLE, (size_t)demod_ring(c) * c->cfg.C, c->fit_hi - c->fit_lo).total;
+}
+// MODE_SOFT: a symbol's LLRs are staged in the FFT buffer (NC + NC/8 points) when they fit with the alignment shift
+// (<= 3 floats) and the last vector's overhang (<= 3 more: read, never stored) -- no LDS beyond the table modes'.
+inline bool demod_soft_stages(const gf3_ctx* c) {
+    return (size_t)c->cfg.C * c->cfg.mu * sizeof(float) + 8 * sizeof(float) <= (size_t)(c->NC + c->NC / 8) * sizeof(cplx);
+}
+inline size_t demod_soft_lds_bytes(const gf3_ctx* c) { return demod_lds_layout(c->NC, LDS_TABLE, 0, c->fit_hi - c->fit_lo).total; }
+// the layout as a kernel's pointers
+struct DemodLdsPtr {
+    double* scratch; cplx* rtab;
+    cplx* fft;                // FFT buffer, DemodOcc::LDS_ELEMS points
+    uint8_t* labs;            // [ring][C] decisions, one byte each
+    // [8][T] (a0, da) of slot s of thread t (table modes), behind the decision bytes: written only after the
+    // channel-estimate stage, whose fit-range arrays may run over this region
+    double2* mags;
+};
+template <int NC, int MODE> GF3_DEV DemodLdsPtr demod_lds_ptrs(double2* smem, const DemodArgs& a) {
+    const DemodLds o = demod_lds_layout(NC, demod_lds_kind(MODE), (size_t)(unsigned)(a.ring * a.C), 0);
+    static_assert(demod_lds_layout(NC, demod_lds_kind(MODE), 0, 0).labs - demod_lds_layout(NC, demod_lds_kind(MODE), 0, 0).fft ==
+                  DemodOcc<NC, MODE>::LDS_ELEMS * sizeof(cplx), "the layout's FFT buffer is the one rfft_regs<.., DemodOcc::PP> runs in");
+    static_assert((demod_lds_kind(MODE) == LDS_TABLE) == DemodOcc<NC, MODE>::MAG_LDS, "the table layout is the one with the (a0, da) pairs");
+    char* b = (char*)smem;
+    uint8_t* labs = (uint8_t*)(b + o.labs);
+    // (the pairs are addressed from the decision bytes: their own offset is not a compile-time constant)
+    return DemodLdsPtr{(double*)(b + o.scratch), (cplx*)(b + o.rtab), (cplx*)(b + o.fft), labs, (double2*)(labs + (int)(o.mags - o.labs))};
+}
 
 // STAGE: the whole packet in one workgroup (STAGE_ALL, the batch path), or -- for long packets, few at a time -- its two
 // halves as separate launches (gf3rx_demod_split.hip): STAGE_EST stops after the channel estimate (input: the time-domain
@@ -151,10 +244,115 @@ template <int NC, int MODE> struct DemodOcc {
 // data symbols [chunk Dc, (chunk + 1) Dc) of packet blockIdx.x / nchunk.  The discarded branches vanish: STAGE_ALL is
 // the kernel it was.
 enum { STAGE_ALL = 0, STAGE_EST = 1, STAGE_DATA = 2 };
-// VAR: two forms of the one-launch QPSK kernel that serve the screened demodulation (gf3rx_dscreen.h, gf3rx_demod_screen.hip).
-// VAR_LISTED: packet = dwork[16 + blockIdx.x] for blockIdx.x < dwork[0], and nothing else differs -- the fp64 pass over the packets
-// the screen could not decide.  VAR_SCREEN (demod_screen_kernel): the data symbols' transforms, rotations and decisions
-// in fp32 under a bound; everything up to the first data symbol is the code below, unchanged.
+// ---- one symbol's raw samples into dst.  Symbol order: start pilots, end pilots, data; STAGE_EST: "symbol" i = side i's pilot sum
+template <int NC, int DT, int STAGE> GF3_DEV void demod_fetch(const DemodArgs& a, int64_t f, int64_t off, int tid, int i, RawPair<DT> (&dst)[8]) {
+    typedef typename RawT<DT>::E E;
+    const int P = a.P;
+    const int pos = i < P ? i : (i < 2 * P ? a.D + i : i - P);           // position in the packet
+    const E* base = (const E*)a.in + (off + (int64_t)pos * a.S + a.CP);               // wave-uniform
+    if constexpr (STAGE == STAGE_EST) base = (const E*)a.psum + ((int64_t)f * 2 + i) * (2 * NC);
+    const unsigned t2 = 2u * (unsigned)launder(tid);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) dst[r].load_u(base, t2 + 2u * (unsigned)(r * (NC / 8)));
+}
+// data position of slot s of thread tid, -1: none
+template <int NC> GF3_DEV int demod_pos_of(const DemodArgs& a, int tid, int s) {
+    if (!Spec<NC>::live(tid, s)) return -1;
+    const int bn = Spec<NC>::bin(tid, s);
+    if (a.contig_lo > 0) return (bn >= a.contig_lo && bn < a.contig_lo + a.C) ? bn - a.contig_lo : -1;
+    return a.pos[bn - 1];
+}
+// ---- phasor start-up.  Channel-model phasor per carrier: Hest = mag * g_l,  g_l = u exp(j slope n f_l),
+// f_l = (l + P/2)/(D+P) is linear in l, so g_{l+1} = g_l * exp(j slope n / (D+P)): one complex multiply per carrier per
+// symbol and no sin/cos inside the symbol loop.  The two start-up rotations exp(j phi0 n), exp(j dphi n) come
+// from small two-level tables (n + 1 = 64 h + i  ->  T[64 + h] * T[i]) built once per packet.
+// l0: the first data symbol of this workgroup (the data stage of the two-phase form starts its phasors there: f_l at l = l0).
+// u: the unit phasor of Hs on entry, g_l0 on return; gstep: g_(l+1) / g_l.
+template <int NC> GF3_DEV void demod_startup(const DemodArgs& a, int tid, int l0, double slope, cplx* rtab, cplx (&u)[8], cplx (&gstep)[8]) {
+    constexpr int T = NC / 8, NTH = NC / 64 + 1, NRT = 64 + NTH;
+    const double denom = (double)(a.D + a.P);
+    const double phi0 = slope * (((double)l0 + 0.5 * (double)a.P) / denom);
+    const double dphi = slope / denom;
+    for (int i = tid; i < NRT; i += T) {
+        const double nn = (double)(i < 64 ? i - 1 : 64 * (i - 64));
+        rtab[i] = cis_fast(phi0 * nn);
+        rtab[NRT + i] = cis_fast(dphi * nn);
+    }
+    lds_barrier();
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int n1 = Spec<NC>::bin(tid, s);                              // n + 1
+        const cplx r0 = cmul(rtab[64 + (n1 >> 6)], rtab[n1 & 63]);
+        gstep[s] = cmul(rtab[NRT + 64 + (n1 >> 6)], rtab[NRT + (n1 & 63)]);
+        u[s] = cmul(u[s], r0);
+    }
+}
+// ---- bit-packing (OFDM.py:487-505).  Decisions are staged as one byte per data carrier in a ring of `ring` symbols in
+// LDS and packed into output words one symbol later (after the next FFT's barriers), so the
+// packing needs no atomics and no barrier of its own.  While symbol l is being decided, the words
+// completed by symbol l-1 are packed; the first of them starts up to 31 bits before that symbol, i.e.
+// ceil(32 / (C mu)) symbols back, and none of those slots may be the one symbol l is written to:
+// ring >= ceil(32 / (C mu)) + 2 (rounded up to a power of two on the host, demod_ring).
+// x: word w of the row, most significant bit first; past the last whole word (w == whi) its leading bytes
+GF3_DEV void demod_store_word(const DemodArgs& a, uint8_t* row, int w, int whi, uint32_t x) {
+    if (w < whi) {
+        if ((a.row_bytes & 3) == 0) ((uint32_t*)row)[w] = __builtin_bswap32(x);
+        else { row[4 * w] = x >> 24; row[4 * w + 1] = x >> 16; row[4 * w + 2] = x >> 8; row[4 * w + 3] = x; }
+    } else {                                                               // partial last word of the packet
+        const int rem = (a.D * a.C * a.mu) & 31;
+        for (int bb = 0; bb < ((rem + 7) >> 3); ++bb) row[4 * w + bb] = (uint8_t)(x >> (24 - 8 * bb));
+    }
+}
+// the words that data symbol l completes (tail: and the packet's partial last word)
+template <int NC> GF3_DEV void demod_pack_words(const DemodArgs& a, uint8_t* row, const uint8_t* labs, int tid, int l, bool tail) {
+    constexpr int T = NC / 8;
+    const int C = a.C, mu = a.mu, Bs = C * mu, RC = a.ring * C;
+    const int wlo = (l * Bs) >> 5, whi = ((l + 1) * Bs) >> 5;
+    const int nlab = a.D * C;                                              // labels in the packet
+    if (mu == 2 && (C & 1) == 0) {
+        // QPSK, even C: a word is 16 labels = 4 aligned dwords of the ring; one multiply moves
+        // the four 2-bit labels of a dword into a byte (label i -> bits 7-2i of it)
+        for (int w = wlo + launder(tid); w < whi + (tail ? 1 : 0); w += T) {
+            const int i0 = 16 * w;
+            int r = i0 % RC;
+            uint32_t x = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t d4 = (i0 + 4 * j < nlab) ? *(const uint32_t*)(labs + r) : 0u;
+                if (i0 + 4 * j + 4 > nlab) d4 &= 0xffffffffu >> (8 * (i0 + 4 * j + 4 - nlab));   // C even => whole pairs
+                x = (x << 8) | ((d4 * 0x40100401u) >> 24);
+                r += 4; if (r >= RC) r -= RC;
+            }
+            demod_store_word(a, row, w, whi, x);
+        }
+        return;
+    }
+    for (int w = wlo + launder(tid); w < whi + (tail ? 1 : 0); w += T) {
+        int i = (32 * w) / mu;                                             // first label touching the word
+        const int skip = 32 * w - i * mu;
+        int r = i % RC;
+        uint64_t acc = 0;
+        int nb = 0;
+        while (nb < skip + 32) {
+            const uint32_t lb = (i < nlab) ? labs[r] : 0u;
+            acc = (acc << mu) | lb;
+            nb += mu; ++i;
+            if (++r == RC) r = 0;
+        }
+        demod_store_word(a, row, w, whi, (uint32_t)(acc >> (nb - skip - 32)));
+    }
+}
+
+// demod_screen_kernel's data symbols (gf3rx_demod_screen.hip: fp32 transforms two at a time under a bound, listing epilogue)
+template <int NC, int DT>
+GF3_DEV void demod_screen_data(const DemodArgs& a, const DemodLdsPtr& m, int64_t f, int64_t off, int tid, uint8_t* row, bool unsafe,
+                               RawPair<DT> (&nxt)[8], const cplx (&g0)[8], const cplx (&gstep)[8]);
+// VAR: the two forms of the one-launch QPSK kernel that make up the screened demodulation (gf3rx_dscreen.h, gf3rx_demod_screen.hip).
+// VAR_LISTED (demod_listed_kernel): packet = dwork[16 + blockIdx.x] for blockIdx.x < dwork[0], and nothing else differs -- the
+// fp64 pass over the packets the screen could not decide.  VAR_SCREEN (demod_screen_kernel): everything up to the first data
+// symbol is the code below, unchanged; then demod_screen_data takes over.  (A parameter of the kernel, not a shared body under
+// thin kernels: a body that is handed the argument block, by value or by reference, costs every sign-mode kernel of N = 1024
+// and 8192 a spilled SGPR, and by reference the table modes up to 24 spilled VGPRs.)
 enum { VAR_PLAIN = 0, VAR_LISTED = 1, VAR_SCREEN = 2 };
 template <int NC, int DT, bool SPECTRA, int MODE, int STAGE = STAGE_ALL, int VAR = VAR_PLAIN>
 __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kernel(DemodArgs a) {
@@ -166,16 +364,13 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     static_assert(STAGE != STAGE_EST || DT == DT_F64, "the estimate stage reads the fp64 pilot sums");
     extern __shared__ double2 smem[];
     constexpr int T = NC / 8;
-    // LDS: [scratch 32 doubles | start-up rotation tables | FFT buffer | decision bytes | (fit-range overflow)]
-    // scratch: doubles [16, 32) are block_sum's (the slope fit); once that is done VAR_SCREEN keeps the per-wave l1 sums of the
-    // data symbols there (as float [2][2][8]), and the packet's "listed" flag in double 8
-    double* scratch = (double*)smem;
-    cplx* rtab = (cplx*)(scratch + 32);                                   // [2][64 + NC/64 + 1]
-    cplx* lds = rtab + 2 * (64 + NC / 64 + 1);                            // FFT buffer, DemodOcc::LDS_ELEMS points
-    uint8_t* labs = (uint8_t*)(lds + DemodOcc<NC, MODE>::LDS_ELEMS);      // [ring][C] decisions, one byte each
-    // [8][T] (a0, da) of slot s of thread t (table modes), behind the decision bytes: written only after the
-    // channel-estimate stage, whose fit-range arrays may run over this region
-    double2* mags = (double2*)(labs + ((a.ring * a.C + 15) & ~15));
+    // LDS (demod_lds_layout); scratch: doubles [16, 32) are block_sum's (the slope fit)
+    const DemodLdsPtr m = demod_lds_ptrs<NC, MODE>(smem, a);
+    double* scratch = m.scratch;
+    cplx* rtab = m.rtab;
+    cplx* lds = m.fft;
+    uint8_t* labs = m.labs;
+    double2* mags = m.mags;
     const int tid = threadIdx.x;
     int64_t f = blockIdx.x;
     if constexpr (VAR == VAR_LISTED) {
@@ -211,31 +406,15 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     const int tq = tid;       // 32-bit per-thread indices derived from it may be hoisted: cheap in registers
     auto bin_of = [&](int s) { return Spec<NC>::bin(tq, s); };
     auto live_of = [&](int s) { return Spec<NC>::live(tq, s); };
-    auto pos_of = [&](int s) {
-        if (!live_of(s)) return -1;
-        const int bn = bin_of(s);
-        if (a.contig_lo > 0) return (bn >= a.contig_lo && bn < a.contig_lo + a.C) ? bn - a.contig_lo : -1;
-        return a.pos[bn - 1];
-    };
 
-    // symbol order: start pilots, end pilots, data (position in the packet)
-    auto sym_pos = [&](int i) { return i < P ? i : (i < 2 * P ? D + i : i - P); };
     RawPair<DT> nxt[8];
-    auto fetch = [&](int i) {
-        typedef typename RawT<DT>::E E;
-        const E* base = (const E*)a.in + (off + (int64_t)sym_pos(i) * S + a.CP);      // wave-uniform
-        if constexpr (STAGE == STAGE_EST) base = (const E*)a.psum + ((int64_t)f * 2 + i) * (2 * NC);   // "symbol" i = side i's pilot sum
-        const unsigned t2 = 2u * (unsigned)launder(tid);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) nxt[r].load_u(base, t2 + 2u * (unsigned)(r * T));
-    };
     const int Msym = STAGE == STAGE_EST ? 2 : (STAGE == STAGE_DATA ? 2 * P + l_hi : 2 * P + D);      // (nothing is fetched from here on)
     const int Pl = STAGE == STAGE_EST ? 1 : P;                            // symbols summed per side
     cplx v[8], z0;
     auto transform = [&](int i) {                     // nxt -> spectrum slots in v; prefetch i+1
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = nxt[r].get();
-        if (i + 1 < Msym) fetch(i + 1);
+        if (i + 1 < Msym) demod_fetch<NC, DT, STAGE>(a, f, off, tid, i + 1, nxt);
         ft.refresh();
         asm volatile("" : "+v"(wb.x), "+v"(wb.y));
         rfft_regs<NC, DemodOcc<NC, MODE>::PP, true>(v, lds, ft, wb, tq, z0, i & 1);
@@ -244,50 +423,9 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
 #pragma unroll
         for (int s2 = 0; s2 < 8; ++s2) v[s2] = sp[bin_of(s2) - 1];
     };
-    // VAR_SCREEN: the data symbols go through the transform two at a time, as the halves of cf2 points (gf3rx_device.h) in
-    // the whole FFT buffer: symbols (l, l + 1) from nxt and nxb -> fp32 spectrum slots in vp, the next pair prefetched (its
-    // first symbol under the transform, its second under the decisions).  An odd last symbol runs the same code with an
-    // absent second half: no loads, zeros, no decisions.
-    // Each symbol's l1 norm is summed while its samples are converted; the per-wave sums go to l1s[parity][half][wave] ahead
-    // of the transform's barriers and are read back after them (two parities: pair i + 1 writes before every wave has read
-    // pair i's; i + 2 writes only after the barriers of transform i + 1).
-    cf2 vp[8], z0p;
-    int tp = tid;                                     // the pair transform's thread index, made opaque ahead of the data loop
-    cf wb32;
-    FftTw<NC, cf> ft32;
-    RawPair<DT> nxb[8];
-    float* l1s = (float*)(scratch + 16);                                  // [2][2][8]; scratch[8]: the packet's "listed" flag
-    int* unsafe_flag = (int*)(scratch + 8);
-    auto fetch_b = [&](int i) {
-        typedef typename RawT<DT>::E E;
-        const E* base = (const E*)a.in + (off + (int64_t)sym_pos(i) * S + a.CP);      // wave-uniform
-        const unsigned t2 = 2u * (unsigned)launder(tid);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) nxb[r].load_u(base, t2 + 2u * (unsigned)(r * T));
-    };
-    auto transform_pair = [&](int l) {                // l: the pair's first data symbol
-        const bool hb = l + 1 < D;
-        float sa = 0.0f, sb = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const cf pa = make_float2((float)nxt[r].v.a, (float)nxt[r].v.b);
-            const cf pb = make_float2(hb ? (float)nxb[r].v.a : 0.0f, hb ? (float)nxb[r].v.b : 0.0f);
-            sa += fabsf(pa.x) + fabsf(pa.y);
-            sb += fabsf(pb.x) + fabsf(pb.y);
-            vp[r] = pair_of(pa, pb);
-        }
-        if (l + 2 < D) fetch(2 * P + l + 2);
-        sa = scr_wave_reduce<false>(sa);
-        sb = scr_wave_reduce<false>(sb);
-        const int par = (l >> 1) & 1;
-        if ((tid & 63) == 0) { l1s[par * 16 + (tid >> 6)] = sa; l1s[par * 16 + 8 + (tid >> 6)] = sb; }
-        ft32.refresh();
-        asm volatile("" : "+v"(wb32.x), "+v"(wb32.y));
-        rfft_regs<NC, DemodOcc<NC, MODE>::PP, true>(vp, (cf2*)lds, ft32, wb32, tp, z0p, par);
-    };
     GF3_STAMP(0);
     GF3_STAMP_RT(6);
-    if constexpr (!SPECTRA) fetch(STAGE == STAGE_DATA ? 2 * P + l_lo : 0);
+    if constexpr (!SPECTRA) demod_fetch<NC, DT, STAGE>(a, f, off, tid, STAGE == STAGE_DATA ? 2 * P + l_lo : 0, nxt);
 
     // ---- pilots: Hs, He = mean over P symbols / known  (OFDM.py:443-451).
     // The mean of the P pilot spectra is the spectrum of the mean pilot symbol (the DFT is linear), so
@@ -322,7 +460,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
             for (int i = side * Pl; i < (side + 1) * Pl; ++i) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) sum[r] = cadd(sum[r], nxt[r].get());
-                if (i + 1 < (SCREEN ? 2 * P : Msym)) fetch(i + 1); // next pilot, or the first data symbol (VAR_SCREEN: ahead of the data loop)
+                if (i + 1 < (SCREEN ? 2 * P : Msym)) demod_fetch<NC, DT, STAGE>(a, f, off, tid, i + 1, nxt); // next pilot, or the first data symbol (SCREEN: ahead of the data loop)
             }
             if (side == 0) GF3_STAMP(1);
 #pragma unroll
@@ -346,7 +484,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     if constexpr (STAGE != STAGE_DATA) lds_barrier();  // FFT buffer is free: reuse it for the fit-range carriers
     const int L = a.fit_hi - a.fit_lo;
     // [L] Hs of carrier fit_lo + j, later its angle in .x.  The two arrays start at the FFT buffer and may run on
-    // over the decision bytes (not in use before the first data symbol) and beyond: demod_lds_bytes sizes it.
+    // over the decision bytes (not in use before the first data symbol) and beyond: demod_lds_layout sizes it.
     cplx* hsl = lds;
     cplx* hel = hsl + L;                              // [L] same for He
     cplx u[8];
@@ -357,7 +495,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     constexpr double XS = SPECTRA ? 1.0 : 2.0;
     const double invP = (1.0 / (double)P) / XS;
     // (a) straight-line over the 8 slots (independent chains overlap): H = mean/known, unit phasor, magnitudes
-    // (VAR_SCREEN) the packet goes to the fp64 pass: a part the bound does not back in any data symbol -- or a non-finite
+    // (SCREEN) the packet goes to the fp64 pass: a part the bound does not back in any data symbol -- or a non-finite
     // end-pilot estimate: the sign mode reads He only through the fit's angles, where atan2_fast turns a NaN into 0, so
     // such a packet could come out decidable; with this every packet that holds a non-finite sample is listed (a data
     // symbol's makes E_l non-finite, a start pilot's makes u and with it every rotated symbol NaN)
@@ -430,182 +568,28 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
     }
 
     // ---- data symbols: FFT -> /Hest -> demap -> bit-pack (OFDM.py:466-478, 487-505)
-    // Decisions are staged as one byte per data carrier in a ring of `ring` symbols in LDS and
-    // packed into output words one symbol later (after the next FFT's barriers), so the
-    // packing needs no atomics and no barrier of its own.  While symbol l is being decided, the words
-    // completed by symbol l-1 are packed; the first of them starts up to 31 bits before that symbol, i.e.
-    // ceil(32 / (C mu)) symbols back, and none of those slots may be the one symbol l is written to:
-    // ring >= ceil(32 / (C mu)) + 2 (rounded up to a power of two on the host, demod_ring).
     const int C = a.C, mu = a.mu;
-    const int RC = a.ring * C;
-    auto pack_words = [&](int l, bool tail) {
-        const int wlo = (l * Bs) >> 5, whi = ((l + 1) * Bs) >> 5;
-        const int nlab = D * C;                                            // labels in the packet
-        if (mu == 2 && (C & 1) == 0) {
-            // QPSK, even C: a word is 16 labels = 4 aligned dwords of the ring; one multiply moves
-            // the four 2-bit labels of a dword into a byte (label i -> bits 7-2i of it)
-            for (int w = wlo + launder(tid); w < whi + (tail ? 1 : 0); w += T) {
-                const int i0 = 16 * w;
-                int r = i0 % RC;
-                uint32_t x = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t d4 = (i0 + 4 * j < nlab) ? *(const uint32_t*)(labs + r) : 0u;
-                    if (i0 + 4 * j + 4 > nlab) d4 &= 0xffffffffu >> (8 * (i0 + 4 * j + 4 - nlab));   // C even => whole pairs
-                    x = (x << 8) | ((d4 * 0x40100401u) >> 24);
-                    r += 4; if (r >= RC) r -= RC;
-                }
-                if (w < whi) {
-                    if ((a.row_bytes & 3) == 0) ((uint32_t*)row)[w] = __builtin_bswap32(x);
-                    else { row[4 * w] = x >> 24; row[4 * w + 1] = x >> 16; row[4 * w + 2] = x >> 8; row[4 * w + 3] = x; }
-                } else {
-                    const int rem = (D * Bs) & 31;
-                    for (int bb = 0; bb < ((rem + 7) >> 3); ++bb) row[4 * w + bb] = (uint8_t)(x >> (24 - 8 * bb));
-                }
-            }
-            return;
-        }
-        for (int w = wlo + launder(tid); w < whi + (tail ? 1 : 0); w += T) {
-            int i = (32 * w) / mu;                                         // first label touching the word
-            const int skip = 32 * w - i * mu;
-            int r = i % RC;
-            uint64_t acc = 0;
-            int nb = 0;
-            while (nb < skip + 32) {
-                const uint32_t lb = (i < nlab) ? labs[r] : 0u;
-                acc = (acc << mu) | lb;
-                nb += mu; ++i;
-                if (++r == RC) r = 0;
-            }
-            const uint32_t x = (uint32_t)(acc >> (nb - skip - 32));
-            if (w < whi) {
-                if ((a.row_bytes & 3) == 0) ((uint32_t*)row)[w] = __builtin_bswap32(x);
-                else { row[4 * w] = x >> 24; row[4 * w + 1] = x >> 16; row[4 * w + 2] = x >> 8; row[4 * w + 3] = x; }
-            } else {                                                       // partial last word of the packet
-                const int rem = (D * Bs) & 31;
-                for (int bb = 0; bb < ((rem + 7) >> 3); ++bb) row[4 * w + bb] = (uint8_t)(x >> (24 - 8 * bb));
-            }
-        }
-    };
     const double denom = (double)(D + P);
-    // Channel-model phasor per carrier: Hest = mag * g_l,  g_l = u exp(j slope n f_l),  f_l = (l + P/2)/(D+P)
-    // is linear in l, so g_{l+1} = g_l * exp(j slope n / (D+P)): one complex multiply per carrier per symbol
-    // and no sin/cos inside the symbol loop.  The two start-up rotations exp(j phi0 n), exp(j dphi n) come
-    // from small two-level tables (n + 1 = 64 h + i  ->  T[64 + h] * T[i]) built once per packet.
-    constexpr int NTH = NC / 64 + 1, NRT = 64 + NTH;
-    {
-        // (the data stage of the two-phase form starts its phasors at its first symbol: f_l at l = l_lo)
-        const double phi0 = STAGE == STAGE_DATA ? slope * (((double)l_lo + 0.5 * (double)P) / denom) : slope * ((0.5 * (double)P) / denom);
-        const double dphi = slope / denom;
-        for (int i = tid; i < NRT; i += T) {
-            const double nn = (double)(i < 64 ? i - 1 : 64 * (i - 64));
-            rtab[i] = cis_fast(phi0 * nn);
-            rtab[NRT + i] = cis_fast(dphi * nn);
-        }
-    }
-    if constexpr (SCREEN) {
-        if (tid == 0) *unsafe_flag = 0;
-        ft32.init(tid, a.tw32);
-        wb32 = a.tw32[NC + tid];
-    }
-    lds_barrier();
     cplx gstep[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const int n1 = bin_of(s);                                          // n + 1
-        const cplx r0 = cmul(rtab[64 + (n1 >> 6)], rtab[n1 & 63]);
-        gstep[s] = cmul(rtab[NRT + 64 + (n1 >> 6)], rtab[NRT + (n1 & 63)]);
-        u[s] = cmul(u[s], r0);                                             // u now holds g_0
+    demod_startup<NC>(a, tid, l_lo, slope, rtab, u, gstep);            // u now holds g_0 (the data stage: g at its first symbol)
+    if constexpr (SCREEN) {
+        demod_screen_data<NC, DT>(a, m, f, off, tid, row, unsafe, nxt, u, gstep);
+        return;
     }
     // data position of every slot, resolved once: a lookup inside the symbol loop would put a vmcnt(0) wait
     // behind the packed-word stores and the next symbol's prefetch
     // (QPSK mode; the table modes have no registers to spare for it -- even packed two to a register the positions push
     //  the kernel from 240 VGPRs to 256 and into spills -- and recompute the position per symbol: plain arithmetic for a
     //  contiguous band)
-    // VAR_SCREEN: g_0 and gstep rounded once; the recurrence runs in fp32 from here on (gf3rx_dscreen.h, "The rotation") and
-    // the 64 registers of fp64 state are free inside the data loop
-    cf g32[8], gs32[8];
-    if constexpr (SCREEN) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            g32[s] = make_float2((float)u[s].x, (float)u[s].y);
-            gs32[s] = make_float2((float)gstep[s].x, (float)gstep[s].y);
-        }
-    }
     int psl[8];
-    uint32_t psp[4];                                  // VAR_SCREEN: the same, two to a register (C < 65535; 0xffff: no data carrier)
-    if constexpr (SCREEN) {
+    if constexpr (MODE == MODE_QPSK) {
 #pragma unroll
-        for (int s = 0; s < 8; s += 2) psp[s >> 1] = ((uint32_t)pos_of(s) & 0xffffu) | ((uint32_t)pos_of(s + 1) << 16);
-    } else if constexpr (MODE == MODE_QPSK) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) psl[s] = pos_of(s);
+        for (int s = 0; s < 8; ++s) psl[s] = demod_pos_of<NC>(a, tid, s);
     }
-    if constexpr (SCREEN) {
-        // cf2 points are as large as fp64 points, so the pair transform's LDS addresses are the pilot transforms': derived from
-        // tid they would be computed once at the top of the kernel and held (or spilled) across the fit
-        tp = launder(tid);
-        // The first pair of data symbols, held behind the fp64 start-up by the scheduling barrier.  Fetched earlier (with the
-        // last pilot, as the one-symbol loops do, or under the rotation tables) the f32 instantiations of the fused sizes
-        // spill 8-11 VGPRs: the start-up has the 32 table reads of its rotations in flight next to u and gstep.  (One exposed
-        // fetch per packet; the CU's other workgroup runs under it.)
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(2 * P);
-        if (D > 1) fetch_b(2 * P + 1);
-        // Two symbols decided and two packed per turn.  The ring (demod_ring): while pack_words(l - 2) and (l - 1) read slots
-        // l - 2 - ceil(32 / (C mu)) .. l - 1, NO slot is written -- the barrier below stands between the packing and the
-        // decisions of symbols l, l + 1, whose slots may then be any the coming packs no longer need: they overwrite l - ring
-        // and l + 1 - ring, and the oldest slot still to be read is l - ceil(32 / (C mu)) (the turn after), so
-        // ring >= ceil(32 / (C mu)) + 2 as for one symbol per turn.  (Without the barrier five slots would be in use at
-        // C mu = 4092 and the ring would have to double, which two workgroups per CU have no LDS for.)
-        for (int l = 0; l < D; l += 2) {
-            const bool hb = l + 1 < D;
-            transform_pair(l);
-            // the next pair's second symbol is fetched under the packing and the decisions, its first under the transform: two
-            // symbols in flight across the transform do not fit the register file (f32 storage: 16 VGPRs each)
-            if (l + 3 < D) fetch_b(2 * P + l + 3);
-            if (l > 0) { pack_words(l - 2, false); pack_words(l - 1, false); }
-            lds_barrier();
-            const int par = (l >> 1) & 1;
-            float l1a = 0.0f, l1b = 0.0f;
-#pragma unroll
-            for (int w = 0; w < (T + 63) / 64; ++w) { l1a += l1s[par * 16 + w]; l1b += l1s[par * 16 + 8 + w]; }
-            const float Ea = dscr_bound<NC>(l1a), Eb = dscr_bound<NC>(l1b);  // (an absent half: l1b = 0, Eb finite)
-            unsafe = unsafe || !(Ea < INFINITY) || !(Eb < INFINITY);
-            if (a.dbg_E && tid == 0) {
-                a.dbg_E[f * D + l] = Ea;
-                if (hb) a.dbg_E[f * D + l + 1] = Eb;
-            }
-            uint8_t* lab_a = labs + (l & (a.ring - 1)) * C;
-            uint8_t* lab_b = labs + ((l + 1) & (a.ring - 1)) * C;
-            const float Ca = dscr_rot(l), Cb = dscr_rot(l + 1);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const cf ga = g32[s];
-                const cf gb = cmul(ga, gs32[s]);                           // the recurrence of the modes below, in fp32
-                g32[s] = cmul(gb, gs32[s]);
-                cf epa, epb;
-                bool safe_a, safe_b;
-                const uint32_t la = dscr_decide(half_a(vp[s]), ga, Ea, Ca, epa, safe_a);
-                const uint32_t lb = dscr_decide(half_b(vp[s]), gb, Eb, Cb, epb, safe_b);
-                const int ps = (int)((psp[s >> 1] >> (16 * (s & 1))) & 0xffffu);
-                if (ps != 0xffff) {
-                    lab_a[ps] = (uint8_t)la;
-                    unsafe = unsafe || !safe_a;
-                    if (a.dbg_ep) a.dbg_ep[(f * D + l) * (int64_t)C + ps] = epa;
-                    if (hb) {
-                        lab_b[ps] = (uint8_t)lb;
-                        unsafe = unsafe || !safe_b;
-                        if (a.dbg_ep) a.dbg_ep[(f * D + l + 1) * (int64_t)C + ps] = epb;
-                    }
-                }
-            }
-        }
-    } else
     for (int l = l_lo; l < l_hi; ++l) {
         if constexpr (SPECTRA) { lds_barrier(); load_spectra(a.sp_data + ((int64_t)f * D + l) * K); }
         else transform(2 * P + l);
-        if constexpr (MODE != MODE_SOFT) { if (l > l_lo) pack_words(l - 1, false); }
+        if constexpr (MODE != MODE_SOFT) { if (l > l_lo) demod_pack_words<NC>(a, row, labs, tid, l - 1, false); }
         const double fl = ((double)l + 0.5 * (double)P) / denom;          // (l + P/2)/(D+P)
         uint8_t* lab_l = labs + (l & (a.ring - 1)) * C;
         if constexpr (MODE == MODE_QPSK) {
@@ -643,7 +627,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
                 const cplx g = u[s];
                 const cplx ep = cmul_conj(v[s], g);
                 u[s] = cmul(g, gstep[s]);
-                const int ps = pos_of(s);
+                const int ps = demod_pos_of<NC>(a, tid, s);
                 const double2 md = mags[s * T + tid];
                 const double mag = fma(md.y, fl, md.x);
                 if (ps >= 0) {
@@ -679,7 +663,7 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
                 const cplx g = u[s];                                       // unit phasor of Hest for this symbol
                 const cplx ep = cmul_conj(v[s], g);                        // X / g  = e * mag
                 u[s] = cmul(g, gstep[s]);                                  // ... and for the next one
-                const int ps = pos_of(s);
+                const int ps = demod_pos_of<NC>(a, tid, s);
                 const double2 md = mags[s * T + tid];
                 const double mag = fma(md.y, fl, md.x);
                 // bits only: the decision needs (ep / mag - lo) inv to far less than full precision (the margin of `clear`
@@ -727,62 +711,10 @@ __global__ __launch_bounds__(NC / 8, (DemodOcc<NC, MODE>::WPS)) void demod_kerne
         }
     }
     GF3_STAMP(4);
-    if constexpr (SCREEN) { if (unsafe) *unsafe_flag = 1; }
     if constexpr (MODE != MODE_SOFT) {
         lds_barrier();
-        if constexpr (SCREEN) { if ((D & 1) == 0) pack_words(D - 2, false); }       // the last pair's first symbol
-        pack_words(l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
-    }
-    if constexpr (SCREEN) {
-        if (tid == 0) {                                                    // (the row is written anyway: the fp64 pass overwrites it)
-            if (*unsafe_flag) a.dwork[16 + atomicAdd(a.dwork, 1)] = (int)f;
-        }
+        demod_pack_words<NC>(a, row, labs, tid, l_hi - 1, l_hi == D && ((D * Bs) & 31) != 0);
     }
     GF3_STAMP(5);
     GF3_STAMP_RT(7);
-}
-
-// ============================================================================
-// host side: LDS layout of demod_kernel
-// ============================================================================
-// symbols in the decision-byte ring of demod_kernel: ceil(32 / (C mu)) + 2, rounded up to a power of two
-// (>= 4: the QPSK packer reads the ring one aligned dword at a time, so ring * C must be a multiple of 4)
-// Invariant: no slot is written while a thread may still read it, and a slot is overwritten only once every word that
-// touches it is packed.  One symbol per turn (fp64 forms): symbol l is written while pack_words(l - 1) reads back to slot
-// l - 1 - ceil(32 / (C mu)) between the same barriers, hence the + 2.  VAR_SCREEN decides two symbols per turn and keeps
-// this ring: a barrier separates its packing from its decisions (see its data loop), so reads and writes never share an
-// interval and only the second half of the invariant is left, which ring >= ceil(32 / (C mu)) + 2 also covers.
-inline int demod_ring(const gf3_ctx* c) {
-    const int Bs = c->cfg.C * c->cfg.mu;
-    const int need = (32 + Bs - 1) / Bs + 2;
-    int r = 4;
-    while (r < need) r <<= 1;
-    return r;
-}
-// DemodOcc::PP_SIZE on the host
-constexpr bool demod_pp_size(int NC) { return NC == 1024 || NC == 2048 || NC == 4096; }
-static_assert(demod_pp_size(512) == DemodOcc<512, MODE_QPSK>::PP_SIZE && demod_pp_size(1024) == DemodOcc<1024, MODE_QPSK>::PP_SIZE &&
-              demod_pp_size(2048) == DemodOcc<2048, MODE_QPSK>::PP_SIZE && demod_pp_size(4096) == DemodOcc<4096, MODE_QPSK>::PP_SIZE,
-              "demod_pp_size restates DemodOcc::PP_SIZE");
-// lean = MODE_QPSK (ping-pong FFT buffers); the table modes use the in-place buffer and NC (a0, da) pairs.
-// Layout: [scratch 32 doubles | rotation tables | FFT buffer | decision bytes | (a0, da) pairs]; everything from the
-// FFT buffer on is overlaid by Hs, He of the fit range during the channel-estimate stage (which may need more).
-inline size_t demod_lds_bytes(const gf3_ctx* c, bool lean = false) {
-    const bool inplace = !lean, pp_size = demod_pp_size(c->NC);
-    const size_t fft = (inplace || !pp_size) ? (size_t)(c->NC + c->NC / 8) * sizeof(cplx) : (size_t)2 * c->NC * sizeof(cplx);
-    const size_t mags = lean ? 0 : (size_t)c->NC * sizeof(double2);
-    const size_t tail = fft + (size_t)((demod_ring(c) * c->cfg.C + 15) & ~15) + mags;
-    const size_t fit = (size_t)2 * (c->fit_hi - c->fit_lo) * sizeof(cplx);
-    return 32 * sizeof(double) + (size_t)2 * (64 + c->NC / 64 + 1) * sizeof(cplx) + (fit > tail ? fit : tail);
-}
-// MODE_SOFT: no decision ring; the (a0, da) pairs follow the FFT buffer directly, and a symbol's LLRs are staged IN the
-// FFT buffer (NC + NC/8 points) when they fit with the alignment shift (<= 3 floats) and the last vector's overhang
-// (<= 3 more: read, never stored) -- no LDS beyond the table modes'.
-inline bool demod_soft_stages(const gf3_ctx* c) {
-    return (size_t)c->cfg.C * c->cfg.mu * sizeof(float) + 8 * sizeof(float) <= (size_t)(c->NC + c->NC / 8) * sizeof(cplx);
-}
-inline size_t demod_soft_lds_bytes(const gf3_ctx* c) {
-    const size_t tail = (size_t)(c->NC + c->NC / 8) * sizeof(cplx) + (size_t)c->NC * sizeof(double2);
-    const size_t fit = (size_t)2 * (c->fit_hi - c->fit_lo) * sizeof(cplx);
-    return 32 * sizeof(double) + (size_t)2 * (64 + c->NC / 64 + 1) * sizeof(cplx) + (fit > tail ? fit : tail);
 }

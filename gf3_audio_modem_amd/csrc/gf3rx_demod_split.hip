@@ -114,14 +114,7 @@ int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStrea
     {
         hipError_t e = hipSuccess;
         const size_t lds = demod_lds_bytes(c, true);
-        switch (NC) {
-#ifndef GF3_DEV_BUILD
-            case 512:  e = launch((demod_kernel<512, DT_F64, false, MODE_QPSK, STAGE_EST>), F, 64, lds, st, a); break;
-            case 1024: e = launch((demod_kernel<1024, DT_F64, false, MODE_QPSK, STAGE_EST>), F, 128, lds, st, a); break;
-            case 4096: e = launch((demod_kernel<4096, DT_F64, false, MODE_QPSK, STAGE_EST>), F, 512, lds, st, a); break;
-#endif
-            default:   e = launch((demod_kernel<2048, DT_F64, false, MODE_QPSK, STAGE_EST>), F, 256, lds, st, a); break;
-        }
+        DISPATCH_NC_F64(NC, e = launch((demod_kernel<NCC, DT_F64, false, MODE_QPSK, STAGE_EST>), F, NCC / 8, lds, st, a));
         HIPCHK(c, e);
     }
     hipError_t e = hipSuccess;

@@ -23,7 +23,7 @@
 //     finite there, the fp64 kernel's label is the two sign bits too (qpsk_sign_rule's common case);
 //   * a packet with any unsafe part in any data symbol, a non-finite E_l or a non-finite end-pilot estimate (which the sign
 //     mode would otherwise see only through the fit's angles) is appended to a list (atomicAdd on a count,
-//     then the packet number -- as corr_screen_kernel does), and demod_kernel<.., VAR_LISTED> -- the fp64 kernel, same code
+//     then the packet number -- as corr_screen_kernel does), and demod_listed_kernel -- the fp64 kernel, same code
 //     path for everything but where its packet number comes from -- runs on the listed packets and overwrites their rows.
 //     No decision rests on an fp32 value that the bound does not back.
 // Ragged packets do what demod_kernel does (zero row, status bit) and are not listed.

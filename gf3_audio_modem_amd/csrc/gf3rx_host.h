@@ -4,7 +4,7 @@
 //   gf3rx_fft.hip            rfft_kernel, tx_kernel
 //   gf3rx_demod_{qpsk,scan,full,soft}.hip   the four modes of demod_kernel (gf3rx_demod.h)
 //   gf3rx_demod_split.hip, gf3rx_dsplit_{qpsk,scan,full,soft}.hip   the two-phase demodulation of long packets
-//   gf3rx_demod_screen.hip   demod_screen_kernel (fp32 data-symbol transforms under a bound, gf3rx_dscreen.h) and the LISTED fp64 pass
+//   gf3rx_demod_screen.hip   demod_screen_kernel (fp32 data-symbol transforms under a bound, gf3rx_dscreen.h) and demod_listed_kernel, the fp64 pass over the packets it listed
 //   gf3rx_corr.hip           corr_kernel, spec_kernel, ols_kernel
 //   gf3rx_screen.hip         scr_ring_kernel, scr_ols_kernel, scr_refine_kernel (gf3rx_screen.h)
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
@@ -99,7 +99,7 @@ struct DemodArgs {
         struct {
             const cf* tw32;           // [NC | NC/2+1] the two twiddle tables rounded once to fp32, one after the other
             int* dwork;               // [count | pad to 16 ints | packet numbers]: the screen appends the packets it cannot
-                                      // decide; the LISTED fp64 pass reads them: packet = dwork[16 + blockIdx.x], blockIdx.x < dwork[0]
+                                      // decide; demod_listed_kernel reads them: packet = dwork[16 + blockIdx.x], blockIdx.x < dwork[0]
             cf* dbg_ep; float* dbg_E; // optional (tests): [F][D][C] fp32 rotated symbols, [F][D] the bound
         };
     };
@@ -292,6 +292,7 @@ static hipError_t launch(Kern k, int64_t grid, int threads, size_t lds, hipStrea
         default:     { constexpr int DTC = DT_F32; CALL; break; }         \
     }
 #define DISPATCH_NC(NCv, DTv, CALL) { constexpr int NCC = 2048; DISPATCH_DT(DTv, CALL); }
+#define DISPATCH_NC_F64(NCv, CALL) { constexpr int NCC = 2048; CALL; }
 #else
 #define DISPATCH_DT(DTv, CALL)                                            \
     switch (DTv) {                                                        \
@@ -306,6 +307,14 @@ static hipError_t launch(Kern k, int64_t grid, int threads, size_t lds, hipStrea
         case 1024: { constexpr int NCC = 1024; DISPATCH_DT(DTv, CALL); break; }   \
         case 2048: { constexpr int NCC = 2048; DISPATCH_DT(DTv, CALL); break; }   \
         default:   { constexpr int NCC = 4096; DISPATCH_DT(DTv, CALL); break; }   \
+    }
+/* kernels that exist for f64 input only (spectra from memory, the estimate stage's pilot sums) */
+#define DISPATCH_NC_F64(NCv, CALL)                                        \
+    switch (NCv) {                                                        \
+        case 512:  { constexpr int NCC = 512;  CALL; break; }             \
+        case 1024: { constexpr int NCC = 1024; CALL; break; }             \
+        case 4096: { constexpr int NCC = 4096; CALL; break; }             \
+        default:   { constexpr int NCC = 2048; CALL; break; }             \
     }
 #endif
 

@@ -38,8 +38,6 @@ if __name__ == "__main__":
                 return subprocess.run(cmd, capture_output=True, text=True).stderr
             with ThreadPoolExecutor(8) as pool:
                 txt = "".join(pool.map(one, units))
-    if "--demangle" in sys.argv or True:
-        pass
     print(f"{'VGPR':>4} {'AGPR':>4} {'SGPR':>4} {'sSpl':>4} {'vSpl':>4} {'scr':>4} {'occ':>3} {'LDS':>6}  kernel")
     for r in table(txt):
         name = r[8]
