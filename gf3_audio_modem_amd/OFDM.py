@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
+from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
@@ -157,6 +158,11 @@ class CamG:
         self.blanking_guard = 8
         self.last_blanked = None
         self.last_sample_level = None
+        # receiver.receive_diversity (several recordings of one transmission, maximal-ratio combined): the packet starts it
+        # found in each recording [B, packets] and, under llr_weighting = "noise", each recording's per-carrier SNR estimate
+        # [B, packets, C] in dB (`last_snr_db` is then the SNR after combining); None otherwise
+        self.last_branch_starts = None
+        self.last_branch_snr_db = None
         self._engines = {}
 
     def __repr__(self):
@@ -537,6 +543,93 @@ class receiver(transmitter):
         print("Number of received bits:            " + str(len(bits)))
         if graph_output:
             self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())
+        return bits, got["Hs0"], got["He0"]
+
+    # ---- receive diversity (not in the reference) ------------------------------------------------------------------
+    def receive_diversity(self, signals, graph_output=False):
+        """receive() on B = 1 .. 4 recordings of ONE transmission (the channels of a stereo recording, a second
+        microphone): a sequence of one-dimensional recordings, which may differ in length, or a 2-D array [B, n].  Every
+        branch is synchronised and demodulated on its own (arrival times differ by the microphones' distances); the
+        equalised symbols are then combined with maximal-ratio weights (Engine.combine_branches) by `llr_weighting`:
+        "csi" (the default), each branch's |H^|^2; "noise", 1 / each branch's measured per-carrier noise variance.  A
+        carrier in a null of one microphone's transfer function is filled from the others.  "QCLDPC-*": the combined LLRs
+        go through decode's chain (LDPC -> CRC -> outer code) and `last_decode_report`; "None" / "XOR": the combined
+        symbols are decided by `demap`'s rule, then un-whitened.  -> (bits, Hs, He of branch 0's first packet), as receive().
+        Leaves `last_branch_starts` int64 [B, F]; under "noise" `last_branch_snr_db` [B, F, C] and `last_snr_db` [F, C]
+        (after combining) in dB.  A branch that lost lock is NOT rejected and poisons the sum: look at its row of
+        `last_branch_snr_db`.  ValueError: B outside 1 .. 4, branches with different packet counts, llr_weighting
+        "noise2d", fused_llr, phase_tracking, decoder_feedback.  NotImplementedError: impulse_blanking, graph_output,
+        the piece-wise host path of long recordings (or host_chunk_samples)."""
+        print("-" * 42 + "\nReceive \n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        if isinstance(signals, torch.Tensor):
+            signals = signals.detach().cpu().numpy()
+        if isinstance(signals, np.ndarray) and signals.ndim != 2:
+            raise ValueError(f"receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n], not an array of shape {signals.shape}")
+        try:
+            B = len(signals)
+        except TypeError:
+            raise ValueError("receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n]")
+        if not 1 <= B <= GF3_MAX_BRANCHES:
+            raise ValueError(f"receive_diversity: 1 to {GF3_MAX_BRANCHES} recordings, not {B}")
+        chain = self._chain()
+        rate = chain.check_diversity()                          # (the refusals: before any GPU work)
+        if self.impulse_blanking:
+            raise NotImplementedError("receive_diversity: impulse_blanking is not combined; blank each recording's samples "
+                                      "with Engine.blank_impulses first")
+        if graph_output:
+            raise NotImplementedError("receive_diversity: no plots; receive() one recording for them")
+        rs = [_as_samples(r) for r in signals]
+        if any(r.ndim != 1 for r in rs):
+            raise ValueError("receive_diversity: every recording must be one-dimensional")
+        if getattr(self, "host_chunk_samples", None) or any(len(r) > (1 << 27) for r in rs):
+            raise NotImplementedError("receive_diversity: the piece-wise host path of long recordings (or host_chunk_samples) "
+                                      "combines nothing; receive shorter recordings")
+        dtype = np.result_type(*[r.dtype for r in rs])
+        eng = self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
+        # 1. sync and 2. demodulate, per branch
+        starts, outs = [], []
+        for r in rs:
+            x = eng._samples(r)
+            st = (eng.sync_stream(x) + 2)[:-1]                  # OFDM.py:393-395
+            starts.append(st)
+            outs.append((x, st))
+        counts = [int(st.numel()) for st in starts]
+        if len(set(counts)) != 1:
+            raise ValueError(f"receive_diversity: the recordings hold different numbers of packets: {counts}")
+        self.no_packets = counts[0]
+        if self.no_packets == 0:
+            raise ValueError("need at least one array to concatenate")
+        outs = [eng.demod_frames(x, st, want=("eq", "Hs", "He", "slope", "status")) for x, st in outs]
+        # 3. combine, then the coded chain or the hard decision and un-whitening
+        pts = self._tables()[0]
+        need = {"Hs0": outs[0]["Hs"][0], "He0": outs[0]["He"][0], "slope": outs[0]["slope"], "starts": torch.stack(starts)}
+        if rate is not None:
+            llr, rows = chain.combine(eng, outs, pts)
+            bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
+            if bad is not None:
+                need["crc_bad"] = bad
+        else:
+            eq, rows = chain.combine(eng, outs, pts, want="eq")
+            bits_t = eng.demap_hard(eq)[0].reshape(-1)
+            if self.encoding == "XOR":
+                mask = torch.from_numpy(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.uint8)).to(eng.device)
+                bits_t = bits_t ^ mask.repeat(-(-bits_t.numel() // mask.numel()))[: bits_t.numel()]
+        # 4. one small copy; last in it the ragged-packet flags
+        got = fetch({**need, **rows, "ragged": torch.cat([o["status"] for o in outs])})
+        if got["ragged"].any():
+            raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
+        print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
+        bits = bits_t.cpu().numpy().astype(np.int64)
+        self._last_slope = got["slope"]
+        self.last_branch_starts = got["starts"]
+        self.last_branch_snr_db = got.get("last_branch_snr_db")
+        if "last_snr_db" in got:
+            self.last_snr_db = got["last_snr_db"]
+        if rate is not None:
+            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
+        print("Number of received bits:            " + str(len(bits)))
         return bits, got["Hs0"], got["He0"]
 
     def _receive_chunked(self, eng, r, chunk):

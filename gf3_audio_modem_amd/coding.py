@@ -215,6 +215,42 @@ class CodedChain:
             llr = eng.interleave(llr, inverse=True)
         return llr, snr
 
+    def check_diversity(self):
+        """What receive_diversity() refuses before any GPU work -> rate."""
+        if self.llr_weighting == "noise2d":
+            raise ValueError("receive_diversity: llr_weighting must be 'csi' or 'noise'; 'noise2d' (per-symbol weights per "
+                             "branch) is not combined")
+        rate, _ = self.check_receive()
+        for name in ("fused_llr", "phase_tracking", "decoder_feedback"):
+            if getattr(self, name):
+                raise ValueError(f"receive_diversity: {name} works on one recording; switch it off")
+        return rate
+
+    def combine(self, eng, outs, points, want="llr"):
+        """Receive diversity: the per-branch demodulator outputs (B dicts with 'eq', 'Hs', 'He') -> (maximal-ratio combined
+        LLRs in coded order -- or, want = "eq", the combined symbols for a hard decision --, {attribute name: rows for the
+        host}).  Weights by `llr_weighting`: "csi" the |H^|^2 of each branch, "noise" 1 / the per-carrier variance
+        Engine.noise_estimate measures on each branch, floored at 1e-6 of the packet's mean over all branches; the latter
+        leaves `last_branch_snr_db` [B, F, C] = 10 log10(Es / floored variance) and `last_snr_db` [F, C] = 10 log10(Es
+        sum_b w_b), the SNR after combining."""
+        eqs, rows = [o["eq"] for o in outs], {}
+        if self.llr_weighting == "csi":
+            got = eng.combine_branches(eqs, Hs=[o["Hs"] for o in outs], He=[o["He"] for o in outs], want=(want,))[want]
+        else:
+            var = torch.stack([eng.noise_estimate(e) for e in eqs])                     # [B, F, C]
+            got = eng.combine_branches(eqs, var=list(var), want=(want,))[want]
+            vbar = var.mean(dim=(0, 2))[None, :, None]
+            flat = ~(torch.isfinite(vbar) & (vbar > 0))
+            floored = torch.maximum(var, 1e-6 * vbar)
+            w = torch.where(flat, torch.ones_like(var), 1.0 / floored)
+            w = torch.where(torch.isfinite(var) & torch.isfinite(w), w, torch.zeros_like(w))
+            es = float(np.mean(np.abs(points) ** 2))
+            rows["last_branch_snr_db"] = 10.0 * torch.log10(es / floored)
+            rows["last_snr_db"] = 10.0 * torch.log10(es * w.sum(dim=0))
+        if want == "llr" and self.interleave:
+            got = eng.interleave(got, inverse=True)
+        return got, rows
+
     def hard_llrs(self, bits, engine):
         """Received hard bits -> +-1 LLRs in coded order; `engine()` is asked for only to undo the interleaver."""
         b = np.asarray(bits)

@@ -128,6 +128,12 @@ GF3_DEV void store_llr(float* llr, int64_t i, const float (&out)[MU]) {
     }
 }
 
+// The reference's channel magnitude at data symbol l of a packet (OFDM.py:469), from the magnitudes s = |Hs| and e = |He|
+// of the two pilot blocks' estimates on a carrier: the CSI weight is its square (csi_weight_kernel, combine_kernel).
+GF3_DEV double csi_mag(double s, double e, int l, int P, int D) {
+    return s + (e - s) * (l + P / 2.0) / (double)(D + P);
+}
+
 // Squared distance to the point the hard decision picks: in-order scan with strict `<`, so a NaN symbol keeps point 0
 // (and a NaN distance).  On a grid table the minimum over the points is the sum of the two axes' minima, exactly:
 // rounding is monotonic, so min_k a_k + min_j b_j and min_kj (a_k + b_j) are the same number.

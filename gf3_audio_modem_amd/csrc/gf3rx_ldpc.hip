@@ -6,6 +6,7 @@
 // (encoder).  Z = 64: one wave is one codeword and the waves of a workgroup are independent (no barrier anywhere).
 // Z = 128, 256 (the *_wide kernels): the Z/64 waves of one workgroup share one codeword and meet at workgroup barriers.
 #include "gf3rx_host.h"
+#include "gf3rx_demap.h"
 
 // The decoder's parity contract is bit-exactness with a float32 NumPy restatement of the same schedule
 // (tests/ldpc_ref.py): no multiply-add may be contracted into an FMA in this unit.
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(256) void csi_weight_kernel(CsiArgs a) {
         const int l = (int)(fl - f * a.D);
         const cplx hs = a.Hs[f * a.K + kk], he = a.He[f * a.K + kk];
         const double s = hypot(hs.x, hs.y), e = hypot(he.x, he.y);
-        const double mag = s + (e - s) * (l + a.P / 2.0) / (double)(a.D + a.P);
+        const double mag = csi_mag(s, e, l, a.P, a.D);
         const double wgt = mag * mag;
         float* p = a.llr + (fl * a.C + pos) * a.mu;
         for (int b = 0; b < a.mu; ++b) p[b] = (float)((double)p[b] * wgt);

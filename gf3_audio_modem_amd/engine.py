@@ -542,6 +542,61 @@ class Engine:
         self._check(self.lib.gf3_soft_demap_nw(self._h, _ptr(eq), _ptr(var), F, _ptr(llr), self._stream()))
         return llr
 
+    def combine_branches(self, eqs, Hs=None, He=None, var=None, out=None, want=("eq", "llr")):
+        """Receive diversity (gf3_combine_branches): maximal-ratio combining of B = len(eqs) <= 4 branches' equalised
+        symbols, eqs[b] = demod_frames' 'eq' [F*D, C] of recording b of ONE transmission (each synchronised and demodulated
+        on its own).  z = sum_b w_b z_b / W, W = sum_b w_b.  Give either Hs and He (B tensors [F, K] each: w_b = the
+        |H^|^2 of soft_demap_csi) or var (B tensors [F, C] from noise_estimate: w_b = 1 / max(var_b, 1e-6 vbar), vbar the
+        packet's mean variance over all branches and carriers; 1 where vbar is 0 or not finite).  A weight whose input is
+        not finite and a symbol that is not finite drop out of both sums (w_b = 0); where every branch does, z = 0 and the
+        LLRs are +0.  want: any of "eq" (z, complex128 [F*D, C]), "w" (W, float64 [F*D, C]), "llr" (maxlog(z; 1) W,
+        float32 [F*D*C*mu], order and sign as soft_demap_csi).  out: optional dict of tensors to write the wanted entries
+        into; out["eq"] must be none of eqs.  -> dict of the wanted entries.  Fixed summation order: two calls give
+        identical bytes."""
+        cfg = self.cfg
+        if (Hs is None) != (He is None):
+            raise ValueError("combine_branches: Hs and He go together")
+        if (Hs is None) == (var is None):
+            raise ValueError("combine_branches: give either Hs and He (csi weights) or var (noise weights), not both or neither")
+        eqs = list(eqs)
+        B = len(eqs)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"combine_branches: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        want = tuple(want)
+        if not want or any(k not in ("eq", "w", "llr") for k in want):
+            raise ValueError(f"combine_branches: want must name at least one of 'eq', 'w', 'llr', not {want!r}")
+        eqs = [self._dev(e) for e in eqs]
+        eq0, F = self._eq_packets(eqs[0], "combine_branches")
+        if any(e.numel() != eq0.numel() for e in eqs):
+            raise ValueError("combine_branches: every branch needs eq [F*D, C] of the same F")
+        sides = []
+        for name, xs, dtype, per, dim in (("Hs", Hs, torch.complex128, cfg.K, "K"), ("He", He, torch.complex128, cfg.K, "K"),
+                                          ("var", var, torch.float64, cfg.C, "C")):
+            if xs is None:
+                sides.append(None)
+                continue
+            xs = [self._dev(x, dtype) for x in xs]
+            if len(xs) != B:
+                raise ValueError(f"combine_branches: {name} holds {len(xs)} branches, eqs {B}")
+            if any(x.numel() != F * per for x in xs):
+                raise ValueError(f"combine_branches: every {name} must be [F, {dim}] for eq [F*D, C]")
+            sides.append(xs)
+        out = dict(out or {})
+        if any(k not in want for k in out):
+            raise ValueError(f"combine_branches: out holds {sorted(out)}, want is {want!r}")
+        kinds = {"eq": ((F * cfg.D, cfg.C), torch.complex128, "F*D*C"), "w": ((F * cfg.D, cfg.C), torch.float64, "F*D*C"),
+                 "llr": ((F * cfg.D * cfg.C * cfg.mu,), torch.float32, "F*D*C*mu")}
+        o = {k: self._out(out.get(k), kinds[k][0], kinds[k][1], kinds[k][2], name=f"combine_branches: out[{k!r}]") for k in want}
+        if F and "eq" in o and any(o["eq"].data_ptr() == e.data_ptr() for e in eqs):
+            raise ValueError("combine_branches: out['eq'] must be none of eqs (the other branches' sums still read it)")
+
+        def table(xs):
+            return None if xs is None else (C.c_void_p * B)(*[x.data_ptr() for x in xs])
+        mode = _lib.GF3_COMBINE_NOISE if var is not None else _lib.GF3_COMBINE_CSI
+        self._check(self.lib.gf3_combine_branches(self._h, B, table(eqs), mode, table(sides[0]), table(sides[1]), table(sides[2]), F,
+                                                  _ptr(o.get("eq")), _ptr(o.get("w")), _ptr(o.get("llr")), self._stream()))
+        return o
+
     def noise_estimate2(self, eq):
         """Per-carrier AND per-symbol noise variance of each packet from one pass over eq [F*D, C]
         (gf3_noise_estimate_cs): var_c [F, C] is noise_estimate's output bit for bit, var_s [F, D] the mean over the

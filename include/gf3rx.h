@@ -506,6 +506,37 @@ int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32
                    void *stream);
 
 /*
+ * Receive diversity (not in the reference): maximal-ratio combining of the equalised symbols of B recordings of ONE
+ * transmission (the two channels of a stereo recording, a second microphone), each synchronised and demodulated on its
+ * own.  A reflection puts deep nulls into each microphone's transfer function; another microphone has them at other
+ * frequencies, and the weights fill each branch's nulls from the others.
+ *   z[f, l, c] = (sum_b w_b z_b) / W,  W = sum_b w_b,  z_b = eq_b[f, l, c], summed for b ascending; 0 + 0i where W = 0.
+ *   mode GF3_COMBINE_CSI:    w_b[f, l, c] = (|Hs_b| + (|He_b| - |Hs_b|) (l + P/2) / (D + P))^2 at the carrier's bin: the
+ *     weight of gf3_soft_demap_csi.  d_Hs_c128[b], d_He_c128[b]: [F, K] of gf3_demod_frames; d_var_f64 is not read.
+ *   mode GF3_COMBINE_NOISE:  vbar[f] = the mean over all b and c of var_b[f, c];  w_b[f, c] = 1 / max(var_b[f, c],
+ *     1e-6 vbar[f]), and 1 for the whole packet where vbar[f] is 0 or not finite: the rule of gf3_soft_demap_nw taken
+ *     over all branches, so a noiseless branch dominates a noisy one.  d_var_f64[b]: [F, C] of gf3_noise_estimate on
+ *     branch b; d_Hs_c128, d_He_c128 are not read.
+ *   In both modes w_b = 0 where its input (|Hs_b|, |He_b| or var_b) is not finite, where it comes out not finite, or
+ *   where z_b is not finite in either part: that symbol of that branch is left out of both sums.
+ *   d_eq_c128, d_Hs_c128, d_He_c128, d_var_f64: HOST arrays of B device pointers (read during the call only), 1 <= B <=
+ *   GF3_MAX_BRANCHES; d_eq_c128[b] is [F*D, C] as gf3_demod_frames writes it.  Outputs, each optional, at least one:
+ *     d_eq_out_c128 [F*D, C]  z (none of the d_eq_c128[b])
+ *     d_wsum_f64 [F*D, C]     W
+ *     d_llr_f32 [F*D*C*mu]    (float)(maxlog(z; sigma^2 = 1) * W) in the order and sign of gf3_soft_demap_csi; +0 where W = 0
+ *   With B = 1 the LLRs are those of gf3_soft_demap_csi / gf3_soft_demap_nw to float32 rounding.
+ *   GF3_EINVAL (the text names gf3_combine_branches) for a null context, B out of range, a null branch pointer, no
+ *   output, F < 0, an unknown mode, more than 65535 packets.  F == 0 is a no-op.  One launch, no allocation, no host
+ *   synchronisation, asynchronous on `stream`; every sum in a fixed order, no atomics: two calls give identical bytes.
+ */
+#define GF3_MAX_BRANCHES 4
+#define GF3_COMBINE_CSI 0
+#define GF3_COMBINE_NOISE 1
+int gf3_combine_branches(gf3_ctx *ctx, int32_t B, const void *const *d_eq_c128, int32_t mode,
+                         const void *const *d_Hs_c128, const void *const *d_He_c128, const double *const *d_var_f64,
+                         int64_t F, void *d_eq_out_c128, double *d_wsum_f64, float *d_llr_f32, void *stream);
+
+/*
  * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
  * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
  * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
