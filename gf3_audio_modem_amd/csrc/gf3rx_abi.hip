@@ -24,17 +24,14 @@ static DemodArgs demod_args(const gf3_ctx* c) {
     return a;
 }
 
-// What the calling thread's last demodulation did (gf3_demod_frames_last): kept per host thread like every other diagnostic.
-static thread_local struct { const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0; } g_demod_last;
+static thread_local LastCall g_demod_last;                    // (gf3_demod_frames_last)
 
 // Whether precision -1 (auto: plain gf3_demod_frames, gf3_demod_frames_ex) takes the screened path where it applies.
 // Decided by the same-box A/B of DESIGN 3.5 / 4; precision 1 asks for the screen explicitly either way.
 #define GF3_DEMOD_AUTO_SCREEN 1
 
-extern "C" int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx* c, int64_t F) {
-    if (!c || F < 0) return 0;
-    return (int64_t)((size_t)F * sizeof(int) + 64);           // [count | pad | listed packet numbers]
-}
+// [count | pad | listed packet numbers]
+extern "C" int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx* c, int64_t F) { return list_workspace_bytes(c, F); }
 
 // precision 0: all fp64 (the reference of the screened path's tests).  1: the fp32 screen of the data symbols under a
 // proven bound (gf3rx_dscreen.h), then the fp64 kernel on the packets it listed, whenever that applies -- the reference
@@ -54,7 +51,7 @@ static int demod_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, const i
     DemodArgs a = demod_args(c);
     a.in = d_in; a.n_in = n_in; a.off = d_off; a.bits = d_bits; a.stamps = c->stamps;
     a.eq = (cplx*)d_eq; a.Hs = (cplx*)d_Hs; a.He = (cplx*)d_He; a.slope = d_slope; a.Hest = (cplx*)d_Hest; a.status = d_status;
-    g_demod_last.ctx = c; g_demod_last.stream = stream; g_demod_last.path = 2; g_demod_last.cap = 0;
+    g_demod_last.set(c, stream, 2, 0);
     // long packets, few at a time: pilot sums, estimate and data symbols as three launches (gf3rx_demod_split.hip)
     if (d_work && demod_wants_split(c, F, mode)) {
         if (screen_only) return fail(c, GF3_EINVAL, "gf3_debug_demod_screen: the two-phase form is not screened");
@@ -67,8 +64,8 @@ static int demod_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, const i
     if (screen_only && !list_ws) return fail(c, GF3_EINVAL, "gf3_debug_demod_screen: the screen does not apply to this context");
     if (list_ws) {
         a.tw32 = c->d_tw32; a.dwork = (int*)list_ws; a.dbg_ep = dbg_ep; a.dbg_E = dbg_E;
-        g_demod_last.path = 0; g_demod_last.cap = (int32_t)F;
-        HIPCHK(c, hipMemsetAsync(a.dwork, 0, 64, st));
+        g_demod_last.set(c, stream, 0, (int32_t)F);
+        HIPCHK(c, hipMemsetAsync(a.dwork, 0, LIST_HEAD, st));
         HIPCHK(c, launch_demod_screen(c, a, F, st));
         if (dbg_cls) HIPCHK(c, launch_demod_verdicts(a.dwork, dbg_cls, F, st));
         if (screen_only) return GF3_OK;
@@ -99,11 +96,7 @@ extern "C" int gf3_demod_frames(gf3_ctx* c, const void* d_in, int64_t n_in, cons
     return gf3_demod_frames_px(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, nullptr, 1, -1, stream);
 }
 extern "C" int gf3_demod_frames_last(const gf3_ctx* c, void* stream, int32_t* path, int32_t* listed_capacity) {
-    if (!c || !path) return fail(c, GF3_EINVAL, "gf3_demod_frames_last: null argument");
-    const bool mine = g_demod_last.ctx == c && g_demod_last.stream == stream;
-    *path = mine ? g_demod_last.path : -1;
-    if (listed_capacity) *listed_capacity = mine ? g_demod_last.cap : 0;
-    return GF3_OK;
+    return g_demod_last.query("gf3_demod_frames_last", c, stream, path, listed_capacity);
 }
 // tests: the screening pass alone -- the fp32 rotated symbols of the data carriers [F][D][C] (data_bins order), the bound
 // per symbol [F][D], the verdict per packet (0 decided, 1 listed), the listed packets in d_list; d_bits gets the screen's rows
@@ -177,8 +170,8 @@ extern "C" int gf3_tx_frames(gf3_ctx* c, const uint8_t* d_bits_packed, const voi
 struct ScArgs { const void* in; int dt; int64_t S; int L; int N; int64_t* out; };
 
 __global__ __launch_bounds__(1024) void schmidl_cox_kernel(ScArgs a) {
-    __shared__ double wsum[16];
-    __shared__ double bval[16];
+    __shared__ double wsum[16];                // (its own scan, not block_scan: doubles, whose sum depends on the order
+    __shared__ double bval[16];                //  carry + woff + (incl - run) -- an integer helper would re-associate it)
     __shared__ long long bidx[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int ITEMS = 4;

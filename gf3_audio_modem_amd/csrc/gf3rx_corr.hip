@@ -1,6 +1,7 @@
 // libgf3rx -- the chirp matched filter in fp64: one search window per workgroup (frames), and the uniformly
 // partitioned overlap-save over whole streams (the fallback and `d_corr` path of gf3_sync_stream, and gf3_sync_chunk).
 #include "gf3rx_host.h"
+#include "gf3rx_peak.h"
 
 // ============================================================================
 // chirp matched filter by partitioned FFT correlation, one search window per workgroup
@@ -121,21 +122,17 @@ GF3_DEV void corr_window(const CorrArgs& a, const int64_t b, double2* smem) {
     lds_barrier();
     const double* y = (const double*)yb;
 
-    // ---- peak rule on the window (OFDM.py:359-361): normalise by the max, first
-    // local extremum above thresh
+    // ---- peak rule on the window (gf3rx_peak.h): normalise by the max, first local extremum above thresh
     double mx = -INFINITY;
     for (int j = tid; j < W; j += T) mx = fmax(mx, y[j]);
     mx = block_max(mx, scratch);
     int first = 0x7fffffff;
-    // Lags that cannot reach the threshold skip the three divisions (y < thresh*max*(1-1e-6) implies
-    // fl(y/max) < thresh; same prefilter as pk_candidates): only the few lags around the peak pay for them.
-    const bool filt = mx > 0.0 && a.thresh > 0.0 && mx < INFINITY && a.thresh < INFINITY;
-    const double lim = filt ? a.thresh * mx * (1.0 - 1e-6) : -INFINITY;
+    // Lags that cannot reach the threshold skip the three divisions: only the few lags around the peak pay for them.
+    const double lim = peak_limit(mx, a.thresh);
     for (int j = 1 + tid; j < W - 1; j += T) {
         const double y0 = y[j];
         if (!(y0 < lim)) {
-            const double pm1 = y[j - 1] / mx, p0 = y0 / mx, pp1 = y[j + 1] / mx;
-            if (((p0 - pm1) * (pp1 - p0) <= 0.0) && (p0 > a.thresh)) first = min(first, j);
+            if (is_peak(y[j - 1] / mx, y0 / mx, y[j + 1] / mx, a.thresh)) first = min(first, j);
         }
     }
     first = block_min_i(first, (int*)(scratch + 16));
@@ -280,9 +277,8 @@ __global__ __launch_bounds__(NC / 8, 2) void ols_kernel(OlsArgs a) {
             }
         }
     }
-    mx = block_max(mx, (double*)lds);                 // (starts with a barrier: every wave is done reading yb)
-    const int anynan = __syncthreads_or(nan ? 1 : 0);  // np.amax propagates NaN (OFDM.py:359): so does this maximum
-    if (tid == 0) a.part[item] = anynan ? NAN : mx;
+    mx = block_amax(mx, nan, (double*)lds);           // (starts with a barrier: every wave is done reading yb)
+    if (tid == 0) a.part[item] = mx;
 }
 
 hipError_t run_corr(const gf3_ctx* c, const CorrPlan& pl, const CorrArgs& a, int64_t grid, hipStream_t st, bool listed) {

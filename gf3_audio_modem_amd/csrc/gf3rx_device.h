@@ -518,6 +518,26 @@ GF3_DEV int block_min_i(int x, int* scratch) {
     for (int i = 1; i < nw; ++i) s = min(s, scratch[i]);
     return s;
 }
+// Inclusive prefix sum over the wave: lane l gets x_0 + ... + x_l.
+template <typename T> GF3_DEV T wave_scan(T x, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const T y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+    return x;
+}
+// Block-wide exclusive scan of a per-thread integer count (int / int64_t) over nw waves: returns the sum of c over the
+// threads before this one, `total` gets the sum over the block.  wsum: nw elements of LDS; one barrier inside -- a caller
+// that loops needs one of its own before the next call.  Integers only: schmidl_cox_kernel (gf3rx_abi.hip) scans doubles, whose
+// result depends on the order of its additions, and keeps its own text.
+template <typename T> GF3_DEV T block_scan(T c, T* wsum, int nw, T& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T x = wave_scan(c, lane);
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    T woff = 0;
+    total = 0;
+    for (int w = 0; w < nw; ++w) { if (w < wave) woff += wsum[w]; total += wsum[w]; }
+    return woff + (x - c);
+}
 
 // sin/cos by Cody-Waite reduction to [-pi/4, pi/4] (three-part pi/2, exact with fma for
 // |x| < ~1e6) and the fdlibm kernel polynomials: <= 1 ulp there, ~30 fp64 ops.

@@ -9,7 +9,7 @@
 //   gf3rx_screen.hip         scr_ring_kernel, scr_ols_kernel, scr_refine_kernel (gf3rx_screen.h)
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
 //   gf3rx_stamp.cpp          the build stamp (source hash), recompiled on every change
-//   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide
+//   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide (the peak rule they share with corr_kernel: gf3rx_peak.h)
 //   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
 //   gf3rx_outer.hip          rs_encode_kernel, rs_recover_kernel + gf3_outer_encode, gf3_outer_recover (field arithmetic: gf3rx_outer.h)
 //   gf3rx_crc.hip            crc_kernel + gf3_crc_attach, gf3_crc_check (per-codeword CRC-32)
@@ -334,6 +334,27 @@ int tx_launch(gf3_ctx* c, const TxArgs& a, int64_t F, hipStream_t st);
 // nullptr: none can be had now (the stream is being captured and nothing large enough exists, the table is full, the
 // allocation failed) -- the caller then runs its fp64 path
 void* ctx_workspace(gf3_ctx* c, hipStream_t st, int slot, int64_t bytes);
+// The list protocol the two screened dispatchers share (frames sync: sync_frames_impl, QPSK demodulation: demod_frames_impl).
+// The screen appends what it cannot decide to a workspace [count | pad to LIST_HEAD bytes | F numbers] (int each); the
+// dispatcher zeroes the head before the screen, and the fp64 pass reads the list.
+enum { LIST_HEAD = 64 };
+inline int64_t list_workspace_bytes(const gf3_ctx* c, int64_t F) {
+    if (!c || F < 0) return 0;
+    return (int64_t)((size_t)F * sizeof(int) + LIST_HEAD);
+}
+// What the calling thread's last call of a dispatcher did -- each keeps one thread_local record, like every other
+// diagnostic -- and the answer to its *_last query: path 0 screened | 2 all fp64 | -1 no such call on this context and stream.
+struct LastCall {
+    const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0;
+    void set(const gf3_ctx* c, void* st, int32_t p, int32_t n) { ctx = c; stream = st; path = p; cap = n; }
+    int query(const char* who, const gf3_ctx* c, void* st, int32_t* p, int32_t* n) const {
+        if (!c || !p) return fail(c, GF3_EINVAL, "%s: null argument", who);
+        const bool mine = ctx == c && stream == st;
+        *p = mine ? path : -1;
+        if (n) *n = mine ? cap : 0;
+        return GF3_OK;
+    }
+};
 // gf3rx_demod_screen.hip: the screened QPSK demodulation (gf3rx_dscreen.h) and the fp64 kernel on the packets it listed
 bool demod_screen_applies(const gf3_ctx* c);
 hipError_t launch_demod_screen(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);

@@ -2,6 +2,7 @@
 // list of cells, the reference's rule on the re-evaluated fp64 values.  Non-template kernels: included by exactly one
 // translation unit (gf3rx_sync.hip).
 #pragma once
+#include "gf3rx_peak.h"
 #include "gf3rx_screen_defs.h"
 
 // One list serves both questions.  With Mlo <= M:  a lag that could be the maximum has an upper bound >= Mlo, a lag
@@ -23,9 +24,7 @@ __global__ __launch_bounds__(SCR_MLO_THREADS) void scr_mlo_kernel(const float* b
             __threadfence();
             m = scr_unkey(atomicMax(&misc->mlo_key, 0ull));
             misc->Mlo = m;
-            // (the prefilter of pk_candidates: only a positive finite maximum and threshold exclude anything)
-            const bool filt = m > 0.0 && thresh > 0.0 && m < INFINITY && thresh < INFINITY;
-            misc->lim = filt ? fmin(m, thresh * m * (1.0 - 1e-6)) : -INFINITY;
+            misc->lim = fmin(m, peak_limit(m, thresh));                       // (-INFINITY: nothing can be excluded)
         }
     }
 }
@@ -130,10 +129,7 @@ __global__ __launch_bounds__(64) void scr_scatter_kernel(const unsigned long lon
     const int lane = threadIdx.x;
     unsigned long long m = masks[(int64_t)blockIdx.x * SCR_LIST_SEGS + lane];
     const int pc = __popcll(m);
-    int x = pc;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    int64_t o = offsets[blockIdx.x] + (x - pc);
+    int64_t o = offsets[blockIdx.x] + (wave_scan(pc, lane) - pc);              // (one wave: the block scan's wave step is all of it)
     const int64_t c0 = ((int64_t)blockIdx.x * SCR_LIST_SEGS + lane) * 64;
     while (m) {
         const int j = __ffsll((long long)m) - 1;
@@ -142,8 +138,8 @@ __global__ __launch_bounds__(64) void scr_scatter_kernel(const unsigned long lon
     }
 }
 
-// candidates of every listed cell: the reference's rule on the fp64 values, division by the maximum first
-// (OFDM.py:359-361).  One thread per cell; bit j of the mask: zeros-index 14 c + j is a candidate.
+// candidates of every listed cell: the reference's rule on the fp64 values, division by the maximum first, then is_peak
+// (gf3rx_peak.h).  One thread per cell; bit j of the mask: zeros-index 14 c + j is a candidate.
 __global__ void scr_decide_kernel(const int64_t* cells, const double* cell_val, ScrMisc* misc, int64_t nz, double thresh,
                                   unsigned* cell_mask, int64_t* cell_cnt) {
     if (misc->status & 1) return;
@@ -158,7 +154,7 @@ __global__ void scr_decide_kernel(const int64_t* cells, const double* cell_val, 
     unsigned mk = 0;
 #pragma unroll
     for (int j = 0; j < GF3_SCR_CELL; ++j) {
-        const bool cand = (m0 + j < nz) && ((p[j + 1] - p[j]) * (p[j + 2] - p[j + 1]) <= 0.0) && (p[j + 1] > thresh);
+        const bool cand = (m0 + j < nz) && is_peak(p[j], p[j + 1], p[j + 2], thresh);
         mk |= cand ? (1u << j) : 0u;
     }
     cell_mask[i] = mk;

@@ -2,6 +2,7 @@
 // gf3_sync_stream(_ex), the piecewise form for host ingest (gf3_sync_chunk / gf3_sync_decide), and the peak-picking
 // kernels they share.  The heavy kernels are launched through gf3rx_screen.hip and gf3rx_corr.hip.
 #include "gf3rx_host.h"
+#include "gf3rx_peak.h"
 #include "gf3rx_screen_list.h"
 
 // ... and the diagnostics of the calling thread's last gf3_sync_stream / gf3_sync_stream_ex (gf3_sync_stream_info)
@@ -9,19 +10,30 @@ static thread_local int64_t g_last_info[4] = {0, 0, 0, 0};
 // Where a call reads its few result words back to: 256 bytes of PINNED host memory per calling thread (allocated on the
 // thread's first call and released when the thread ends -- a pool that is recreated per job does not accumulate pinned
 // pages; a copy into pageable memory goes through the runtime's staging path, which costs a call tens of microseconds).
-// nullptr if the allocation fails -- the caller then copies into a local variable as before.
+// If the allocation fails the words go to the page's own pageable bytes instead.
 struct ReadbackPage {
     void* p = nullptr;
-    bool tried = false;
+    alignas(16) char local[256];
+    ReadbackPage() { if (hipHostMalloc(&p, sizeof(local), hipHostMallocPortable) != hipSuccess) { p = nullptr; (void)hipGetLastError(); } }
     ~ReadbackPage() { if (p) { (void)hipHostFree(p); p = nullptr; } }   // (a failure at process teardown is of no consequence)
 };
-static void* readback_buffer() {
+// The read-back of a call: `bytes` from d_src -- and, behind them, bytes2 from d_src2 when given -- to the calling thread's
+// page, the stream synchronised; *h = the host copy (valid until the thread's next read-back).
+static int read_back(const gf3_ctx* c, hipStream_t st, const void** h, const void* d_src, size_t bytes,
+                     const void* d_src2 = nullptr, size_t bytes2 = 0) {
     static thread_local ReadbackPage page;
-    if (!page.tried) {
-        page.tried = true;
-        if (hipHostMalloc(&page.p, 256, hipHostMallocPortable) != hipSuccess) { page.p = nullptr; (void)hipGetLastError(); }
-    }
-    return page.p;
+    char* dst = page.p ? (char*)page.p : page.local;
+    HIPCHK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
+    if (d_src2) HIPCHK(c, hipMemcpyAsync(dst + bytes, d_src2, bytes2, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    *h = dst;
+    return GF3_OK;
+}
+// {count, status} of the suppression walk (pk_nms) -> *n_peaks, and GF3_ERANGE when the peaks did not fit
+static int finish_peaks(const gf3_ctx* c, const char* who, const int64_t* h, int64_t cap, int64_t* n_peaks) {
+    *n_peaks = h[0];
+    if (h[1] == 2) return fail(c, GF3_ERANGE, "%s: %lld peaks exceed capacity %lld", who, (long long)h[0], (long long)cap);
+    return GF3_OK;
 }
 
 // ============================================================================
@@ -30,27 +42,27 @@ static void* readback_buffer() {
 #define PK_THREADS 256
 #define PK_ITEMS 8
 
-__global__ void pk_max_final(const double* partial, int n, double* out) {
+// out[0] = amax(part[0..n)) with NumPy's NaN rule (block_amax): the stream's maximum from the ols workgroups' maxima, or one
+// piece's own.  run_max (optional): the running maximum of a stream that arrives in pieces, run_max[0] = amax(run_max[0], out[0]).
+__global__ void ck_fold_max(const double* part, int n, double* out, double* run_max) {
     __shared__ double scratch[16];
     double mx = -INFINITY;
     bool nan = false;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { const double v = partial[i]; mx = fmax(mx, v); nan = nan || !(v == v); }
-    mx = block_max(mx, scratch);
-    const int anynan = __syncthreads_or(nan ? 1 : 0);
-    if (threadIdx.x == 0) out[0] = anynan ? NAN : mx;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) { const double v = part[i]; mx = fmax(mx, v); nan = nan || !(v == v); }
+    mx = block_amax(mx, nan, scratch);
+    if (threadIdx.x == 0) {
+        out[0] = mx;
+        if (run_max) { const double run = run_max[0]; run_max[0] = (!(mx == mx) || !(run == run)) ? NAN : fmax(run, mx); }
+    }
 }
 // pass 0: count per block; pass 1: write ascending indices at the block's offset (blocks that counted none return
 // at once, and candidates are a handful per chirp, so the second pass costs next to nothing).
-// Candidate at i  <=>  (p1-p0)(p2-p1) <= 0 and p1 > thresh with p = P/max (OFDM.py:359-361: the division is done
-// first there, so it is done here too -- one correctly rounded division per lag, shared by its three uses).
-// Lags that cannot reach the threshold skip the divisions: P1 < thresh*max*(1-1e-6) implies fl(P1/max) < thresh.
+// Candidate at i  <=>  is_peak on p = P / max; lags under peak_limit skip the divisions (gf3rx_peak.h).
 __global__ void pk_candidates(const double* __restrict__ P, int64_t nz, const double* mxp, double thresh,
                               int64_t* counts, const int64_t* offsets, int64_t* cand) {
     __shared__ int wsum[PK_THREADS / 64];
     if (offsets && counts[blockIdx.x] == 0) return;
-    const double mx = mxp[0];
-    const bool filt = mx > 0.0 && thresh > 0.0 && mx < INFINITY && thresh < INFINITY;
-    const double lim = filt ? thresh * mx * (1.0 - 1e-6) : -INFINITY;
+    const double mx = mxp[0], lim = peak_limit(mx, thresh);
     const int64_t base = ((int64_t)blockIdx.x * PK_THREADS + threadIdx.x) * PK_ITEMS;
     int c = 0;
     unsigned flags = 0;
@@ -67,19 +79,13 @@ __global__ void pk_candidates(const double* __restrict__ P, int64_t nz, const do
             for (int k = 0; k < PK_ITEMS + 2; ++k) q[k] = q[k] / mx;
 #pragma unroll
             for (int k = 0; k < PK_ITEMS; ++k)
-                if (k < cnt && ((q[k + 1] - q[k]) * (q[k + 2] - q[k + 1]) <= 0.0) && (q[k + 1] > thresh)) { flags |= 1u << k; ++c; }
+                if (k < cnt && is_peak(q[k], q[k + 1], q[k + 2], thresh)) { flags |= 1u << k; ++c; }
         }
     }
-    // block-wide exclusive scan of c
-    int x = c;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < PK_THREADS / 64; ++w) { if (w < wave) woff += wsum[w]; total += wsum[w]; }
+    int total;
+    const int before = block_scan(c, wsum, PK_THREADS / 64, total);
     if (!offsets) { if (threadIdx.x == 0) counts[blockIdx.x] = total; return; }
-    int64_t o = offsets[blockIdx.x] + woff + (x - c);
+    int64_t o = offsets[blockIdx.x] + before;
     for (int k = 0; k < PK_ITEMS; ++k) if (flags & (1u << k)) cand[o++] = base + k;
 }
 #define SCAN_PER 16
@@ -92,20 +98,14 @@ __global__ void pk_scan(const int64_t* counts, int64_t n, int64_t* offsets, int6
     if (n_dev && (int64_t)n_dev[0] < n) n = n_dev[0] < 0 ? 0 : (int64_t)n_dev[0];
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int64_t base = 0; base < n; base += (int64_t)blockDim.x * SCAN_PER) {
         const int64_t i0 = base + (int64_t)threadIdx.x * SCAN_PER;
         int64_t loc[SCAN_PER];
         int64_t c = 0;
 #pragma unroll
         for (int k = 0; k < SCAN_PER; ++k) { loc[k] = (i0 + k < n) ? counts[i0 + k] : 0; c += loc[k]; }
-        int64_t x = c;
-        for (int d = 1; d < 64; d <<= 1) { const int64_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int64_t woff = 0, tot = 0;
-        for (int w = 0; w < nw; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        int64_t o = carry + woff + (x - c);
+        int64_t tot;
+        int64_t o = carry + block_scan(c, wsum, (int)(blockDim.x >> 6), tot);
 #pragma unroll
         for (int k = 0; k < SCAN_PER; ++k) { if (i0 + k < n) offsets[i0 + k] = o; o += loc[k]; }
         __syncthreads();
@@ -206,8 +206,30 @@ struct StreamWs { int64_t plen, nz, nb_max, nb_c, nblk, nwin; size_t o_P, o_part
                   // screened path (gf3rx_screen.h); P32 overlays o_P, the per-workgroup counts / offsets overlay o_cnt / o_off
                   int64_t s_nblk, s_ncell, s_nwg, s_cap;
                   size_t o_sblk, o_smisc, o_segm, o_cell, o_cval, o_mask, o_ccnt, o_coff; };
+// ... and its typed pointers, carved out of a workspace once (the screened path's are meaningful when w.s_nblk > 0)
+struct StreamPtrs {
+    double *P, *part, *mx;                          // every lag in fp64, the ols workgroups' maxima, the maximum
+    int64_t *cnt, *offs, *cand, *total, *np;        // counts and their scan, candidates, their number, [count, status] of the walk
+    cplx* spec;
+    float *P32, *blk_max, *blk_err;                 // screened path: every lag in fp32 (overlays P), bound per block
+    ScrMisc* misc; int* mlo;                        // its scalars; the screen's running lower bound of the maximum (float bits)
+    unsigned long long* segm; unsigned* mask;       // hit mask per segment of 64 cells; candidate mask per listed cell
+    int64_t *cell, *ccnt, *coff; double* cval;      // listed cells, their candidate counts and scan, their 16 fp64 values each
+};
+static StreamPtrs stream_ptrs(const StreamWs& w, void* d_work) {
+    char* base = (char*)d_work;
+    StreamPtrs p;
+    p.P = (double*)(base + w.o_P); p.part = (double*)(base + w.o_part); p.spec = (cplx*)(base + w.o_spec);
+    p.cnt = (int64_t*)(base + w.o_cnt); p.offs = (int64_t*)(base + w.o_off); p.cand = (int64_t*)(base + w.o_cand);
+    p.mx = (double*)(base + w.o_misc); p.total = (int64_t*)(base + w.o_misc + 8); p.np = (int64_t*)(base + w.o_misc + 16);
+    p.P32 = (float*)(base + w.o_P); p.blk_max = (float*)(base + w.o_sblk); p.blk_err = p.blk_max + w.s_nblk;
+    p.misc = (ScrMisc*)(base + w.o_smisc); p.mlo = (int*)(base + w.o_smisc + sizeof(ScrMisc));
+    p.segm = (unsigned long long*)(base + w.o_segm); p.mask = (unsigned*)(base + w.o_mask); p.cval = (double*)(base + w.o_cval);
+    p.cell = (int64_t*)(base + w.o_cell); p.ccnt = (int64_t*)(base + w.o_ccnt); p.coff = (int64_t*)(base + w.o_coff);
+    return p;
+}
 static StreamWs stream_ws(const gf3_ctx* c, int64_t n) {
-    StreamWs w;
+    StreamWs w{};
     w.plen = n + c->Lc - 1; w.nz = w.plen - 2;
     w.nb_max = ((w.plen + c->stream_plan.Lp - 1) / c->stream_plan.Lp + OLS_B - 1) / OLS_B;      // one partial maximum per ols workgroup
     w.nb_c = (w.nz + PK_THREADS * PK_ITEMS - 1) / (PK_THREADS * PK_ITEMS);
@@ -249,6 +271,15 @@ static StreamWs stream_ws(const gf3_ctx* c, int64_t n) {
     w.total = o;
     return w;
 }
+// the all-fp64 overlap-save of d_in [n] into P (run_spec_ols)
+static OlsArgs ols_args(const gf3_ctx* c, const StreamWs& w, const StreamPtrs& p, const void* d_in, int64_t n, double* P) {
+    const CorrPlan& pl = c->stream_plan;
+    OlsArgs a{};
+    a.t = pl.t; a.in = d_in; a.n_in = n; a.dt = c->cfg.in_dtype;
+    a.Hq = pl.d_Hq; a.Q = pl.Q; a.H = pl.Lp; a.Lc = c->Lc;
+    a.spec = p.spec; a.nwin = w.nwin; a.plen = w.plen; a.corr = P; a.part = p.part;
+    return a;
+}
 extern "C" int64_t gf3_sync_stream_workspace_bytes(const gf3_ctx* c, int64_t n) {
     if (!c || n < 1) return 0;
     return (int64_t)stream_ws(c, n).total;
@@ -256,30 +287,18 @@ extern "C" int64_t gf3_sync_stream_workspace_bytes(const gf3_ctx* c, int64_t n) 
 
 // Screened path of gf3_sync_stream (gf3rx_screen.h).  Enqueues everything on `st`; the caller reads back
 // {peaks, suppression status} at np and the ScrMisc block.
-static int sync_stream_screened(const gf3_ctx* c, const void* d_r, int64_t n, const StreamWs& w, char* base, int64_t* d_peaks,
+static int sync_stream_screened(const gf3_ctx* c, const void* d_r, int64_t n, const StreamWs& w, const StreamPtrs& p, int64_t* d_peaks,
                                 int64_t cap, int mode, hipStream_t st) {
     const auto& sp = c->scr;
-    float* P32 = (float*)(base + w.o_P);
-    float* blk_max = (float*)(base + w.o_sblk);
-    float* blk_err = blk_max + w.s_nblk;
-    ScrMisc* misc = (ScrMisc*)(base + w.o_smisc);
-    int64_t* cnt = (int64_t*)(base + w.o_cnt);
-    int64_t* offs = (int64_t*)(base + w.o_off);
-    int64_t* total = (int64_t*)&misc->total;
+    ScrMisc* misc = p.misc;
+    int64_t* total = (int64_t*)&misc->total;           // (this path keeps its scalars in the ScrMisc block: one read-back)
     int64_t* np = (int64_t*)misc->np;
-    int64_t* cand = (int64_t*)(base + w.o_cand);
-    unsigned long long* segm = (unsigned long long*)(base + w.o_segm);
-    int64_t* cell = (int64_t*)(base + w.o_cell);
-    double* cval = (double*)(base + w.o_cval);
-    unsigned* mask = (unsigned*)(base + w.o_mask);
-    int64_t* ccnt = (int64_t*)(base + w.o_ccnt);
-    int64_t* coff = (int64_t*)(base + w.o_coff);
     const int dt = c->cfg.in_dtype;
     // (the scalars of the call, and behind them the screen's running lower bound of the maximum: float bits, 0 = none yet)
     HIPCHK(c, hipMemsetAsync(misc, 0, sizeof(ScrMisc) + 16, st));
     {   // 1. every lag in fp32, with a bound per block
         ScreenArgs a{d_r, n, dt, sp.d_tw, sp.d_twn, sp.d_Hs, sp.d_H0N, sp.d_Hinf, sp.Q, sp.H, c->Lc, w.s_nblk, w.plen,
-                     P32, blk_max, blk_err, (int*)(base + w.o_smisc + sizeof(ScrMisc)), (float)c->cfg.thresh, nullptr, nullptr, 0,
+                     p.P32, p.blk_max, p.blk_err, p.mlo, (float)c->cfg.thresh, nullptr, nullptr, 0,
                      (unsigned long long*)&misc->status};
         HIPCHK(c, launch_screen(c, a, mode == 3, st));
     }
@@ -287,26 +306,26 @@ static int sync_stream_screened(const gf3_ctx* c, const void* d_r, int64_t n, co
     {
         int64_t g = (w.s_nblk + SCR_MLO_THREADS * 4 - 1) / (SCR_MLO_THREADS * 4);
         g = g < 1 ? 1 : (g > 128 ? 128 : g);
-        hipLaunchKernelGGL(scr_mlo_kernel, dim3((unsigned)g), dim3(SCR_MLO_THREADS), 0, st, (const float*)blk_max, (const float*)blk_err, w.s_nblk, misc,
+        hipLaunchKernelGGL(scr_mlo_kernel, dim3((unsigned)g), dim3(SCR_MLO_THREADS), 0, st, (const float*)p.blk_max, (const float*)p.blk_err, w.s_nblk, misc,
                            (double)c->cfg.thresh);
     }
-    hipLaunchKernelGGL(scr_flag_kernel, dim3((unsigned)w.s_nwg), dim3(SCR_LIST_THREADS), 0, st, (const float*)P32, (const float*)blk_max,
-                       (const float*)blk_err, sp.H, w.plen, w.s_ncell, (const ScrMisc*)misc, segm, cnt);
-    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)cnt, w.s_nwg, offs, total, (const long long*)nullptr, (const long long*)nullptr);
-    hipLaunchKernelGGL(scr_scatter_kernel, dim3((unsigned)w.s_nwg), dim3(64), 0, st, (const unsigned long long*)segm, (const int64_t*)cnt,
-                       (const int64_t*)offs, (const int64_t*)total, misc, cell, w.s_cap);
+    hipLaunchKernelGGL(scr_flag_kernel, dim3((unsigned)w.s_nwg), dim3(SCR_LIST_THREADS), 0, st, (const float*)p.P32, (const float*)p.blk_max,
+                       (const float*)p.blk_err, sp.H, w.plen, w.s_ncell, (const ScrMisc*)misc, p.segm, p.cnt);
+    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)p.cnt, w.s_nwg, p.offs, total, (const long long*)nullptr, (const long long*)nullptr);
+    hipLaunchKernelGGL(scr_scatter_kernel, dim3((unsigned)w.s_nwg), dim3(64), 0, st, (const unsigned long long*)p.segm, (const int64_t*)p.cnt,
+                       (const int64_t*)p.offs, (const int64_t*)total, misc, p.cell, w.s_cap);
     {   // 3. their lags in fp64, once (the maximum is kept as the cells complete); the reference's rule on those values
-        RefineArgs a{d_r, n, dt, c->d_chirp, c->Lc, cell, misc, w.plen, cval, c->d_chirp_t, c->stamps};
+        RefineArgs a{d_r, n, dt, c->d_chirp, c->Lc, p.cell, misc, w.plen, p.cval, c->d_chirp_t, c->stamps};
         HIPCHK(c, launch_refine(c, a, w.s_cap, st));
     }
-    hipLaunchKernelGGL(scr_decide_kernel, dim3((unsigned)((w.s_cap + 255) / 256)), dim3(256), 0, st, (const int64_t*)cell, (const double*)cval, misc,
-                       w.nz, (double)c->cfg.thresh, mask, ccnt);
+    hipLaunchKernelGGL(scr_decide_kernel, dim3((unsigned)((w.s_cap + 255) / 256)), dim3(256), 0, st, (const int64_t*)p.cell, (const double*)p.cval, misc,
+                       w.nz, (double)c->cfg.thresh, p.mask, p.ccnt);
     // 4. candidates in ascending order, suppression walk
-    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)ccnt, w.s_cap, coff, total, (const long long*)&misc->ncell,
+    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)p.ccnt, w.s_cap, p.coff, total, (const long long*)&misc->ncell,
                        (const long long*)&misc->status);
-    hipLaunchKernelGGL(scr_expand_kernel, dim3((unsigned)((w.s_cap + 255) / 256)), dim3(256), 0, st, (const int64_t*)cell, (const unsigned*)mask,
-                       (const int64_t*)coff, (const ScrMisc*)misc, cand, w.nz + 2);
-    hipLaunchKernelGGL(pk_nms, dim3(1), dim3(NMS_THREADS), 0, st, (const int64_t*)cand, (const int64_t*)total,
+    hipLaunchKernelGGL(scr_expand_kernel, dim3((unsigned)((w.s_cap + 255) / 256)), dim3(256), 0, st, (const int64_t*)p.cell, (const unsigned*)p.mask,
+                       (const int64_t*)p.coff, (const ScrMisc*)misc, p.cand, w.nz + 2);
+    hipLaunchKernelGGL(pk_nms, dim3(1), dim3(NMS_THREADS), 0, st, (const int64_t*)p.cand, (const int64_t*)total,
                        (int64_t)c->Lc, w.nz, d_peaks, cap, np);
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
@@ -348,16 +367,9 @@ extern "C" int gf3_sync_stream_ex(const gf3_ctx* c, const void* d_r, int64_t n, 
         return fail(c, GF3_EINVAL, "gf3_sync_stream: bad argument (mode must be 0 by length, 1 fp64 only, 2 always screen, 3 always screen with the general kernel)");
     hipStream_t st = (hipStream_t)stream;
     const StreamWs w = stream_ws(c, n);
-    char* base = (char*)d_work;
-    double* P = d_corr ? d_corr : (double*)(base + w.o_P);
-    double* part = (double*)(base + w.o_part);
-    int64_t* cnt = (int64_t*)(base + w.o_cnt);
-    int64_t* offs = (int64_t*)(base + w.o_off);
-    int64_t* cand = (int64_t*)(base + w.o_cand);
-    double* mx = (double*)(base + w.o_misc);
-    int64_t* total = (int64_t*)(base + w.o_misc + 8);
-    int64_t* np = (int64_t*)(base + w.o_misc + 16);        // [count, status]
-    const CorrPlan& pl = c->stream_plan;
+    const StreamPtrs p = stream_ptrs(w, d_work);
+    double* P = d_corr ? d_corr : p.P;
+    const void* h = nullptr;
     // diagnostics of this call: the caller's array when given, and always the calling thread's own copy
     // (gf3_sync_stream_info); nothing of a call is kept in the context
     int64_t info_local[4];
@@ -365,47 +377,32 @@ extern "C" int gf3_sync_stream_ex(const gf3_ctx* c, const void* d_r, int64_t n, 
     struct Publish { int64_t* i; ~Publish() { memcpy(g_last_info, i, sizeof(g_last_info)); } } publish{info};
     info[0] = 2; info[1] = info[2] = info[3] = 0;
     if (!d_corr && c->scr.ok && w.s_nblk > 0 && (mode >= 2 || (mode == 0 && n >= GF3_SCR_MIN_SAMPLES))) {
-        int rc = sync_stream_screened(c, d_r, n, w, base, d_peaks, cap, mode, st);
+        int rc = sync_stream_screened(c, d_r, n, w, p, d_peaks, cap, mode, st);
         if (rc != GF3_OK) return rc;
-        static_assert(sizeof(ScrMisc) <= 256, "readback_buffer() holds 256 bytes");
-        ScrMisc hm_local;
-        void* pin = readback_buffer();
-        ScrMisc& hm = pin ? *(ScrMisc*)pin : hm_local;
-        HIPCHK(c, hipMemcpyAsync(&hm, base + w.o_smisc, sizeof(ScrMisc), hipMemcpyDeviceToHost, st));      // (the one read-back of the call)
-        HIPCHK(c, hipStreamSynchronize(st));
-        const int64_t h[2] = {hm.np[0], hm.np[1]}, ncand = hm.total;
-        info[1] = hm.ncell; info[2] = hm.nhit; info[3] = ncand;
+        static_assert(sizeof(ScrMisc) <= sizeof(ReadbackPage::local), "read_back() holds 256 bytes");
+        rc = read_back(c, st, &h, p.misc, sizeof(ScrMisc));               // (the one read-back of the call)
+        if (rc != GF3_OK) return rc;
+        const ScrMisc& hm = *(const ScrMisc*)h;
+        info[1] = hm.ncell; info[2] = hm.nhit; info[3] = hm.total;
         if (!(hm.status & 1)) {
             info[0] = 0;
-            *n_peaks = h[0];
-            if (h[1] == 2) return fail(c, GF3_ERANGE, "gf3_sync_stream: %lld peaks exceed capacity %lld", (long long)h[0], (long long)cap);
-            return GF3_OK;
+            const int64_t np[2] = {hm.np[0], hm.np[1]};
+            return finish_peaks(c, "gf3_sync_stream", np, cap, n_peaks);
         }
         info[0] = 1;                                      // the screen was not selective: all-fp64 path below
     }
-    {
-        OlsArgs a{};
-        a.t = pl.t; a.in = d_r; a.n_in = n; a.dt = c->cfg.in_dtype;
-        a.Hq = pl.d_Hq; a.Q = pl.Q; a.H = pl.Lp; a.Lc = c->Lc;
-        a.spec = (cplx*)(base + w.o_spec); a.nwin = w.nwin; a.plen = w.plen; a.corr = P; a.part = part;
-        HIPCHK(c, run_spec_ols(pl, a, w.nwin, w.nblk, st));
-    }
-    hipLaunchKernelGGL(pk_max_final, dim3(1), dim3(256), 0, st, (const double*)part, (int)w.nb_max, mx);
+    HIPCHK(c, run_spec_ols(c->stream_plan, ols_args(c, w, p, d_r, n, P), w.nwin, w.nblk, st));
+    hipLaunchKernelGGL(ck_fold_max, dim3(1), dim3(256), 0, st, (const double*)p.part, (int)w.nb_max, p.mx, (double*)nullptr);
     hipLaunchKernelGGL(pk_candidates, dim3((unsigned)w.nb_c), dim3(PK_THREADS), 0, st, (const double*)P, w.nz,
-                       (const double*)mx, c->cfg.thresh, cnt, (const int64_t*)nullptr, (int64_t*)nullptr);
-    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)cnt, w.nb_c, offs, total, (const long long*)nullptr, (const long long*)nullptr);
+                       (const double*)p.mx, c->cfg.thresh, p.cnt, (const int64_t*)nullptr, (int64_t*)nullptr);
+    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)p.cnt, w.nb_c, p.offs, p.total, (const long long*)nullptr, (const long long*)nullptr);
     hipLaunchKernelGGL(pk_candidates, dim3((unsigned)w.nb_c), dim3(PK_THREADS), 0, st, (const double*)P, w.nz,
-                       (const double*)mx, c->cfg.thresh, cnt, (const int64_t*)offs, cand);
-    hipLaunchKernelGGL(pk_nms, dim3(1), dim3(NMS_THREADS), 0, st, (const int64_t*)cand, (const int64_t*)total,
-                       (int64_t)c->Lc, w.nz, d_peaks, cap, np);
+                       (const double*)p.mx, c->cfg.thresh, p.cnt, (const int64_t*)p.offs, p.cand);
+    hipLaunchKernelGGL(pk_nms, dim3(1), dim3(NMS_THREADS), 0, st, (const int64_t*)p.cand, (const int64_t*)p.total,
+                       (int64_t)c->Lc, w.nz, d_peaks, cap, p.np);
     HIPCHK(c, hipGetLastError());
-    int64_t h_local[2] = {0, 0};
-    int64_t* h = readback_buffer() ? (int64_t*)readback_buffer() : h_local;
-    HIPCHK(c, hipMemcpyAsync(h, np, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *n_peaks = h[0];
-    if (h[1] == 2) return fail(c, GF3_ERANGE, "gf3_sync_stream: %lld peaks exceed capacity %lld", (long long)h[0], (long long)cap);
-    return GF3_OK;
+    const int rc = read_back(c, st, &h, p.np, 16);
+    return rc != GF3_OK ? rc : finish_peaks(c, "gf3_sync_stream", (const int64_t*)h, cap, n_peaks);
 }
 
 // the legacy entry point: the context's default mode (gf3_sync_stream_mode), diagnostics through gf3_sync_stream_info
@@ -434,23 +431,8 @@ __global__ __launch_bounds__(CK_THREADS) void ck_max_kernel(const double* __rest
         mx = fmax(mx, v);
         nan = nan || !(v == v);
     }
-    mx = block_max(mx, scratch);
-    const int anynan = __syncthreads_or(nan ? 1 : 0);                   // np.amax propagates NaN (OFDM.py:359)
-    if (threadIdx.x == 0) part[blockIdx.x] = anynan ? NAN : mx;
-}
-// run_max[0] = amax(run_max[0], part[0..n)) with NumPy's NaN rule; run_max[1] = amax(part[0..n)): this piece's own maximum
-__global__ void ck_fold_max(const double* part, int n, double* run_max) {
-    __shared__ double scratch[16];
-    double mx = -INFINITY;
-    bool nan = false;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { const double v = part[i]; mx = fmax(mx, v); nan = nan || !(v == v); }
-    mx = block_max(mx, scratch);
-    const int anynan = __syncthreads_or(nan ? 1 : 0);
-    if (threadIdx.x == 0) {
-        const double run = run_max[0];
-        run_max[0] = (anynan || !(run == run)) ? NAN : fmax(run, mx);
-        run_max[1] = anynan ? NAN : mx;
-    }
+    mx = block_amax(mx, nan, scratch);
+    if (threadIdx.x == 0) part[blockIdx.x] = mx;
 }
 // pass 0 (offsets == nullptr): count per block; pass 1: write zeros-index g - 1 + lag_offset and the raw triple of every
 // listed lag g in [lo, hi), ascending
@@ -458,24 +440,17 @@ __global__ __launch_bounds__(PK_THREADS) void ck_list_kernel(const double* __res
                                                              int64_t lag_offset, int64_t* counts, const int64_t* offsets, int64_t* idx, double* val3) {
     __shared__ int wsum[PK_THREADS / 64];
     if (offsets && counts[blockIdx.x] == 0) return;
-    const double mx = mxp[0];
-    const bool filt = mx > 0.0 && thresh > 0.0 && mx < INFINITY && thresh < INFINITY;
-    const double lim = filt ? thresh * mx * (1.0 - 1e-6) : -INFINITY;   // (no positive finite maximum yet: every lag stays listed)
+    const double lim = peak_limit(mxp[0], thresh);                      // (no positive finite maximum yet: every lag stays listed)
     const int64_t base = lo + ((int64_t)blockIdx.x * PK_THREADS + threadIdx.x) * PK_ITEMS;
     int c = 0;
     unsigned flags = 0;
 #pragma unroll
     for (int k = 0; k < PK_ITEMS; ++k)
         if (base + k < hi && !(P[base + k] < lim)) { flags |= 1u << k; ++c; }
-    int x = c;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < PK_THREADS / 64; ++w) { if (w < wave) woff += wsum[w]; total += wsum[w]; }
+    int total;
+    const int before = block_scan(c, wsum, PK_THREADS / 64, total);
     if (!offsets) { if (threadIdx.x == 0) counts[blockIdx.x] = total; return; }
-    int64_t o = offsets[blockIdx.x] + woff + (x - c);
+    int64_t o = offsets[blockIdx.x] + before;
     for (int k = 0; k < PK_ITEMS; ++k)
         if (flags & (1u << k)) {
             const int64_t g = base + k;
@@ -484,8 +459,8 @@ __global__ __launch_bounds__(PK_THREADS) void ck_list_kernel(const double* __res
             ++o;
         }
 }
-// the reference's rule on the listed raw values (OFDM.py:359-361): p = P / max first, then
-// (p1 - p0)(p2 - p1) <= 0 and p1 > thresh; survivors compacted in order.  One workgroup.
+// the reference's rule on the listed raw values: p = P / max first, then is_peak (gf3rx_peak.h); survivors compacted in
+// order.  One workgroup.
 __global__ __launch_bounds__(1024) void ck_decide_kernel(const int64_t* idx, const double* val3, int64_t n, const double* mxp, double thresh,
                                                          int64_t* cand, int64_t* total) {
     __shared__ int wsum[16];
@@ -493,21 +468,15 @@ __global__ __launch_bounds__(1024) void ck_decide_kernel(const int64_t* idx, con
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     const double mx = mxp[0];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t b0 = 0; b0 < n; b0 += 1024) {
         const int64_t i = b0 + threadIdx.x;
         int f = 0;
         if (i < n) {
-            const double p0 = val3[3 * i] / mx, p1 = val3[3 * i + 1] / mx, p2 = val3[3 * i + 2] / mx;
-            f = (((p1 - p0) * (p2 - p1) <= 0.0) && (p1 > thresh)) ? 1 : 0;
+            f = is_peak(val3[3 * i] / mx, val3[3 * i + 1] / mx, val3[3 * i + 2] / mx, thresh) ? 1 : 0;
         }
-        int x = f;
-        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        if (f) cand[carry + woff + (x - 1)] = idx[i];
+        int tot;
+        const int before = block_scan(f, wsum, 16, tot);
+        if (f) cand[carry + before] = idx[i];
         __syncthreads();
         if (threadIdx.x == 0) carry += tot;
         __syncthreads();
@@ -532,45 +501,30 @@ extern "C" int gf3_sync_chunk(const gf3_ctx* c, const void* d_buf, int64_t n, in
     if (h_piece_max) *h_piece_max = -INFINITY;
     if (lag_lo == lag_hi) return GF3_OK;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)d_work;
-    double* P = (double*)(base + w.o_P);
-    double* part = (double*)(base + w.o_part);
-    int64_t* cnt = (int64_t*)(base + w.o_cnt);
-    int64_t* offs = (int64_t*)(base + w.o_off);
-    int64_t* total = (int64_t*)(base + w.o_misc + 8);
-    const CorrPlan& pl = c->stream_plan;
-    {   // P of the whole buffer, all fp64 (the overlap-save of gf3_sync_stream's fp64 path)
-        OlsArgs a{};
-        a.t = pl.t; a.in = d_buf; a.n_in = n; a.dt = c->cfg.in_dtype;
-        a.Hq = pl.d_Hq; a.Q = pl.Q; a.H = pl.Lp; a.Lc = c->Lc;
-        a.spec = (cplx*)(base + w.o_spec); a.nwin = w.nwin; a.plen = w.plen; a.corr = P; a.part = part;
-        HIPCHK(c, run_spec_ols(pl, a, w.nwin, w.nblk, st));
-    }
+    const StreamPtrs p = stream_ptrs(w, d_work);
+    // P of the whole buffer, all fp64 (the overlap-save of gf3_sync_stream's fp64 path)
+    HIPCHK(c, run_spec_ols(c->stream_plan, ols_args(c, w, p, d_buf, n, p.P), w.nwin, w.nblk, st));
     // the maximum of the lags this piece owns joins the running maximum (the ols workgroups' own maxima cover lags at
     // the buffer's edges whose sums are cut off: they are not values of the stream's P)
     int64_t gmax = (lag_hi - lag_lo + CK_THREADS * 8 - 1) / (CK_THREADS * 8);
     gmax = gmax < 1 ? 1 : (gmax > w.nb_max ? w.nb_max : (gmax > 2048 ? 2048 : gmax));
-    hipLaunchKernelGGL(ck_max_kernel, dim3((unsigned)gmax), dim3(CK_THREADS), 0, st, (const double*)P, lag_lo, lag_hi, part);
-    hipLaunchKernelGGL(ck_fold_max, dim3(1), dim3(256), 0, st, (const double*)part, (int)gmax, d_run_max);
+    hipLaunchKernelGGL(ck_max_kernel, dim3((unsigned)gmax), dim3(CK_THREADS), 0, st, (const double*)p.P, lag_lo, lag_hi, p.part);
+    hipLaunchKernelGGL(ck_fold_max, dim3(1), dim3(256), 0, st, (const double*)p.part, (int)gmax, d_run_max + 1, d_run_max);   // [running, this piece's own]
     const int64_t nb = (lag_hi - lag_lo + PK_THREADS * PK_ITEMS - 1) / (PK_THREADS * PK_ITEMS);     // <= nb_c of the workspace
-    hipLaunchKernelGGL(ck_list_kernel, dim3((unsigned)nb), dim3(PK_THREADS), 0, st, (const double*)P, lag_lo, lag_hi, (const double*)d_run_max,
-                       c->cfg.thresh, lag_offset, cnt, (const int64_t*)nullptr, (int64_t*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)cnt, nb, offs, total, (const long long*)nullptr, (const long long*)nullptr);
+    hipLaunchKernelGGL(ck_list_kernel, dim3((unsigned)nb), dim3(PK_THREADS), 0, st, (const double*)p.P, lag_lo, lag_hi, (const double*)d_run_max,
+                       c->cfg.thresh, lag_offset, p.cnt, (const int64_t*)nullptr, (int64_t*)nullptr, (double*)nullptr);
+    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, (const int64_t*)p.cnt, nb, p.offs, p.total, (const long long*)nullptr, (const long long*)nullptr);
     HIPCHK(c, hipGetLastError());
-    int64_t want_local = 0;
-    double pmax_local = -INFINITY;
-    void* pin = readback_buffer();
-    int64_t& want = pin ? *(int64_t*)pin : want_local;
-    double& pmax = pin ? *(double*)((char*)pin + 8) : pmax_local;
-    HIPCHK(c, hipMemcpyAsync(&want, total, 8, hipMemcpyDeviceToHost, st));
-    if (h_piece_max) HIPCHK(c, hipMemcpyAsync(&pmax, d_run_max + 1, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    const void* h = nullptr;                                // [lags to keep | this piece's maximum, when asked for]
+    const int rc = read_back(c, st, &h, p.total, 8, h_piece_max ? d_run_max + 1 : nullptr, 8);
+    if (rc != GF3_OK) return rc;
+    const int64_t want = *(const int64_t*)h;
     *n_listed = want;
-    if (h_piece_max) *h_piece_max = pmax;
+    if (h_piece_max) *h_piece_max = ((const double*)h)[1];
     if (want > cap) return fail(c, GF3_ERANGE, "gf3_sync_chunk: %lld lags to keep exceed capacity %lld", (long long)want, (long long)cap);
     if (want > 0) {
-        hipLaunchKernelGGL(ck_list_kernel, dim3((unsigned)nb), dim3(PK_THREADS), 0, st, (const double*)P, lag_lo, lag_hi, (const double*)d_run_max,
-                           c->cfg.thresh, lag_offset, cnt, (const int64_t*)offs, d_idx, d_val3);
+        hipLaunchKernelGGL(ck_list_kernel, dim3((unsigned)nb), dim3(PK_THREADS), 0, st, (const double*)p.P, lag_lo, lag_hi, (const double*)d_run_max,
+                           c->cfg.thresh, lag_offset, p.cnt, (const int64_t*)p.offs, d_idx, d_val3);
         HIPCHK(c, hipGetLastError());
     }
     return GF3_OK;
@@ -594,11 +548,7 @@ extern "C" int gf3_sync_decide(const gf3_ctx* c, const int64_t* d_idx, const dou
     hipLaunchKernelGGL(pk_nms, dim3(1), dim3(NMS_THREADS), 0, st, (const int64_t*)cand, (const int64_t*)total,
                        (int64_t)c->Lc, nz_total, d_peaks, cap, np);
     HIPCHK(c, hipGetLastError());
-    int64_t h_local[2] = {0, 0};
-    int64_t* h = readback_buffer() ? (int64_t*)readback_buffer() : h_local;
-    HIPCHK(c, hipMemcpyAsync(h, np, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *n_peaks = h[0];
-    if (h[1] == 2) return fail(c, GF3_ERANGE, "gf3_sync_decide: %lld peaks exceed capacity %lld", (long long)h[0], (long long)cap);
-    return GF3_OK;
+    const void* h = nullptr;
+    const int rc = read_back(c, st, &h, np, 16);
+    return rc != GF3_OK ? rc : finish_peaks(c, "gf3_sync_decide", (const int64_t*)h, cap, n_peaks);
 }

@@ -3,13 +3,10 @@
 #include "gf3rx_host.h"
 #include "gf3rx_fscreen.h"
 
-extern "C" int64_t gf3_sync_frames_workspace_bytes(const gf3_ctx* c, int64_t F) {
-    if (!c || F < 0) return 0;
-    return (int64_t)((size_t)F * sizeof(int) + 64);           // [count | pad | unresolved window numbers]
-}
+// [count | pad | unresolved window numbers]
+extern "C" int64_t gf3_sync_frames_workspace_bytes(const gf3_ctx* c, int64_t F) { return list_workspace_bytes(c, F); }
 
-// What the calling thread's last frames sync did (gf3_sync_frames_last): kept per host thread like every other diagnostic.
-static thread_local struct { const gf3_ctx* ctx = nullptr; void* stream = nullptr; int32_t path = -1, cap = 0; } g_fs_last;
+static thread_local LastCall g_fs_last;                       // (gf3_sync_frames_last)
 
 // mode 0: all fp64 (corr_kernel on every window).  mode 1: fp32 screen with a proven bound per window (gf3rx_fscreen.h) in
 // the caller's workspace; the windows it cannot decide are listed and corr_kernel runs on those.  mode -1 (auto, what plain
@@ -37,15 +34,15 @@ static int sync_frames_impl(gf3_ctx* c, const void* d_in, int64_t n_in, int64_t 
     if (mode == -1 && can_screen) work = ctx_workspace(c, st, gf3_ctx::WS_SYNC, gf3_sync_frames_workspace_bytes(c, F));
     const bool screened = can_screen && work;
     if (screen_only && !screened) return fail(c, GF3_EINVAL, "gf3_debug_frames_screen: no screening plan for this window (max_window %d)", fp.wmax);
-    g_fs_last.ctx = c; g_fs_last.stream = stream; g_fs_last.path = screened ? 0 : 2; g_fs_last.cap = screened ? (int32_t)F : 0;
+    g_fs_last.set(c, stream, screened ? 0 : 2, screened ? (int32_t)F : 0);
     if (!screened) {
-        if (d_work) HIPCHK(c, hipMemsetAsync(d_work, 0, 64, st));      // a caller's workspace never keeps an earlier call's count
+        if (d_work) HIPCHK(c, hipMemsetAsync(d_work, 0, LIST_HEAD, st));      // a caller's workspace never keeps an earlier call's count
         HIPCHK(c, run_corr(c, pl, a, F, st));
         return GF3_OK;
     }
     int* count = (int*)work;
-    int* list = (int*)((char*)work + 64);
-    HIPCHK(c, hipMemsetAsync(count, 0, 64, st));
+    int* list = (int*)((char*)work + LIST_HEAD);
+    HIPCHK(c, hipMemsetAsync(count, 0, LIST_HEAD, st));
     FScreenArgs fa{d_in, n_in, c->cfg.in_dtype, fp.d_tw, fp.d_twn, fp.d_Hs, fp.d_H0N, fp.d_Hinf, fp.Q, fp.Lp, c->Lc, W,
                    stride, win_lo, W, (float)c->cfg.thresh, d_starts, list, count, dbg_y32, dbg_err, dbg_cls};
     HIPCHK(c, launch_fscreen(c, fa, F, st));
@@ -63,11 +60,7 @@ extern "C" int gf3_sync_frames_ex(gf3_ctx* c, const void* d_in, int64_t n_in, in
     return sync_frames_impl(c, d_in, n_in, F, stride, win_lo, win_hi, d_starts, d_peak, mode, d_work, nullptr, nullptr, nullptr, false, stream);
 }
 extern "C" int gf3_sync_frames_last(const gf3_ctx* c, void* stream, int32_t* path, int32_t* unresolved_capacity) {
-    if (!c || !path) return fail(c, GF3_EINVAL, "gf3_sync_frames_last: null argument");
-    const bool mine = g_fs_last.ctx == c && g_fs_last.stream == stream;
-    *path = mine ? g_fs_last.path : -1;
-    if (unresolved_capacity) *unresolved_capacity = mine ? g_fs_last.cap : 0;
-    return GF3_OK;
+    return g_fs_last.query("gf3_sync_frames_last", c, stream, path, unresolved_capacity);
 }
 // tests: the screening pass alone -- fp32 lags [F][W], the bound per window, the verdict per window (0 resolved with a
 // detection, 1 resolved without, 2 unresolved: d_starts is then left alone), the unresolved windows in d_work

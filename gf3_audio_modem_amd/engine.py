@@ -210,6 +210,18 @@ class Engine:
             work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)
         return work, 0 if split is None else (2 if split else 1)
 
+    def _last_call(self, query, cap_name):
+        """Answer of a screened dispatcher's *_last query on the current stream: dict(path, <cap_name>).  No device read."""
+        path, cap = C.c_int32(-1), C.c_int32(0)
+        self._check(query(self._h, self._stream(), C.byref(path), C.byref(cap)))
+        return {"path": int(path.value), cap_name: int(cap.value)}
+
+    @staticmethod
+    def _listed(work):
+        """The numbers a screen left in its list workspace [count | pad to 64 bytes | int32 list], sorted."""
+        n = int(work[:4].view(torch.int32).item())
+        return torch.sort(work[64: 64 + 4 * n].view(torch.int32)).values
+
     # ------------------------------------------------------------------ ABI calls
     def chirp_replica(self):
         out = np.empty(self.cfg.chirp_length)
@@ -253,9 +265,7 @@ class Engine:
     def demod_frames_last(self):
         """Of the calling thread's last demod_frames call on the current stream: dict(path = 0 screened | 2 all fp64 | -1 no
         such call, listed_capacity = packets its fp64 pass could take).  No device read."""
-        path, cap = C.c_int32(-1), C.c_int32(0)
-        self._check(self.lib.gf3_demod_frames_last(self._h, self._stream(), C.byref(path), C.byref(cap)))
-        return dict(path=int(path.value), listed_capacity=int(cap.value))
+        return self._last_call(self.lib.gf3_demod_frames_last, "listed_capacity")
 
     def debug_rfft32_batch(self, x, offsets):
         """The screened demodulation's fp32 transform alone (tests): [n_sym, N/2+1] complex64 spectra of the N samples
@@ -293,8 +303,7 @@ class Engine:
         work = self._new((int(self.lib.gf3_demod_screen_workspace_bytes(self._h, F)),), torch.uint8)
         self._check(self.lib.gf3_debug_demod_screen(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(o["bits"]), _ptr(o["ep32"]),
                                                     _ptr(o["E"]), _ptr(o["cls"]), _ptr(work), self._stream()))
-        n = int(work[:4].view(torch.int32).item())
-        o["listed"] = torch.sort(work[64: 64 + 4 * n].view(torch.int32)).values
+        o["listed"] = self._listed(work)
         return o
 
     def demod_frames_llr(self, x, frame_offsets, weight="csi", want=(), split=None, out=None):
@@ -367,9 +376,7 @@ class Engine:
     def sync_frames_last(self):
         """Of the calling thread's last sync_frames call on the current stream: dict(path = 0 screened | 2 all fp64 | -1 no
         such call, unresolved_capacity = windows its fp64 pass could take).  No device read."""
-        path, cap = C.c_int32(-1), C.c_int32(0)
-        self._check(self.lib.gf3_sync_frames_last(self._h, self._stream(), C.byref(path), C.byref(cap)))
-        return dict(path=int(path.value), unresolved_capacity=int(cap.value))
+        return self._last_call(self.lib.gf3_sync_frames_last, "unresolved_capacity")
 
     def sync_frames_workspace(self, F):
         return self._new((int(self.lib.gf3_sync_frames_workspace_bytes(self._h, F)),), torch.uint8)
@@ -385,8 +392,7 @@ class Engine:
         work = self.sync_frames_workspace(F)
         self._check(self.lib.gf3_debug_frames_screen(self._h, _ptr(x), x.numel(), F, stride, win_lo, win_hi, _ptr(o["starts"]),
                                                      _ptr(o["y32"]), _ptr(o["err"]), _ptr(o["cls"]), _ptr(work), self._stream()))
-        n = int(work[:4].view(torch.int32).item())
-        o["unresolved"] = torch.sort(work[64: 64 + 4 * n].view(torch.int32)).values
+        o["unresolved"] = self._listed(work)
         return o
 
     def sync_stream(self, x, cap=None, want_corr=False, mode=None, want_info=False):
