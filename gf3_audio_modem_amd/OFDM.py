@@ -22,6 +22,7 @@ import torch
 from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
 from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
+from .loading import map_loaded, validate_loading
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -163,6 +164,17 @@ class CamG:
         # [B, packets, C] in dB (`last_snr_db` is then the SNR after combining); None otherwise
         self.last_branch_starts = None
         self.last_branch_snr_db = None
+        # adaptive bit loading (loading.py): bit_loading = a table of one QAM order per data carrier, uint8 [C] of
+        # 0 / 2 / 4 / 6 in data_carriers order, e.g. loading.bit_loading_from_snr(last_snr_db, gap_db) of a QPSK probe
+        # received under llr_weighting = "noise"; both ends must hold the same table.  A carrier of order m > 0 sends
+        # engine.square_qam_table(m) -- at m = 2 too, which is NOT `mapping_table` (the reference's first bit lies on the Q
+        # axis) --, a carrier of order 0 its bin's pilot symbol.  A packet then carries packet_length *
+        # loaded_bits_per_symbol coded bits; mu, data_bits_per_symbol and bits_per_symbol keep the reference's values.
+        # "None" and "QCLDPC-*" with llr_weighting "csi" or "noise"; under "None" receive() returns the hard decisions of the
+        # CSI-weighted LLRs (a raw bit error rate).  ValueError with interleave, "noise2d", fused_llr, phase_tracking,
+        # decoder_feedback, "XOR" and receive_diversity; NotImplementedError with graph_output and the piece-wise host path.
+        # None: everything as without it.
+        self.bit_loading = None
         self._engines = {}
 
     def __repr__(self):
@@ -199,13 +211,26 @@ class CamG:
         return self._engine().chirp_replica()
 
     # ---- the coded chain ("QCLDPC-*": coding.py) ------------------------------------------------------------------------
+    def _loading(self):
+        """`bit_loading` validated (uint8 [C]; ValueError for a wrong length, another value, no loaded carrier), or None."""
+        return None if self.bit_loading is None else validate_loading(self.bit_loading, self.data_carriers_per_symbol)
+
+    @property
+    def loaded_bits_per_symbol(self):
+        """Coded bits a data symbol carries: Bs = sum(bit_loading), or data_bits_per_symbol without a loading."""
+        order = self._loading()
+        return self.data_bits_per_symbol if order is None else int(order.sum(dtype=np.int64))
+
     def _chain(self) -> CodedChain:
         """The coding attributes as they are at this call; codes come from this module's `_qcldpc_code`, looked up late."""
+        order = self._loading()
+        bits = self.data_bits_per_symbol if order is None else int(order.sum(dtype=np.int64))
         return CodedChain(self.encoding, self.ldpc_n, self.ldpc_max_iter, self.llr_weighting, self.interleave, self.fused_llr,
-                          self.outer_code, per_packet=self.packet_length * self.data_bits_per_symbol,
+                          self.outer_code, per_packet=self.packet_length * bits,
                           make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc),
                           phase_tracking=bool(self.phase_tracking), decoder_feedback=self.decoder_feedback,
-                          feedback_window=self.feedback_window, feedback_min_known=self.feedback_min_known)
+                          feedback_window=self.feedback_window, feedback_min_known=self.feedback_min_known,
+                          loading=None if order is None else tuple(order.tolist()))
 
     def _qcldpc_rate(self):
         """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
@@ -344,6 +369,8 @@ class transmitter(CamG):
         print("OFDM Paramters:")
         print(self)
         bits_encoded = np.asarray(self.encode(np.asarray(bits)), dtype=np.uint8)
+        if self.bit_loading is not None:
+            return self._transmit_loaded(bits, bits_encoded, graph_output)
         eng = self._engine()
         nbp = self.packet_length * self.data_bits_per_symbol
         self.no_packets = len(bits_encoded) // nbp
@@ -357,10 +384,29 @@ class transmitter(CamG):
         signal = np.hstack([rows.cpu().numpy().reshape(-1), self.sync_chirp()])     # final chirp (OFDM.py:259)
         print("Number of packets to transmit:      " + str(self.no_packets))
         if graph_output:
-            import matplotlib.pyplot as plt
-            time = np.linspace(0, len(signal) / self.fs, len(signal))
-            plt.plot(time, 5 * signal, label="Signal")
-            plt.title("OFDM Frame"); plt.xlabel("time"); plt.legend(); plt.savefig("OFDM Frame"); plt.show()
+            self._plot_frame(signal)
+        return signal
+
+    def _plot_frame(self, signal):
+        import matplotlib.pyplot as plt
+        time = np.linspace(0, len(signal) / self.fs, len(signal))
+        plt.plot(time, 5 * signal, label="Signal")
+        plt.title("OFDM Frame"); plt.xlabel("time"); plt.legend(); plt.savefig("OFDM Frame"); plt.show()
+
+    def _transmit_loaded(self, bits, bits_encoded, graph_output):
+        """transmit() under `bit_loading`, on the host (gf3_tx_frames maps one table): the loaded mapper, then the
+        reference's own steps -- build_OFDM_symbol (which draws the unused-carrier filler), ifft, add_cp, send_to_stream."""
+        order = self._loading()
+        known = self.map(np.asarray(self.known_sequence[:self.bits_per_symbol]).reshape(self.K, self.mu))
+        payload = map_loaded(bits_encoded, order, known[np.asarray(self.data_carriers) - 1])
+        n_sym = payload.shape[0]
+        print("Number of bits to transmit:         " + str(len(bits)))
+        print("Number of OFDM symbols to transmit: " + str(n_sym))
+        time_data = self.add_cp(np.fft.ifft(self.build_OFDM_symbol(payload)))
+        signal = self.send_to_stream(time_data, self.sync_chirp())[0]
+        print("Number of packets to transmit:      " + str(self.no_packets))
+        if graph_output:
+            self._plot_frame(signal)
         return signal
 
 
@@ -484,6 +530,12 @@ class receiver(transmitter):
         rate, fused = chain.check_receive()                     # (the refusals: before any GPU work)
         blanking = Engine.check_blanking(self.blanking_threshold, self.blanking_guard) if self.impulse_blanking else None
         r = _as_samples(signal)
+        if chain.loading is not None:                           # (what a loading has no path for: also before any GPU work)
+            if graph_output:
+                raise NotImplementedError("bit_loading: the plots draw one constellation; receive with graph_output = False")
+            if getattr(self, "host_chunk_samples", None) or len(r) > (1 << 27):
+                raise NotImplementedError("bit_loading: the piece-wise host path of long recordings (or host_chunk_samples) "
+                                          "decides by the context's one table; receive shorter recordings")
         eng = self._engine(r.dtype)
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
         # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
@@ -522,6 +574,8 @@ class receiver(transmitter):
                 bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
             if bad is not None:                                 # (codeword_crc: the flags ride in the same copy)
                 need["crc_bad"] = bad
+        elif chain.loading is not None:                         # "None" under a loading: the raw decisions of every loaded carrier
+            bits_t = (chain.weigh_loaded(eng, o, "csi")[0] < 0).to(torch.int64)
         else:
             bits_t = self._decode_packed(eng, o["bits"])
         # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
@@ -530,7 +584,7 @@ class receiver(transmitter):
         if got["ragged"][0] != 0:                               # (before anything is printed: get_symbols fails first in the reference)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
-        bits = bits_t.cpu().numpy().astype(np.int64) if rate is not None else bits_t.numpy()
+        bits = bits_t.cpu().numpy().astype(np.int64) if bits_t.is_cuda else bits_t.numpy()
         self._last_slope = got["slope"]
         self.last_phase_track = self.last_phase_measured = None
         self.last_blanked, self.last_sample_level = got.get("last_blanked"), got.get("last_sample_level")

@@ -8,6 +8,7 @@ Layout
   OFDM.py    drop-in mirror of the reference's `receiver` class (same names/shapes)
   ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
   outer.py   OuterRS: Reed-Solomon erasure code across codewords (repairs the codewords the LDPC decoder gives up on)
+  loading.py adaptive bit loading: a QAM order per carrier from the measured SNR, the loaded mapper (host, NumPy)
   crc.py     CodewordCRC: CRC-32 per codeword (catches the codewords the LDPC decoder converged on wrongly)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)
 """

@@ -70,11 +70,13 @@ class CodedChain:
     decoder_feedback: int = 0               # receive(): extra decoding passes at most, each re-equalised from the trusted codewords
     feedback_window: tuple = (2, 8)         # (half_symbols, half_bins) of Engine.feedback_equalise
     feedback_min_known: int = 4             # known symbols a window needs before its gain is used
+    loading: tuple = None                   # adaptive bit loading (loading.py): the validated order per data carrier; per_packet then counts its bits
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
         """Rate of a "QCLDPC-*" encoding, else None.  The interleaver and the codeword CRC exist on these encodings only."""
         rate = QCLDPC_ENCODINGS.get(self.encoding)
+        self.check_loading()
         if self.interleave and rate is None:
             raise ValueError(f"interleave needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
         if self.codeword_crc and rate is None:
@@ -84,6 +86,20 @@ class CodedChain:
         if rate is None:
             self.outer()                        # (ValueError: the outer code exists on these encodings only)
         return rate
+
+    def check_loading(self):
+        """What a bit loading refuses: the steps that assume the context's uniform C mu layout (the interleaver's
+        permutation, the carrier x symbol demapper, the fused kernel) or its one table's decisions (the tracker, the
+        feedback's re-mapped symbols), and the XOR whitening, whose mask has the period of a uniform symbol."""
+        if self.loading is None:
+            return
+        for name, on in (("interleave", self.interleave), ("llr_weighting 'noise2d'", self.llr_weighting == "noise2d"),
+                         ("fused_llr", self.fused_llr), ("phase_tracking", self.phase_tracking),
+                         ("decoder_feedback", self.decoder_feedback)):
+            if on:
+                raise ValueError(f"bit_loading: {name} works on the uniform layout of one table; switch it off")
+        if self.encoding == "XOR":
+            raise ValueError("bit_loading: encoding 'XOR' whitens with the period of a uniform symbol; use 'None' or 'QCLDPC-*'")
 
     def code(self, rate, device=None):
         """The code of this rate at block length `ldpc_n`, on `device` (None: the current one)."""
@@ -173,7 +189,8 @@ class CodedChain:
         """receive()'s demodulator call: Hs, He, slopes, ragged flag; eq for the staged soft path, eq and Hest for the plots
         (which therefore take the staged path); LLRs straight from the samples when fused."""
         fused = fused and not plots
-        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plots else ("eq",) if rate is not None and not fused else ())
+        soft = (rate is not None and not fused) or self.loading is not None
+        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plots else ("eq",) if soft else ())
         return eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
 
     def llrs(self, eng, o, points):
@@ -196,6 +213,8 @@ class CodedChain:
 
     def weigh(self, eng, o, points):
         """The weights' part of `llrs`, on o["eq"] as it is: -> (LLRs in coded order, the SNR rows)."""
+        if self.loading is not None:
+            return self.weigh_loaded(eng, o, self.llr_weighting)
         snr = {}
         if self.llr_weighting == "csi":
             llr = o["llr"] if "llr" in o else eng.soft_demap_csi(o["eq"], o["Hs"], o["He"])
@@ -215,8 +234,22 @@ class CodedChain:
             llr = eng.interleave(llr, inverse=True)
         return llr, snr
 
+    def weigh_loaded(self, eng, o, weighting):
+        """`weigh` under a bit loading: every carrier by its own table (Engine.soft_demap_loaded).  "noise" leaves
+        `last_snr_db` [F, C] = 10 log10(1 / v') -- the tables have unit energy --, the carriers of order 0 included: their
+        residual against the known pilot symbol is what lets a later allocation switch them back on."""
+        ld = eng.loading(np.asarray(self.loading, dtype=np.uint8))
+        if weighting == "csi":
+            return eng.soft_demap_loaded(o["eq"], ld, Hs=o["Hs"], He=o["He"]), {}
+        var = eng.noise_estimate_loaded(o["eq"], ld)
+        llr = eng.soft_demap_loaded(o["eq"], ld, var=var)
+        floor = 1e-6 * var.mean(dim=1, keepdim=True)
+        return llr, {"last_snr_db": 10.0 * torch.log10(1.0 / torch.maximum(var, floor))}
+
     def check_diversity(self):
         """What receive_diversity() refuses before any GPU work -> rate."""
+        if self.loading is not None:
+            raise ValueError("receive_diversity: bit_loading is not combined (the combiner demaps by the context's one table)")
         if self.llr_weighting == "noise2d":
             raise ValueError("receive_diversity: llr_weighting must be 'csi' or 'noise'; 'noise2d' (per-symbol weights per "
                              "branch) is not combined")

@@ -1,5 +1,6 @@
 // Per-symbol arithmetic of the soft demappers, shared by the stand-alone kernels (gf3rx_demap.hip: gf3_soft_demap, and
-// through it gf3_soft_demap_csi) and the noise-weighted path (gf3rx_noise.hip): squared distances to the table and the
+// through it gf3_soft_demap_csi), the noise-weighted path (gf3rx_noise.hip) and its form for a QAM order per carrier
+// (gf3rx_loading.hip): squared distances to the table and the
 // max-log difference  min over points with bit = 1 of d^2  -  min over points with bit = 0 of d^2  per label bit.  The
 // callers scale the difference (1 / noise_var, or the per-carrier weight) and round it to float32.
 #pragma once

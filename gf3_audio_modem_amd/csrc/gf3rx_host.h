@@ -16,6 +16,8 @@
 //   gf3rx_noise.hip          noise_estimate_kernel, soft_demap_nw_kernel + gf3_noise_estimate, gf3_soft_demap_nw; their
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
 //                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
+//   gf3rx_loading.hip        noise_estimate_loaded_kernel, soft_demap_loaded_kernel + gf3_loading_*, gf3_noise_estimate_loaded,
+//                            gf3_soft_demap_loaded (adaptive bit loading: a QAM order per carrier, the noise pair for such a packet)
 //   gf3rx_combine.hip        combine_kernel + gf3_combine_branches (receive diversity: maximal-ratio combining of B branches' symbols)
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
 //   gf3rx_feedback.hip       feedback_kernel + gf3_feedback_equalise (residual channel from re-encoded codewords, divided out)

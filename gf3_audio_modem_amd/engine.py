@@ -106,6 +106,14 @@ class RxConfig:
         return map_bits(kb, self.const_points, self.const_bits)
 
 
+class Loading:
+    """One gf3_loading of an engine (Engine.loading): handle, the order table (uint8 [C]) and bits = Bs."""
+
+    def __init__(self, engine, handle, order, bits):
+        self.engine, self.handle, self.order, self.bits = engine, handle, order, bits
+        self.order.setflags(write=False)
+
+
 class Engine:
     """One gf3_ctx on one GPU."""
 
@@ -144,6 +152,7 @@ class Engine:
         self._h = h
         self._sync_mode = 0
         self._tls = threading.local()
+        self._loadings = {}                     # bytes of an order table -> Loading (Engine.loading), least recently used first
         self.n_cu = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
         self.bytes_per_frame = int(self.lib.gf3_bytes_per_frame(h))
         self.max_window = int(self.lib.gf3_sync_max_window(h))
@@ -151,6 +160,10 @@ class Engine:
     def close(self):
         ingest.release(self)
         self._tls = threading.local()
+        for ld in getattr(self, "_loadings", {}).values():
+            self.lib.gf3_loading_destroy(ld.handle)
+            ld.handle = None
+        self._loadings = {}
         if getattr(self, "_h", None):
             self.lib.gf3_ctx_destroy(self._h)
             self._h = None
@@ -546,6 +559,76 @@ class Engine:
             raise ValueError("soft_demap_nw: need var [F, C] for eq [F*D, C]")
         llr = self._llr_out(out, F)
         self._check(self.lib.gf3_soft_demap_nw(self._h, _ptr(eq), _ptr(var), F, _ptr(llr), self._stream()))
+        return llr
+
+    # ---- adaptive bit loading (gf3_loading_*) ----
+    LOADING_CACHE = 8                           # loading objects an engine keeps at most
+
+    def loading(self, order):
+        """The loading object (gf3_loading_create) of a table of per-carrier orders, uint8 [C] of 0 / 2 / 4 / 6 in
+        data_bins order: cached by the table's bytes, immutable.  The cache keeps the LOADING_CACHE tables used last (a
+        receiver that allocates anew after every probe does not grow): a table beyond that is destroyed once the device
+        has finished the work queued on it -- a Loading still held for it is then refused like one of a closed engine --
+        and the rest with the engine.  ValueError for a table the library refuses (wrong length, another value, no loaded
+        carrier)."""
+        if isinstance(order, Loading):
+            if order.engine is not self or order.handle is None:
+                raise ValueError("the loading belongs to another engine, a closed one, or has left this engine's cache")
+            return order
+        a = np.ascontiguousarray(order)
+        if a.ndim != 1 or a.dtype.kind not in "iub" or (a.size and (a.min() < 0 or a.max() > 255)):
+            raise ValueError("a loading is a one-dimensional table of integer orders (0, 2, 4 or 6)")
+        a = a.astype(np.uint8)
+        key = a.tobytes()
+        ld = self._loadings.pop(key, None)
+        if ld is not None:
+            self._loadings[key] = ld            # (used last)
+        else:
+            h = C.c_void_p()
+            with torch.cuda.device(self.device):
+                rc = self.lib.gf3_loading_create(self._h, a.ctypes.data_as(C.c_void_p), len(a), C.byref(h))
+            self._check(rc)
+            ld = self._loadings[key] = Loading(self, h, a, int(self.lib.gf3_loading_bits(h)))
+            while len(self._loadings) > self.LOADING_CACHE:
+                old = self._loadings.pop(next(iter(self._loadings)))
+                with torch.cuda.device(self.device):
+                    torch.cuda.synchronize()    # (kernels in flight may still read its tables)
+                self.lib.gf3_loading_destroy(old.handle)
+                old.handle = None
+        return ld
+
+    def noise_estimate_loaded(self, eq, loading):
+        """noise_estimate for a loaded packet (gf3_noise_estimate_loaded): each carrier's residual against its OWN table's
+        decision, against the known pilot symbol on a carrier of order 0.  -> float64 [F, C]."""
+        ld = self.loading(loading)
+        eq, F = self._eq_packets(eq, "noise_estimate_loaded")
+        var = self._new((F, self.cfg.C), torch.float64)
+        self._check(self.lib.gf3_noise_estimate_loaded(self._h, ld.handle, _ptr(eq), F, _ptr(var), self._stream()))
+        return var
+
+    def soft_demap_loaded(self, eq, loading, Hs=None, He=None, var=None, out=None):
+        """Max-log LLRs of a loaded packet (gf3_soft_demap_loaded), each carrier by its own table, times the weight the
+        arguments choose: var [F, C] (noise_estimate_loaded) -> soft_demap_nw's rule; Hs and He [F, K] -> soft_demap_csi's
+        |H^|^2; neither -> 1.  -> float32 [F*D*Bs], Bs = loading.bits, order packet -> symbol -> carrier -> bit; carriers of
+        order 0 have no entries."""
+        ld = self.loading(loading)
+        cfg = self.cfg
+        eq, F = self._eq_packets(eq, "soft_demap_loaded")
+        if var is not None:
+            var = self._dev(var, torch.float64)
+            if var.numel() != F * cfg.C:
+                raise ValueError("soft_demap_loaded: need var [F, C] for eq [F*D, C]")
+        if Hs is not None:
+            Hs = self._dev(Hs)
+            if Hs.numel() != F * cfg.K:
+                raise ValueError("soft_demap_loaded: need Hs [F, K] for eq [F*D, C]")
+        if He is not None:
+            He = self._dev(He)
+            if He.numel() != F * cfg.K:
+                raise ValueError("soft_demap_loaded: need He [F, K] for eq [F*D, C]")
+        llr = self._out(out, (F * cfg.D * ld.bits,), torch.float32, "F*D*Bs")
+        self._check(self.lib.gf3_soft_demap_loaded(self._h, ld.handle, _ptr(eq), _ptr(Hs), _ptr(He), _ptr(var), F, _ptr(llr),
+                                                   self._stream()))
         return llr
 
     def combine_branches(self, eqs, Hs=None, He=None, var=None, out=None, want=("eq", "llr")):

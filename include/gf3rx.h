@@ -506,6 +506,41 @@ int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32
                    void *stream);
 
 /*
+ * Adaptive bit loading (not in the reference): a QAM order per data carrier, and the noise pair above for such a
+ * mixed-order packet.  Opt-in; every entry point above is unchanged and still works on the context's one table.
+ *   A loading is order[C] in data_bins order, each 0, 2, 4 or 6 bits.  Bs = sum(order) coded bits travel per data symbol,
+ *   carrier c's at off[c] = sum(order[:c]) (packet -> symbol -> carrier -> bit, the existing order with a variable
+ *   width; every off[c] is even).  A carrier of order m > 0 uses the Gray-coded square 2^m-QAM of unit energy, label
+ *   bits MSB first, the first m/2 on the I axis: level i of an axis of L = 2^(m/2) levels is the double
+ *   (2i - (L-1)) * (1 / sqrt(2 (L^2 - 1) / 3)) and carries the label bits i ^ (i >> 1).  At m = 2 this is NOT the
+ *   reference's QPSK table, whose first bit lies on the Q axis.  A carrier of order 0 carries no payload: it transmits
+ *   the pilot symbol of its bin (gf3_config.known_re / known_im), so it stays a measured carrier.
+ *   gf3_loading_create:  validates on the host (GF3_EINVAL: null argument, C != the context's C, a value outside
+ *     {0, 2, 4, 6}, no loaded carrier) and uploads the tables to the context's device.  The object is immutable: it can
+ *     be shared by calls in flight on any stream, and must outlive them.  It does not keep the context.
+ *   gf3_loading_bits:  Bs (0 for a null handle).
+ *   gf3_noise_estimate_loaded:  gf3_noise_estimate with s the point of carrier c's OWN table that the hard decision
+ *     picks, and the known pilot point on a carrier of order 0 (a residual with no decision error in it).  The same
+ *     structure and summation order: on an all-m loading and a context of that table, the same bits.
+ *   gf3_soft_demap_loaded:  LLR[f, l, off[c] + b] = (float)(maxlog(eq[f, l, c]; table of order[c])[b] * w), the product
+ *     in fp64 and rounded once; +0 where w = 0; carriers of order 0 write nothing.  The weight is chosen by the optional
+ *     arguments:  d_var given: gf3_soft_demap_nw's rule, vbar the mean of v over all C carriers.  d_Hs and d_He given:
+ *     gf3_soft_demap_csi's weight (|Hs| + (|He| - |Hs|) (l + P/2) / (D + P))^2 at the carrier's bin.  None: w = 1.
+ *     d_var together with d_Hs / d_He, or only one of d_Hs / d_He: GF3_EINVAL.
+ *   d_eq_c128 [F*D, C]   d_var_f64 [F, C]   d_Hs / d_He [F, K]   d_llr_f32 [F*D*Bs].  F == 0 is a no-op; at most 65535
+ *   packets per call.
+ */
+typedef struct gf3_loading gf3_loading;
+int gf3_loading_create(const gf3_ctx *ctx, const uint8_t *h_order, int32_t C, gf3_loading **out);
+void gf3_loading_destroy(gf3_loading *ld);
+int gf3_loading_bits(const gf3_loading *ld);
+int gf3_noise_estimate_loaded(gf3_ctx *ctx, const gf3_loading *ld, const void *d_eq_c128, int64_t F,
+                              double *d_var_f64, void *stream);
+int gf3_soft_demap_loaded(gf3_ctx *ctx, const gf3_loading *ld, const void *d_eq_c128,
+                          const void *d_Hs_c128_or_null, const void *d_He_c128_or_null,
+                          const double *d_var_f64_or_null, int64_t F, float *d_llr_f32, void *stream);
+
+/*
  * Receive diversity (not in the reference): maximal-ratio combining of the equalised symbols of B recordings of ONE
  * transmission (the two channels of a stereo recording, a second microphone), each synchronised and demodulated on its
  * own.  A reflection puts deep nulls into each microphone's transfer function; another microphone has them at other
