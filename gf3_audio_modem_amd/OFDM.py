@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
+from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, check_clock, correct_clock, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
 from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
@@ -175,6 +175,25 @@ class CamG:
         # decoder_feedback, "XOR" and receive_diversity; NotImplementedError with graph_output and the piece-wise host path.
         # None: everything as without it.
         self.bit_loading = None
+        # every encoding: clock_correction corrects the offset between the two sound cards' sampling clocks (tens of ppm for
+        # ordinary hardware, a few hundred for cheap USB audio) by resampling every packet's body between sync (and
+        # blanking) and demodulation (Engine.resample_frames): the phase slope between the pilot blocks, which the
+        # demodulator fits and removes, is only the visible part of such an offset; the inter-carrier interference inside
+        # every symbol, about (pi k eps)^2 / 3 of carrier k's power, is not, and the higher QAM orders of a bit loading
+        # cannot live under it.  "auto": one more demodulation measures the offset of every packet from its slope
+        # (Engine.clock_offset) and the median of the finite estimates is applied to all packets -- a sound card has one
+        # clock; a number: that offset in ppm (> 0: this recording's clock took fewer samples than were sent), at most 2000
+        # in magnitude, no first pass.  clock_taps = 32 or 64 taps of the windowed sinc: 32 is clean up to carrier 1500 of
+        # 2048 (the *2 and *3 modes), 64 up to 0.85 of the band; neither reaches its top few percent, so the full-band *1
+        # modes want 64 and still lose their highest carriers.  receive() leaves the value applied in `last_clock_ppm` and,
+        # under "auto", the per-packet estimates [packets] in `last_clock_ppm_packets`; both are None otherwise.
+        # receive_diversity() estimates and corrects every recording on its own: `last_clock_ppm` is then an array [B].
+        # ValueError for another string, a number that is not finite or beyond 2000 ppm, clock_taps other than 32 or 64;
+        # NotImplementedError on the piece-wise host path.  None: everything as without it.
+        self.clock_correction = None
+        self.clock_taps = 32
+        self.last_clock_ppm = None
+        self.last_clock_ppm_packets = None
         self._engines = {}
 
     def __repr__(self):
@@ -529,6 +548,7 @@ class receiver(transmitter):
         chain = self._chain()
         rate, fused = chain.check_receive()                     # (the refusals: before any GPU work)
         blanking = Engine.check_blanking(self.blanking_threshold, self.blanking_guard) if self.impulse_blanking else None
+        clock = check_clock(self.clock_correction, self.clock_taps)
         r = _as_samples(signal)
         if chain.loading is not None:                           # (what a loading has no path for: also before any GPU work)
             if graph_output:
@@ -546,6 +566,9 @@ class receiver(transmitter):
             if blanking:
                 raise NotImplementedError("impulse_blanking: the piece-wise host path of long recordings (or "
                                           "host_chunk_samples) has no blanking pass; receive shorter recordings")
+            if clock:
+                raise NotImplementedError("clock_correction: the piece-wise host path of long recordings (or "
+                                          "host_chunk_samples) has no resampling pass; receive shorter recordings")
             if rate is not None:
                 raise NotImplementedError(f"encoding {self.encoding!r}: the piece-wise host path of long recordings (or "
                                           "host_chunk_samples) has no soft-decision decoding; receive shorter recordings")
@@ -561,6 +584,9 @@ class receiver(transmitter):
         blanked = {}
         if blanking:
             x, blanked["last_blanked"], blanked["last_sample_level"], _ = eng.blank_impulses(x, starts, *blanking)
+        if clock:                                               # (the packets' bodies at the corrected rate, packed)
+            x, starts, clk = correct_clock(eng, x, starts, clock)
+            blanked.update(clk)
         o = chain.demodulate(eng, x, starts, rate, fused, graph_output)
         # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
         need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
@@ -581,13 +607,15 @@ class receiver(transmitter):
         # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
         # packet that runs past the recording: the reference's get_symbols fails on it)
         got = fetch({**need, **snr, **blanked, "ragged": o["status"]})
-        if got["ragged"][0] != 0:                               # (before anything is printed: get_symbols fails first in the reference)
+        if got["ragged"][0] != 0 or ("clock_status" in got and got["clock_status"].any()):      # (before anything is printed: get_symbols fails first in the reference)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
         bits = bits_t.cpu().numpy().astype(np.int64) if bits_t.is_cuda else bits_t.numpy()
         self._last_slope = got["slope"]
         self.last_phase_track = self.last_phase_measured = None
         self.last_blanked, self.last_sample_level = got.get("last_blanked"), got.get("last_sample_level")
+        self.last_clock_ppm = float(got["clock_ppm"]) if clock else None
+        self.last_clock_ppm_packets = got.get("clock_ppm_packets")
         for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only;
             setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
         if rate is not None:
@@ -611,7 +639,8 @@ class receiver(transmitter):
         symbols are decided by `demap`'s rule, then un-whitened.  -> (bits, Hs, He of branch 0's first packet), as receive().
         Leaves `last_branch_starts` int64 [B, F]; under "noise" `last_branch_snr_db` [B, F, C] and `last_snr_db` [F, C]
         (after combining) in dB.  A branch that lost lock is NOT rejected and poisons the sum: look at its row of
-        `last_branch_snr_db`.  ValueError: B outside 1 .. 4, branches with different packet counts, llr_weighting
+        `last_branch_snr_db`.  Under `clock_correction` every recording is estimated and corrected on its own (a second laptop
+        is a second clock) and `last_clock_ppm` is an array [B].  ValueError: B outside 1 .. 4, branches with different packet counts, llr_weighting
         "noise2d", fused_llr, phase_tracking, decoder_feedback.  NotImplementedError: impulse_blanking, graph_output,
         the piece-wise host path of long recordings (or host_chunk_samples)."""
         print("-" * 42 + "\nReceive \n" + "-" * 42)
@@ -629,6 +658,7 @@ class receiver(transmitter):
             raise ValueError(f"receive_diversity: 1 to {GF3_MAX_BRANCHES} recordings, not {B}")
         chain = self._chain()
         rate = chain.check_diversity()                          # (the refusals: before any GPU work)
+        clock = check_clock(self.clock_correction, self.clock_taps)
         if self.impulse_blanking:
             raise NotImplementedError("receive_diversity: impulse_blanking is not combined; blank each recording's samples "
                                       "with Engine.blank_impulses first")
@@ -655,6 +685,12 @@ class receiver(transmitter):
         self.no_packets = counts[0]
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
+        clk = []
+        if clock:                                               # (every recording has its own clock: estimated and corrected on its own)
+            for b, (x, st) in enumerate(outs):
+                x, st, rows_b = correct_clock(eng, x, st, clock)
+                outs[b] = (x, st)
+                clk.append(rows_b)
         outs = [eng.demod_frames(x, st, want=("eq", "Hs", "He", "slope", "status")) for x, st in outs]
         # 3. combine, then the coded chain or the hard decision and un-whitening
         pts = self._tables()[0]
@@ -671,7 +707,11 @@ class receiver(transmitter):
                 mask = torch.from_numpy(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.uint8)).to(eng.device)
                 bits_t = bits_t ^ mask.repeat(-(-bits_t.numel() // mask.numel()))[: bits_t.numel()]
         # 4. one small copy; last in it the ragged-packet flags
-        got = fetch({**need, **rows, "ragged": torch.cat([o["status"] for o in outs])})
+        if clk:
+            need["clock_ppm"] = torch.stack([c["clock_ppm"] for c in clk])
+            if "clock_ppm_packets" in clk[0]:
+                need["clock_ppm_packets"] = torch.stack([c["clock_ppm_packets"] for c in clk])
+        got = fetch({**need, **rows, "ragged": torch.cat([o["status"] for o in outs] + [c["clock_status"] for c in clk])})
         if got["ragged"].any():
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
         print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
@@ -679,6 +719,7 @@ class receiver(transmitter):
         self._last_slope = got["slope"]
         self.last_branch_starts = got["starts"]
         self.last_branch_snr_db = got.get("last_branch_snr_db")
+        self.last_clock_ppm, self.last_clock_ppm_packets = got.get("clock_ppm"), got.get("clock_ppm_packets")
         if "last_snr_db" in got:
             self.last_snr_db = got["last_snr_db"]
         if rate is not None:

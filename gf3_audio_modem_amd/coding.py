@@ -36,6 +36,54 @@ def fetch(tensors):
     return out
 
 
+CLOCK_MAX_PPM = 2000.0                                      # |eps| <= 2e-3: beyond it gf3_resample_frames copies the body
+
+
+def check_clock(clock_correction, clock_taps):
+    """What `clock_correction` / `clock_taps` refuse before any GPU work -> None (off), or ("auto" | the offset in ppm as a float,
+    half_taps).  ValueError for another string, a value that is not a finite number of at most 2000 ppm in magnitude, and a
+    tap count other than 32 or 64."""
+    if clock_correction is None:
+        return None
+    if isinstance(clock_taps, bool) or clock_taps not in (32, 64):
+        raise ValueError(f"clock_taps must be 32 or 64, not {clock_taps!r}")
+    if isinstance(clock_correction, str):
+        if clock_correction != "auto":
+            raise ValueError(f"clock_correction must be None, 'auto' or a number in ppm, not {clock_correction!r}")
+        return "auto", int(clock_taps) // 2
+    try:
+        ppm = float(clock_correction)
+        ok = not isinstance(clock_correction, bool) and np.isfinite(ppm) and abs(ppm) <= CLOCK_MAX_PPM
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"clock_correction must be None, 'auto' or a finite number of at most {CLOCK_MAX_PPM:.0f} ppm in "
+                         f"magnitude, not {clock_correction!r}")
+    return ppm, int(clock_taps) // 2
+
+
+def correct_clock(eng, x, starts, clock):
+    """The clock correction of one recording, shared by receive() and receive_diversity(): clock = check_clock's answer (not
+    None).  "auto": one demodulation for the slopes, eps per packet (Engine.clock_offset), and the median of the finite
+    estimates for every packet -- a sound card has one clock, and one noisy packet must not get its own rate.  A number:
+    that many ppm, no first pass.  -> (rows, offsets: what the demodulator takes in place of (x, starts), {"clock_ppm": the value
+    applied, a 0-d tensor, "clock_ppm_packets": the estimates [F] ("auto" only), "clock_status": int32 [F], non-zero for a
+    packet that runs past the recording or an eps that could not be applied})."""
+    how, half_taps = clock
+    F = starts.numel()
+    rows = {}
+    if how == "auto":
+        est = eng.clock_offset(eng.demod_frames(x, starts, want=("slope", "status"))["slope"])
+        rows["clock_ppm_packets"] = est * 1e6
+        eps = torch.nanmedian(torch.where(torch.isfinite(est), est, torch.full_like(est, float("nan"))))
+        rows["clock_ppm"] = eps * 1e6
+    else:
+        rows["clock_ppm"] = torch.full((), how, dtype=torch.float64, device=eng.device)
+        eps = rows["clock_ppm"] * 1e-6
+    out, offsets, rows["clock_status"] = eng.resample_frames(x, starts, eps.expand(F).contiguous(), half_taps=half_taps)
+    return out, offsets, rows
+
+
 def decode_report(iters, status, outer=None, crc_bad=None):
     """`last_decode_report` from the decoder's iteration counts and the group statuses (host arrays; no statuses without
     an outer code).  With the outer code (G, R) it covers the members of the groups -- the rest is fill.  crc_bad: the

@@ -24,6 +24,7 @@
 // The kernels read d_in only and write d_out only under the mask: a blanked neighbour cannot change a flag, and two runs
 // give identical bytes.
 #include "gf3rx_host.h"
+#include "gf3rx_storage.h"       // to_storage: mu in the storage type
 
 namespace {
 
@@ -118,13 +119,6 @@ __global__ __launch_bounds__(BL_THREADS) void blank_level_kernel(BlankArgs a) {
         a.level[2 * f + 1] = sqrt(en[m]);
     }
 }
-
-// mu in the storage type: rint (half to even) clamped to the range for the integer types, a cast for f32
-template <int DT> GF3_DEV typename RawT<DT>::E to_storage(double mu);
-template <> GF3_DEV double to_storage<DT_F64>(double mu) { return mu; }
-template <> GF3_DEV float to_storage<DT_F32>(double mu) { return (float)mu; }
-template <> GF3_DEV int16_t to_storage<DT_I16>(double mu) { return (int16_t)fmin(fmax(rint(mu), -32768.0), 32767.0); }
-template <> GF3_DEV uint8_t to_storage<DT_U8>(double mu) { return (uint8_t)fmin(fmax(rint(mu), 0.0), 255.0); }
 
 typedef unsigned long long u64;
 

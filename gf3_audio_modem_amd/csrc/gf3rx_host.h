@@ -22,6 +22,8 @@
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
 //   gf3rx_feedback.hip       feedback_kernel + gf3_feedback_equalise (residual channel from re-encoded codewords, divided out)
 //   gf3rx_blank.hip          blank_stats_kernel, blank_level_kernel, blank_write_kernel + gf3_blank_impulses (impulse blanking of the samples)
+//   gf3rx_resample.hip       resample_kernel + gf3_resample_frames, gf3_resample_coefficients (sampling-clock correction of the packet
+//                            bodies; the storage rounding it shares with gf3rx_blank.hip is gf3rx_storage.h)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
@@ -228,7 +230,7 @@ struct gf3_ctx {
     // single-precision screening plan of the frames-mode sync (gf3rx_fscreen.h): 2048-sample transforms, partitions of 2048 - wmax + 1 taps
     struct { bool ok = false; int Q = 0, Lp = 0, wmax = 0; cf *d_tw = nullptr, *d_twn = nullptr; float4* d_Hs = nullptr;
              float *d_H0N = nullptr, *d_Hinf = nullptr; } fscr;
-    // Two things a call may write after gf3_ctx_create.  (i) The default evaluation mode of the legacy entry point
+    // Three things a call may write after gf3_ctx_create.  (i) The default evaluation mode of the legacy entry point
     // gf3_sync_stream (gf3_sync_stream_mode sets it; gf3_sync_stream_ex takes the mode per call and never reads it).
     // 0: by stream length (screen from GF3_SCR_MIN_SAMPLES on); 1: fp64 only; 2: screen whenever a plan exists; 3: as 2 with the general kernel
     std::atomic<int> default_stream_mode{0};
@@ -244,6 +246,9 @@ struct gf3_ctx {
     std::mutex ws_mu;
     std::vector<Work> ws_work;
     std::vector<void*> ws_retired;
+    // (iii) The resampler's coefficient tables (gf3rx_resample.hip), [1025][2T] for T = 16 and T = 32: made on the first
+    // gf3_resample_frames with that T, under ws_mu, entered in `owned`
+    double* d_resample_h[2] = {nullptr, nullptr};
     std::vector<double> chirp;
     std::vector<cplx> known_pts;
     std::vector<void*> owned;           // every device allocation that lives as long as the context (gf3rx_ctx.hip)

@@ -800,6 +800,39 @@ class Engine:
                                                 _ptr(energy), _ptr(level), _ptr(counts), self._stream()))
         return out, counts, level, energy
 
+    def resample_frames(self, x, frame_offsets, eps, half_taps=16, out=None):
+        """Sampling-clock correction of the packet bodies (gf3_resample_frames): the body of packet f, 2P + D symbols from
+        frame_offsets[f] on, is read at the times j / (1 + eps_f) through a Kaiser-windowed sinc of 2 half_taps taps
+        (half_taps 16: clean up to 0.74 of Nyquist; 32: up to 0.85).  eps: a Python float for every packet, or a device / host
+        array [F]; eps > 0 means this recording's clock took fewer samples than were sent (ppm = 1e6 eps).  out: optional
+        contiguous tensor of F * M * S samples in the storage type, not x itself.
+        -> (rows [F, M S] in the storage type, offsets int64 [F] = f M S -- what any demodulator call takes next to rows --,
+        status int32 [F]: bit 0 the body is not inside the samples (row of zeros), bit 1 eps_f is not finite or beyond 2e-3
+        (row copied).)  Two calls give identical bytes."""
+        if half_taps not in (16, 32):
+            raise ValueError(f"resample_frames: half_taps must be 16 or 32, not {half_taps!r}")
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F, n = off.numel(), self.cfg.M * self.cfg.S
+        if isinstance(eps, (int, float, np.floating, np.integer)):
+            eps = torch.full((F,), float(eps), dtype=torch.float64, device=self.device)
+        else:
+            eps = self._dev(eps, torch.float64)
+            if eps.numel() != F:
+                raise ValueError(f"resample_frames: eps must be a number or hold one value per packet ({F}), not {eps.numel()}")
+        rows = self._out(out, (F, n), self.cfg.in_dtype, "F * M * S").reshape(F, n)
+        status = self._new((F,), torch.int32)
+        self._check(self.lib.gf3_resample_frames(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(eps), int(half_taps), _ptr(rows),
+                                                 _ptr(status), self._stream()))
+        return rows, torch.arange(F, dtype=torch.int64, device=self.device) * n, status
+
+    def clock_offset(self, slope):
+        """The sampling-clock offset eps a fitted phase slope stands for (demod_frames(want=("slope",))): the slope is the
+        phase per carrier index accrued over the (P + D) S samples between the pilot blocks' centres, so
+        eps = slope N / (2 pi (P + D) S).  A device expression: nothing is read back."""
+        cfg = self.cfg
+        return self._dev(slope, torch.float64) * (cfg.N / (2.0 * math.pi * (cfg.P + cfg.D) * cfg.S))
+
     def interleave(self, x, inverse=False):
         """The packet interleaver on whole packets of nbp = D*C*mu elements (gf3_interleave): x is uint8 or float32 with a
         multiple of nbp elements; coded element i of a packet moves to position (i s) mod nbp, `inverse` moves it back.

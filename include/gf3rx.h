@@ -662,6 +662,45 @@ int gf3_blank_impulses(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64
                        int32_t *d_counts_i32, void *stream);
 
 /*
+ * Sampling-clock correction in the sample domain, between sync (and blanking) and demodulation (not in the reference).
+ * Opt-in.  Two sound cards differ by tens to hundreds of ppm; the phase slope between the pilot blocks, which the
+ * demodulator fits and removes, is the visible part of that offset, the inter-carrier interference inside every symbol
+ * (about (pi k eps)^2 / 3 of carrier k's power) is not.  Here every packet body is resampled at its own rate.
+ *   Clock model: receiver sample j of a body that starts at s holds the transmitted waveform at time j (1 + eps); eps > 0
+ *   means the receiver took fewer samples than were sent; ppm = 1e6 eps.  From the fitted slope of gf3_demod_frames (the
+ *   phase per carrier index accrued over the (P + D) S samples between the pilot blocks' centres):
+ *       eps = slope N / (2 pi (P + D) S).
+ *   Packet f: body [s_f, s_f + M S), s_f = d_frame_offsets[f], M = 2P + D, eps_f = d_eps_f64[f]; all in fp64:
+ *       r   = 1.0 / (1.0 + eps_f)
+ *       t_j = (double)j * r                       (one rounding; j = 0 .. M S - 1)
+ *       i_j = floor(t_j),  mu = t_j - i_j,  q = mu * L,  p = min((int)q, L - 1),  a = q - p
+ *       c_k = h[p][k] + a * (h[p+1][k] - h[p][k])           (k = 0 .. 2T - 1; formed with one fused multiply-add)
+ *       out[f, j] = sum_k c_k * x[s_f + i_j + k - T + 1]    (ascending k, one fused multiply-add per tap; samples outside
+ *                                                            [0, n_in) read as 0)
+ *   Table: L = 1024 phases, rows p = 0 .. L, T = half_taps, Kaiser window with beta = 10:
+ *       h[p][k] = sinc(u) I0(beta sqrt(1 - (u / T)^2)) / I0(beta),   u = (k - T + 1) - p / L,   window 0 for |u| >= T;
+ *   rows 0 and L are unit impulses exactly, so eps = 0 returns the bodies unchanged for finite input.
+ *   gf3_resample_coefficients writes the (L + 1) x 2T table to host memory: pure host code, no GPU, no context.
+ *   Band: T = 16 keeps the interpolation error under -100 dB up to 0.74 pi (carriers <= 1500 of N = 4096), -40 dB at
+ *   0.85 pi; T = 32 under -100 dB up to 0.85 pi, about -20 dB at 0.95 pi.  Neither reaches the top few percent of the
+ *   band: full-band modes want T = 32 and still lose their highest carriers.
+ *   d_out is a packed [F, M S] array in the context's storage type (fp64 as is, f32 by a cast, i16 / u8 by rint, half to
+ *   even, clamped); frame offsets f M S into it feed every demodulator entry point.
+ *   d_status_i32 [F]: bit 0 -- the body is not inside [0, n_in) (the rule of gf3_blank_impulses), the row is zeros;
+ *   bit 1 -- eps_f is not finite or |eps_f| > 2e-3, the row is resampled with eps = 0 (a copy of the body).  Taps that
+ *   merely reach past either end of the recording read zeros and set nothing: with eps < 0 the last end pilot of a
+ *   recording that stops right after the body loses its last few samples.
+ *   GF3_EINVAL (the text names the function) for a null pointer with F > 0, d_out == d_in, F < 0, n_in < 0, half_taps
+ *   other than 16 or 32, and more than 2^31 - 1 tiles of 512 outputs in one call.  F == 0 is a no-op.  One launch, no
+ *   atomics (two runs give identical bytes), asynchronous on `stream`.  The context holds the device copy of the table
+ *   and makes it on the first call with that half_taps (one allocation and one blocking copy: not inside a stream
+ *   capture); later calls neither allocate nor synchronise.
+ */
+int gf3_resample_coefficients(int32_t half_taps, double *h_out);
+int gf3_resample_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                        const double *d_eps_f64, int32_t half_taps, void *d_out, int32_t *d_status_i32, void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64, 128
  * or 256; the shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, Z) for the
  * circulant whose row z has its one in column (z + s) mod Z.  Block columns 0 .. nb-mb-1 carry the message (systematic

@@ -1,0 +1,263 @@
+"""Sampling-clock correction on the GPU: gf3_resample_frames against the NumPy restatement (tests/resample_ref.py) at the
+smallest shapes at which the kernel can go wrong, its refusals, and `clock_correction` end to end through the façade on a
+packet recorded with an exactly synthesised clock offset.
+
+Shape of the kernel tests: N = 1024, CP = 56, P = 1, D = 2, so a body has M S = 4320 samples -- no multiple of 64 or of the
+kernel's tile of 1024 outputs, five tiles with a last one of 224 outputs (three and a half waves).  Four packets in one
+stream: a body that starts at sample 3 (taps reach before the stream), an ordinary one, one that ends exactly with the
+stream (taps reach behind it), one that runs one sample past it (status bit 0, a row of zeros).
+
+Tolerances.  fp64 storage: |out - ref| <= 1e-13 max|x|.  The kernel accumulates with fused multiply-adds and forms c_k with
+one, the restatement with neither: the gap is at most (2T + 2) 2^-53 sum|c_k| max|x|, below 1.5e-14 max|x| with
+sum|c_k| < 4 (asserted on the table in tests/test_resample_cpu.py); the bound adds a sevenfold margin for table entries
+that differ by 1e-15 between libm and NumPy.  f32 storage: the restatement cast to f32 within 1 ulp of f32.  Integer
+storage: |out - ref before rounding| <= 0.5 + 1e-9, the reference clamped to the type's range like the output."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import gf3_oracle as orc
+from tests import resample_ref as RR
+from tests.util import modeA2_params
+
+pytestmark = pytest.mark.gpu
+TORCH_OF = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32, np.dtype("int16"): torch.int16,
+            np.dtype("uint8"): torch.uint8}
+ENGINES = {}
+N_BODY = 4320
+STARTS = np.array([3, 3 + N_BODY + 17, 3 + 2 * N_BODY + 46, 3 + 2 * N_BODY + 47])
+N_IN = 3 + 3 * N_BODY + 46
+EPS_SETS = {"mixed": [1e-6, -50e-6, 2e-3, 0.0], "caps": [-2e-3, 2e-3, -2e-3, 1e-6], "refused": [np.nan, 3e-3, 0.0, -50e-6]}
+
+
+def engine_of(dtype):
+    from gf3_audio_modem_amd import Engine, RxConfig
+    key = np.dtype(dtype)
+    if key not in ENGINES:
+        pts, bits = orc.qpsk_table()
+        ENGINES[key] = Engine(RxConfig(N=1024, CP=56, P=1, D=2, data_bins=np.arange(10, 200), const_points=pts, const_bits=bits,
+                                       known_bits=np.zeros(1022, np.uint8), in_dtype=TORCH_OF[key], fit_lo=10, fit_hi=100))
+    assert ENGINES[key].cfg.M * ENGINES[key].cfg.S == N_BODY
+    return ENGINES[key]
+
+
+def samples(dtype, seed=1):
+    """Band-unlimited noise in the storage type; the integer types keep 2.8 x their spread inside the range (sum|c_k| < 2.8)."""
+    rng = np.random.default_rng(seed)
+    dtype = np.dtype(dtype)
+    if dtype.kind == "f":
+        return rng.normal(0.0, 3.0, N_IN).astype(dtype)
+    if dtype == np.int16:
+        return rng.integers(-10000, 10001, N_IN).astype(dtype)
+    return rng.integers(96, 161, N_IN).astype(dtype)
+
+
+def check(out, rows, raw, x):
+    dtype = x.dtype
+    if dtype == np.float64:
+        err = float(np.abs(out - raw).max())
+        bound = 1e-13 * float(np.abs(x).max())
+    elif dtype == np.float32:
+        err = float((np.abs(out.astype(np.float64) - rows.astype(np.float64)) / np.spacing(np.maximum(np.abs(rows), np.abs(out)))).max())
+        bound = 1.0
+    else:
+        info = np.iinfo(dtype)
+        # (the clamp is part of the storage rule: the body that ends with the stream rings below 0 in uint8 where its taps
+        # read the zeros behind it)
+        raw = np.clip(raw, info.min, info.max)
+        err = float(np.abs(out.astype(np.float64) - raw).max())
+        bound = 0.5 + 1e-9
+        decided = np.abs(np.abs(raw - np.floor(raw)) - 0.5) > 1e-6
+        assert np.array_equal(out[decided], rows[decided])
+    return err, bound
+
+
+@pytest.mark.parametrize("which", list(EPS_SETS))
+@pytest.mark.parametrize("T", [16, 32])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int16, np.uint8])
+def test_kernel_against_the_restatement(dtype, T, which):
+    eng = engine_of(dtype)
+    x = samples(dtype)
+    eps = np.array(EPS_SETS[which])
+    rows, raw, status = RR.resample_rows(x, STARTS, N_BODY, eps, T)
+    xt = torch.from_numpy(x).cuda()
+    out, off, st = eng.resample_frames(xt, STARTS, eps, half_taps=T)
+    assert out.dtype == xt.dtype and tuple(out.shape) == (4, N_BODY) and out.is_contiguous()
+    assert off.dtype == torch.int64 and off.tolist() == [0, N_BODY, 2 * N_BODY, 3 * N_BODY]
+    assert st.dtype == torch.int32 and st.cpu().numpy().tolist() == status.tolist()
+    assert np.array_equal(xt.cpu().numpy().view(np.uint8), x.view(np.uint8))          # the input is not written
+    out = out.cpu().numpy()
+    err, bound = check(out, rows, raw, x)
+    print(f"{np.dtype(dtype).name} T {T} {which}: status {status.tolist()}, largest error {err:.3e} (bound {bound:.3e})")
+    assert err <= bound
+    assert status[3] & 1 and not out[3].any()                # the packet that runs past the stream
+    if which == "refused":
+        assert status.tolist() == [2, 2, 0, 1]
+        for f in (0, 1, 2):                                  # NaN, 3e-3: copied like eps = 0
+            assert np.array_equal(out[f].view(np.uint8), x[STARTS[f]: STARTS[f] + N_BODY].view(np.uint8))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int16, np.uint8])
+def test_zero_offset_returns_the_bodies_and_two_runs_agree(dtype):
+    eng = engine_of(dtype)
+    x = samples(dtype, seed=2)
+    if np.dtype(dtype) == np.uint8:
+        x = np.random.default_rng(2).integers(0, 256, N_IN).astype(np.uint8)           # (the whole range: a copy clamps nothing)
+    xt = torch.from_numpy(x).cuda()
+    for T in (16, 32):
+        out, _, st = eng.resample_frames(xt, STARTS[:3], 0.0, half_taps=T)
+        assert st.tolist() == [0, 0, 0]
+        for f in range(3):
+            assert np.array_equal(out[f].cpu().numpy().view(np.uint8), x[STARTS[f]: STARTS[f] + N_BODY].view(np.uint8))
+    eps = torch.tensor([2e-3, -50e-6, 1e-6, 0.0], dtype=torch.float64)
+    runs = [eng.resample_frames(xt, STARTS, eps, half_taps=32) for _ in range(2)]
+    for a, b in zip(*runs):
+        assert a is not b and np.array_equal(a.cpu().numpy().view(np.uint8), b.cpu().numpy().view(np.uint8))
+
+
+def test_u8_clamps_at_both_ends():
+    """A square wave 0, 0, 255, 255, ... overshoots both ends of the range when it is read between its samples."""
+    eng = engine_of(np.uint8)
+    x = np.tile(np.array([0, 0, 255, 255], dtype=np.uint8), N_IN // 4 + 1)[:N_IN]
+    rows, raw, _ = RR.resample_rows(x, STARTS[1:2], N_BODY, 2e-3, 16)
+    assert raw.min() < -5 and raw.max() > 260
+    out = eng.resample_frames(torch.from_numpy(x).cuda(), STARTS[1:2], 2e-3)[0].cpu().numpy()
+    decided = np.abs(np.abs(raw - np.floor(raw)) - 0.5) > 1e-6
+    assert np.array_equal(out[decided], rows[decided]) and out.min() == 0 and out.max() == 255
+
+
+def test_no_packets_an_own_buffer_and_refusals():
+    from gf3_audio_modem_amd import _lib
+    eng = engine_of(np.float64)
+    x = samples(np.float64)
+    xt = torch.from_numpy(x).cuda()
+    rows, off, st = eng.resample_frames(xt, torch.empty(0, dtype=torch.int64), 1e-4)
+    assert tuple(rows.shape) == (0, N_BODY) and off.numel() == 0 and st.numel() == 0
+    mine = torch.full((2 * N_BODY,), 7.0, dtype=torch.float64, device="cuda")
+    rows, _, _ = eng.resample_frames(xt, STARTS[:2], [1e-4, -1e-4], out=mine)
+    assert rows.data_ptr() == mine.data_ptr() and tuple(rows.shape) == (2, N_BODY)
+    assert np.abs(rows.cpu().numpy() - RR.resample_rows(x, STARTS[:2], N_BODY, [1e-4, -1e-4], 16)[1]).max() <= 1e-13 * np.abs(x).max()
+    with pytest.raises(ValueError, match="half_taps"):
+        eng.resample_frames(xt, STARTS, 0.0, half_taps=8)
+    with pytest.raises(ValueError, match="eps"):
+        eng.resample_frames(xt, STARTS, [0.0, 0.0])
+    with pytest.raises(ValueError, match="out"):
+        eng.resample_frames(xt, STARTS, 0.0, out=mine)
+    lib, p = eng.lib, _lib.ptr
+    off = torch.from_numpy(STARTS).cuda()
+    eps = torch.zeros(4, dtype=torch.float64, device="cuda")
+    out = torch.full((4, N_BODY), 7.0, dtype=torch.float64, device="cuda")
+    status = torch.full((4,), 77, dtype=torch.int32, device="cuda")
+    good = [eng._h, p(xt), xt.numel(), p(off), 4, p(eps), 16, p(out), p(status), None]
+    cases = [(at, None) for at in (0, 1, 3, 5, 7, 8)] + [(4, -1), (2, -1), (6, 8), (6, 0), (6, 24), (6, 64), (7, p(xt)), (4, 2 ** 30)]
+    for at, value in cases:
+        args = list(good)
+        args[at] = value
+        assert lib.gf3_resample_frames(*args) == _lib.GF3_EINVAL, (at, value)
+        assert b"gf3_resample_frames" in lib.gf3_last_error(None)
+    args = list(good)
+    args[4], args[7] = 0, p(xt)                                    # refused even when there is nothing to do
+    assert lib.gf3_resample_frames(*args) == _lib.GF3_EINVAL
+    args = [eng._h, None, 0, None, 0, None, 16, None, None, None]  # F = 0: no array needs an address
+    assert lib.gf3_resample_frames(*args) == 0
+    torch.cuda.synchronize()
+    assert (out == 7.0).all() and (status == 77).all()             # no refusal wrote anything
+    assert lib.gf3_resample_frames(*good) == 0
+    torch.cuda.synchronize()
+    assert status.tolist() == [0, 0, 0, 1] and torch.equal(out[1], xt[STARTS[1]: STARTS[1] + N_BODY])
+
+
+def test_clock_offset_is_the_formula():
+    eng = engine_of(np.float64)
+    slope = np.array([0.0, 1e-3, -2.5e-3, np.nan, 0.7])
+    p = orc.RxParams(N=1024, CP=56, P=1, D=2, const_points=orc.qpsk_table()[0], const_bits=orc.qpsk_table()[1])
+    got = eng.clock_offset(torch.from_numpy(slope).cuda())
+    assert got.is_cuda and got.dtype == torch.float64
+    np.testing.assert_allclose(got.cpu().numpy(), RR.clock_offset(slope, p), rtol=4e-16, atol=0.0, equal_nan=True)
+    assert np.isclose(RR.clock_offset(2 * np.pi, p), 1024 / (3 * 1080))
+
+
+# ---- end to end through the façade ----------------------------------------------------------------------------------
+LEAD, TAIL = 1500, 1500
+
+
+def evm_db(eq, ref):
+    return 10.0 * np.log10(np.mean(np.abs(eq - ref) ** 2) / np.mean(np.abs(ref) ** 2))
+
+
+def recordings(rx, coded, seed):
+    """One A2 packet of P = 2 pilot and D = 4 data symbols carrying `coded`, at 40 dB SNR, as recorded with no clock offset,
+    +100 ppm and -60 ppm (tests/resample_ref.py::drifted_stream; the same noise samples on each)."""
+    p = dataclasses.replace(modeA2_params(np.asarray(rx.known_sequence[: rx.K * rx.mu], dtype=np.uint8)), P=2, D=4)
+    rng = np.random.default_rng(seed)
+    fill = orc.qpsk_table()[0][rng.integers(0, 4, size=p.K - p.C)]
+    out = {}
+    for ppm in (0.0, 100.0, -60.0):
+        r = RR.drifted_stream(coded, fill, p, ppm * 1e-6, lead=LEAD, tail=TAIL)
+        if ppm == 0.0:
+            body = r[LEAD + p.Lc: LEAD + p.Lc + p.M * p.S]
+            noise = np.random.default_rng(seed + 1).normal(0.0, float(np.sqrt(np.mean(body ** 2))) / 100.0, len(r) + 64)
+        out[ppm] = r + noise[: len(r)]
+    return out
+
+
+def symbols(rx, r, eps=None):
+    """The equalised symbols of the engine's demodulation at the sync's starts, of the samples as they are or resampled"""
+    eng = rx._engine(np.dtype("float64"))
+    x = eng._samples(r)
+    starts = (eng.sync_stream(x) + 2)[:-1]
+    if eps is not None:
+        x, starts, st = eng.resample_frames(x, starts, eps, half_taps=rx.clock_taps // 2)
+        assert not st.any()
+    return eng.demod_frames(x, starts, want=("eq",))["eq"].cpu().numpy()
+
+
+@pytest.mark.parametrize("encoding", ["None", "QCLDPC-1/2"])
+def test_facade_clock_correction(encoding):
+    """Mode A2 with no_pilots = 2, packet_length = 4: one packet, +100 ppm, 40 dB SNR.  The figures are printed."""
+    from gf3_audio_modem_amd.OFDM import receiver
+    rx = receiver("A2", encoding=encoding, no_pilots=2, packet_length=4)
+    rng = np.random.default_rng(21)
+    per_packet = rx.packet_length * rx.data_bits_per_symbol
+    if encoding == "None":
+        payload = rng.integers(0, 2, size=per_packet)
+        coded = payload
+    else:
+        payload = rng.integers(0, 2, size=768 * (per_packet // 1536))
+        coded = np.asarray(rx.encode(payload))
+        coded = np.concatenate([coded, rng.integers(0, 2, size=per_packet - len(coded))])
+    rec = recordings(rx, coded.astype(np.uint8), seed=22)
+    want = rx.receive(rec[0.0])[0]
+    assert np.array_equal(want[: len(payload)], payload) and rx.last_clock_ppm is None and rx.last_clock_ppm_packets is None
+    ref = symbols(rx, rec[0.0])
+    baseline = evm_db(symbols(rx, rec[100.0]), ref)
+
+    rx.clock_correction = "auto"
+    got = rx.receive(rec[100.0])[0]
+    ppm, per = rx.last_clock_ppm, rx.last_clock_ppm_packets
+    corrected = evm_db(symbols(rx, rec[100.0], eps=ppm * 1e-6), ref)
+    print(f"{encoding}: estimate {ppm:.2f} ppm; error vector against the undrifted packet {baseline:.1f} dB -> {corrected:.1f} dB")
+    assert isinstance(ppm, float) and abs(ppm - 100.0) <= 2.0
+    assert per.shape == (1,) and per.dtype == np.float64 and per[0] == ppm
+    assert np.array_equal(got, want)
+    assert corrected <= baseline - 10.0
+
+    rx.clock_correction, rx.clock_taps = 100.0, 64
+    got = rx.receive(rec[100.0])[0]
+    assert np.array_equal(got, want) and rx.last_clock_ppm == 100.0 and rx.last_clock_ppm_packets is None
+
+    rx.clock_correction, rx.clock_taps = "auto", 32
+    got = rx.receive_diversity([rec[100.0], rec[-60.0]])[0]
+    ppm = rx.last_clock_ppm
+    print(f"{encoding}: two recordings at +100 and -60 ppm: estimates {ppm.tolist()}")
+    assert ppm.shape == (2,) and ppm[0] > 50.0 and ppm[1] < -30.0 and rx.last_clock_ppm_packets.shape == (2, 1)
+    assert np.array_equal(got[: len(payload)], payload)
+
+    rx.clock_correction = None
+    rx.receive(rec[0.0])
+    assert rx.last_clock_ppm is None and rx.last_clock_ppm_packets is None
+    rx.clock_correction, rx.host_chunk_samples = "auto", 1 << 22
+    with pytest.raises(NotImplementedError, match="clock_correction.*piece-wise host path"):
+        rx.receive(rec[100.0])
