@@ -194,6 +194,22 @@ class CamG:
         self.clock_taps = 32
         self.last_clock_ppm = None
         self.last_clock_ppm_packets = None
+        # every encoding: channel_denoising = True denoises the pilot channel estimate in the delay domain ahead of everything
+        # that rests on it (Engine.denoise_pilots): the least-squares estimate spends one unknown per carrier on
+        # a channel of a few dozen to a few hundred taps, and only the averaging over no_pilots symbols per side holds its
+        # noise down.  Every delay-domain tap below denoise_threshold x the tap noise variance (9.0: 3 sigma), the noise
+        # measured from the pilot repeats, is set to zero; with it no_pilots = 2 estimates about as well as 32 do without,
+        # i.e. the reference's 20 can drop to 2 (180/184 instead of 180/220 of the air time for data).  Set it for short
+        # pilot blocks and low SNR.  It changes nothing where more than a quarter of the taps stand above the threshold (a
+        # clean recording), loses up to a few dB on a diffuse channel as long as the symbol, and assumes no response at DC
+        # and Nyquist (an audio path has none).  Hs and He returned by receive() are the denoised estimates; the first pass of
+        # clock_correction = "auto" stays plain.  receive() leaves (noise variance, taps kept, largest kept delay, largest
+        # kept precursor, applied) per packet and side [packets, 2, 5] in `last_denoise_report` -- the delay spread tells
+        # whether the cyclic prefix is long enough --, receive_diversity() [B, packets, 2, 5]; None otherwise.  ValueError with
+        # fused_llr, no_pilots < 2, a threshold that is not a finite number > 0; NotImplementedError on the piece-wise host path.
+        self.channel_denoising = False
+        self.denoise_threshold = 9.0
+        self.last_denoise_report = None
         self._engines = {}
 
     def __repr__(self):
@@ -249,7 +265,8 @@ class CamG:
                           make_code=lambda *a, **kw: _qcldpc_code(*a, **kw), codeword_crc=bool(self.codeword_crc),
                           phase_tracking=bool(self.phase_tracking), decoder_feedback=self.decoder_feedback,
                           feedback_window=self.feedback_window, feedback_min_known=self.feedback_min_known,
-                          loading=None if order is None else tuple(order.tolist()))
+                          loading=None if order is None else tuple(order.tolist()),
+                          denoise=(self.denoise_threshold, self.no_pilots) if self.channel_denoising else None)
 
     def _qcldpc_rate(self):
         """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
@@ -550,6 +567,9 @@ class receiver(transmitter):
         blanking = Engine.check_blanking(self.blanking_threshold, self.blanking_guard) if self.impulse_blanking else None
         clock = check_clock(self.clock_correction, self.clock_taps)
         r = _as_samples(signal)
+        if chain.denoise is not None and not graph_output and (getattr(self, "host_chunk_samples", None) or len(r) > (1 << 27)):
+            raise NotImplementedError("channel_denoising: the piece-wise host path of long recordings (or host_chunk_samples) "
+                                      "has no denoising pass; receive shorter recordings")
         if chain.loading is not None:                           # (what a loading has no path for: also before any GPU work)
             if graph_output:
                 raise NotImplementedError("bit_loading: the plots draw one constellation; receive with graph_output = False")
@@ -590,6 +610,8 @@ class receiver(transmitter):
         o = chain.demodulate(eng, x, starts, rate, fused, graph_output)
         # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
         need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
+        if "denoise_report" in o:                               # (under channel_denoising only)
+            blanked["last_denoise_report"] = o["denoise_report"]
         if rate is not None:
             feedback = None
             if chain.decoder_feedback:
@@ -616,6 +638,7 @@ class receiver(transmitter):
         self.last_blanked, self.last_sample_level = got.get("last_blanked"), got.get("last_sample_level")
         self.last_clock_ppm = float(got["clock_ppm"]) if clock else None
         self.last_clock_ppm_packets = got.get("clock_ppm_packets")
+        self.last_denoise_report = got.get("last_denoise_report")
         for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only;
             setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
         if rate is not None:
@@ -641,7 +664,8 @@ class receiver(transmitter):
         (after combining) in dB.  A branch that lost lock is NOT rejected and poisons the sum: look at its row of
         `last_branch_snr_db`.  Under `clock_correction` every recording is estimated and corrected on its own (a second laptop
         is a second clock) and `last_clock_ppm` is an array [B].  ValueError: B outside 1 .. 4, branches with different packet counts, llr_weighting
-        "noise2d", fused_llr, phase_tracking, decoder_feedback.  NotImplementedError: impulse_blanking, graph_output,
+        "noise2d", fused_llr, phase_tracking, decoder_feedback.  Under `channel_denoising` every recording's estimate is
+        denoised on its own and `last_denoise_report` is [B, packets, 2, 5].  NotImplementedError: impulse_blanking, graph_output,
         the piece-wise host path of long recordings (or host_chunk_samples)."""
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
@@ -691,7 +715,7 @@ class receiver(transmitter):
                 x, st, rows_b = correct_clock(eng, x, st, clock)
                 outs[b] = (x, st)
                 clk.append(rows_b)
-        outs = [eng.demod_frames(x, st, want=("eq", "Hs", "He", "slope", "status")) for x, st in outs]
+        outs = [eng.demod_frames(x, st, want=("eq", "Hs", "He", "slope", "status"), denoise=chain.check_denoise()) for x, st in outs]
         # 3. combine, then the coded chain or the hard decision and un-whitening
         pts = self._tables()[0]
         need = {"Hs0": outs[0]["Hs"][0], "He0": outs[0]["He"][0], "slope": outs[0]["slope"], "starts": torch.stack(starts)}
@@ -711,6 +735,8 @@ class receiver(transmitter):
             need["clock_ppm"] = torch.stack([c["clock_ppm"] for c in clk])
             if "clock_ppm_packets" in clk[0]:
                 need["clock_ppm_packets"] = torch.stack([c["clock_ppm_packets"] for c in clk])
+        if "denoise_report" in outs[0]:                         # (under channel_denoising only)
+            need["denoise_report"] = torch.stack([o["denoise_report"] for o in outs])
         got = fetch({**need, **rows, "ragged": torch.cat([o["status"] for o in outs] + [c["clock_status"] for c in clk])})
         if got["ragged"].any():
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
@@ -720,6 +746,7 @@ class receiver(transmitter):
         self.last_branch_starts = got["starts"]
         self.last_branch_snr_db = got.get("last_branch_snr_db")
         self.last_clock_ppm, self.last_clock_ppm_packets = got.get("clock_ppm"), got.get("clock_ppm_packets")
+        self.last_denoise_report = got.get("denoise_report")
         if "last_snr_db" in got:
             self.last_snr_db = got["last_snr_db"]
         if rate is not None:

@@ -119,6 +119,7 @@ class CodedChain:
     feedback_window: tuple = (2, 8)         # (half_symbols, half_bins) of Engine.feedback_equalise
     feedback_min_known: int = 4             # known symbols a window needs before its gain is used
     loading: tuple = None                   # adaptive bit loading (loading.py): the validated order per data carrier; per_packet then counts its bits
+    denoise: tuple = None                   # receive() under `channel_denoising`: (denoise_threshold as the façade holds it, no_pilots)
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
@@ -186,6 +187,9 @@ class CodedChain:
         if fused and self.phase_tracking:
             raise ValueError("phase_tracking needs fused_llr = False: the fused kernel never materialises the equalised "
                              "symbols the tracker works on")
+        if self.check_denoise() is not None and fused:
+            raise ValueError("channel_denoising needs fused_llr = False: the denoiser sits between the two-phase form's "
+                             "launches, and the fused kernel is one launch")
         self.feedback()
         if self.decoder_feedback and rate is None:
             raise ValueError(f"decoder_feedback needs a 'QCLDPC-*' encoding, not {self.encoding!r}")
@@ -193,6 +197,17 @@ class CodedChain:
             raise ValueError("decoder_feedback needs fused_llr = False: the fused kernel never materialises the equalised "
                              "symbols the feedback corrects")
         return rate, fused
+
+    def check_denoise(self):
+        """The denoiser's threshold, or None where `channel_denoising` is off.  ValueError for a threshold that is not a
+        finite number > 0 and for fewer than two pilot symbols per side."""
+        if self.denoise is None:
+            return None
+        from .engine import Engine
+        threshold = Engine.check_denoise(self.denoise[0])
+        if self.denoise[1] < 2:
+            raise ValueError(f"channel_denoising measures the noise from the pilot repeats: no_pilots >= 2, not {self.denoise[1]!r}")
+        return threshold
 
     def feedback(self):
         """(passes, half_symbols, half_bins, min_known) of the decoder feedback; ValueError for a count that is not an
@@ -235,11 +250,14 @@ class CodedChain:
     # ---- receive side ----------------------------------------------------------------------------------------------------
     def demodulate(self, eng, x, starts, rate, fused, plots):
         """receive()'s demodulator call: Hs, He, slopes, ragged flag; eq for the staged soft path, eq and Hest for the plots
-        (which therefore take the staged path); LLRs straight from the samples when fused."""
+        (which therefore take the staged path); LLRs straight from the samples when fused.  Under `channel_denoising` the
+        estimate behind all of them is the denoised one, and 'denoise_report' comes back too."""
         fused = fused and not plots
         soft = (rate is not None and not fused) or self.loading is not None
         want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plots else ("eq",) if soft else ())
-        return eng.demod_frames_llr(x, starts, weight="csi", want=want) if fused else eng.demod_frames(x, starts, want=want)
+        if fused:
+            return eng.demod_frames_llr(x, starts, weight="csi", want=want)
+        return eng.demod_frames(x, starts, want=want, denoise=self.check_denoise())
 
     def llrs(self, eng, o, points):
         """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: rows for the host}: the SNR in dB

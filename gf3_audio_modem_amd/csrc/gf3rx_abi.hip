@@ -95,6 +95,23 @@ extern "C" int gf3_demod_frames(gf3_ctx* c, const void* d_in, int64_t n_in, cons
                                 int32_t* d_status, void* stream) {
     return gf3_demod_frames_px(c, d_in, n_in, d_off, F, d_bits, d_eq, d_Hs, d_He, d_slope, d_Hest, d_status, nullptr, 1, -1, stream);
 }
+// The two-phase form with the pilot sums denoised between its first and second launch (gf3rx_denoise.hip).
+extern "C" int gf3_demod_frames_dn(gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F,
+                                   uint8_t* d_bits, void* d_eq, void* d_Hs, void* d_He, double* d_slope, void* d_Hest,
+                                   int32_t* d_status, void* d_work, double threshold, double* d_report, void* stream) {
+    DeviceGuard dg(c);
+    if (!c) return fail(c, GF3_EINVAL, "gf3_demod_frames_dn: null context");
+    if (c->cfg.P < 2) return fail(c, GF3_EINVAL, "gf3_demod_frames_dn: the noise is measured from the pilot repeats, P >= 2 (P=%d)", c->cfg.P);
+    if (!(threshold > 0.0) || !(fabs(threshold) < INFINITY)) return fail(c, GF3_EINVAL, "gf3_demod_frames_dn: the threshold must be a finite number > 0");
+    if (!d_work) return fail(c, GF3_EINVAL, "gf3_demod_frames_dn: null workspace (gf3_demod_workspace_bytes)");
+    if (F == 0) return GF3_OK;
+    if (!d_in || !d_off || !d_bits || F < 0) return fail(c, GF3_EINVAL, "gf3_demod_frames_dn: bad argument");
+    DemodArgs a = demod_args(c);
+    a.in = d_in; a.n_in = n_in; a.off = d_off; a.bits = d_bits; a.stamps = c->stamps;
+    a.eq = (cplx*)d_eq; a.Hs = (cplx*)d_Hs; a.He = (cplx*)d_He; a.slope = d_slope; a.Hest = (cplx*)d_Hest; a.status = d_status;
+    g_demod_last.set(c, stream, 2, 0);
+    return demod_split(c, a, F, d_work, (hipStream_t)stream, threshold, d_report);
+}
 extern "C" int gf3_demod_frames_last(const gf3_ctx* c, void* stream, int32_t* path, int32_t* listed_capacity) {
     return g_demod_last.query("gf3_demod_frames_last", c, stream, path, listed_capacity);
 }

@@ -93,7 +93,16 @@ extern "C" int gf3_demod_split_plan(const gf3_ctx* c, int64_t F, int32_t mode, i
     return F > 0 && demod_wants_split(c, F, mode) ? 1 : 0;
 }
 
-int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStream_t st) {
+hipError_t launch_pilot_sum(const gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F, double* psum, hipStream_t st) {
+    PilotSumArgs pa{d_in, n_in, d_off, c->cfg.CP, c->S, c->cfg.P, c->cfg.D, c->NC, psum};
+    const int64_t grid = F * 2 * (c->NC / 256);
+    DISPATCH_DT(c->cfg.in_dtype, hipLaunchKernelGGL((pilot_sum_kernel<DTC>), dim3((unsigned)grid), dim3(256), 0, st, pa));
+    return hipGetLastError();
+}
+
+// denoise > 0: the pilot sums are denoised in the delay domain with that threshold before the estimate stage reads them
+// (gf3rx_denoise.hip; d_report [F][2][5] or null); 0: not
+int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStream_t st, double denoise, double* d_report) {
     const int NC = c->NC, K = c->K;
     char* w = (char*)d_work;
     double* psum = (double*)w;
@@ -105,11 +114,10 @@ int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStrea
     if (!a.slope) a.slope = (double*)w;
     a.psum = psum;
     split_geometry(c, F, a.Dc, a.nchunk);
-    {
-        PilotSumArgs pa{a.in, a.n_in, a.off, a.CP, a.S, a.P, a.D, NC, psum};
-        const int64_t grid = F * 2 * (NC / 256);
-        DISPATCH_DT(a.dt, hipLaunchKernelGGL((pilot_sum_kernel<DTC>), dim3((unsigned)grid), dim3(256), 0, st, pa));
-        HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch_pilot_sum(c, a.in, a.n_in, a.off, F, psum, st));
+    if (denoise != 0.0) {
+        const int rc = launch_denoise(c, a.in, a.n_in, a.off, F, denoise, psum, d_report, st);
+        if (rc != GF3_OK) return rc;
     }
     {
         hipError_t e = hipSuccess;

@@ -24,10 +24,11 @@
 //   gf3rx_blank.hip          blank_stats_kernel, blank_level_kernel, blank_write_kernel + gf3_blank_impulses (impulse blanking of the samples)
 //   gf3rx_resample.hip       resample_kernel + gf3_resample_frames, gf3_resample_coefficients (sampling-clock correction of the packet
 //                            bodies; the storage rounding it shares with gf3rx_blank.hip is gf3rx_storage.h)
+//   gf3rx_denoise.hip        denoise_kernel + gf3_denoise_pilots (delay-domain denoising of the pilot sums ahead of the estimate stage)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
-//   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex), gf3_demod_frames_llr, gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
+//   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex, _dn), gf3_demod_frames_llr, gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -375,7 +376,11 @@ hipError_t launch_demod_spectra(const gf3_ctx* c, const DemodArgs& a, int64_t F,
 hipError_t launch_demod_soft(const gf3_ctx* c, const DemodArgs& a, int64_t F, hipStream_t st);      // gf3rx_demod_soft.hip: LLRs, no bits
 // gf3rx_demod_split.hip + gf3rx_dsplit_{qpsk,scan,full}.hip: the two-phase form for long packets, few at a time
 bool demod_wants_split(const gf3_ctx* c, int64_t F, int mode);
-int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStream_t st);
+int demod_split(const gf3_ctx* c, DemodArgs a, int64_t F, void* d_work, hipStream_t st, double denoise = 0.0, double* d_report = nullptr);
+hipError_t launch_pilot_sum(const gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F, double* psum, hipStream_t st);
+// gf3rx_denoise.hip: the delay-domain denoiser on pilot sums [F][2][N], in place (refuses P < 2 and a threshold that is not finite or <= 0)
+int launch_denoise(const gf3_ctx* c, const void* d_in, int64_t n_in, const int64_t* d_off, int64_t F, double threshold,
+                   double* d_psum, double* d_report, hipStream_t st);
 hipError_t launch_dsplit_qpsk(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
 hipError_t launch_dsplit_scan(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);
 hipError_t launch_dsplit_full(const gf3_ctx* c, const DemodArgs& a, int64_t grid, hipStream_t st);

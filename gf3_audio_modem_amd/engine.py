@@ -250,7 +250,33 @@ class Engine:
         self._check(self.lib.gf3_rfft_batch(self._h, _ptr(x), x.numel(), _ptr(offsets), n, _ptr(out), self._stream()))
         return out
 
-    def demod_frames(self, x, frame_offsets, want=(), out_bits=None, split=None, precision=None):
+    @staticmethod
+    def check_denoise(threshold):
+        """ValueError for a denoising threshold that is not a finite number > 0 -> the threshold as a float."""
+        number = isinstance(threshold, (int, float, np.integer, np.floating)) and not isinstance(threshold, (bool, np.bool_))
+        if not number or not math.isfinite(float(threshold)) or float(threshold) <= 0.0:
+            raise ValueError(f"denoising threshold must be a finite number > 0, not {threshold!r}")
+        return float(threshold)
+
+    def denoise_pilots(self, x, frame_offsets, threshold=9.0):
+        """The delay-domain denoiser of the pilot channel estimate on its own (gf3_denoise_pilots): per packet and side the
+        time-domain sum of the P pilot symbols, with every delay-domain tap of its channel estimate below `threshold`
+        times the tap noise variance -- measured from the pilot repeats -- set to zero.
+        -> (psum float64 [F, 2, N], report float64 [F, 2, 5] = (v, kept, post, pre, applied)): noise variance, taps kept,
+        the largest kept delay and the largest kept precursor (the measured delay spread), and whether the row was
+        rewritten (not when v is not finite, the packet is ragged or more than N/4 taps are kept).  Needs P >= 2.  Fixed
+        summation order: two calls give identical bytes."""
+        threshold = self.check_denoise(threshold)
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F = off.numel()
+        psum = self._new((F, 2, self.cfg.N), torch.float64)
+        report = self._new((F, 2, 5), torch.float64)
+        self._check(self.lib.gf3_denoise_pilots(self._h, _ptr(x), x.numel(), _ptr(off), F, threshold, _ptr(psum), _ptr(report),
+                                                self._stream()))
+        return psum, report
+
+    def demod_frames(self, x, frame_offsets, want=(), out_bits=None, split=None, precision=None, denoise=None):
         """Fused a3-a10.  Returns dict with 'bits' (packed uint8
         [F, bytes_per_frame]) plus any of 'eq','Hs','He','slope','Hest','status'.
         split: None -- the library chooses between one packet per workgroup and the two-phase form for long packets,
@@ -260,14 +286,30 @@ class Engine:
         output and f32 / i16 / u8 samples the data symbols are transformed in fp32 under a proven bound and the fp64 kernel
         runs only on the packets the bound cannot decide -- the all-fp64 outputs, bit for bit.  "fp64": the all-fp64 kernel
         on every packet.  "screen": ask for the screened path (it still runs all fp64 where it does not apply).
-        demod_frames_last() tells which way a call went."""
+        demod_frames_last() tells which way a call went.
+        denoise: None, or the threshold of the delay-domain denoiser (denoise_pilots; 9.0 is 3 sigma): the call then takes
+        the two-phase form (gf3_demod_frames_dn) with the pilot sums denoised ahead of the channel estimate, and the dict
+        gains 'denoise_report' float64 [F, 2, 5].  Not with split=False or precision="screen" (the two-phase form has no
+        fp32 screen): ValueError."""
         if precision not in (None, "fp64", "screen"):
             raise ValueError(f"precision must be None, 'fp64' or 'screen', not {precision!r}")
+        if denoise is not None:
+            denoise = self.check_denoise(denoise)
+            if split is False or precision == "screen":
+                raise ValueError("denoise runs in the two-phase form: not with split=False or precision='screen'")
         x = self._samples(x)
         off = self._dev(frame_offsets, torch.int64)
         F = off.numel()
         bits = out_bits if out_bits is not None else self._new((F, self.bytes_per_frame), torch.uint8)
         o = {"bits": bits, **self._wanted(want, F, ("eq", "Hs", "He", "slope", "Hest", "status"))}
+        if denoise is not None:
+            work = self._new((int(self.lib.gf3_demod_workspace_bytes(self._h, F)),), torch.uint8)     # (_split_work(F, True), also for F = 0)
+            o["denoise_report"] = self._new((F, 2, 5), torch.float64)
+            self._check(self.lib.gf3_demod_frames_dn(
+                self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(bits), _ptr(o.get("eq")), _ptr(o.get("Hs")),
+                _ptr(o.get("He")), _ptr(o.get("slope")), _ptr(o.get("Hest")), _ptr(o.get("status")),
+                _ptr(work), denoise, _ptr(o["denoise_report"]), self._stream()))
+            return o
         work, mode = self._split_work(F, split)
         self._check(self.lib.gf3_demod_frames_px(
             self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(bits), _ptr(o.get("eq")), _ptr(o.get("Hs")),

@@ -197,6 +197,41 @@ int gf3_demod_frames_px(gf3_ctx *ctx, const void *d_in, int64_t n_in,
                         double *d_slope, void *d_Hest, int32_t *d_status,
                         void *d_work, int32_t mode, int32_t precision, void *stream);
 int gf3_demod_frames_last(const gf3_ctx *ctx, void *stream, int32_t *path, int32_t *listed_capacity);
+
+/*
+ * Delay-domain denoising of the pilot channel estimate (not in the reference, whose least-squares estimate treats its K
+ * carriers as K unknowns, OFDM.py:443-451; an acoustic channel has a few dozen to a few hundred significant taps).  Per
+ * packet and per side (start / end pilot block), with tau = threshold and x_p[n] the N samples after the prefix of pilot
+ * symbol p = 0 .. P-1, all in fp64:
+ *     S[n] = sum_p x_p[n]                                      (the two-phase form's pilot sum, bit for bit)
+ *     v    = sum_n sum_p (x_p[n] - S[n]/P)^2 / ((P-1) N)       (noise variance, from the pilot repeats)
+ *     H_k  = rfft(S)_k / (P known_k), k = 1 .. K;  H_0 = H_{N/2} = 0;   h = irfft(H)     (N real taps)
+ *     s2   = 2 v / (N P) sum_k 1/|known_k|^2                   (noise variance of one tap)
+ *     tap n is kept iff h[n]^2 > tau s2 (strict);  kept = their number;  post = the largest kept n < N/2, -1 if none;
+ *     pre = the largest N - n among kept n >= N/2, 0 if none
+ *     the row stays bit for bit as it was (applied = 0) when v is not finite, when the packet does not lie inside the
+ *     samples (its pilot sum is the zero row; reported as v = 0, kept = 0, post = -1, pre = 0), or when kept > N/4 (the
+ *     channel is not sparse at this noise level; also noiseless input, where every tap is kept);
+ *     else S' = irfft(X'), X'_k = rfft(h keep)_k P known_k for k = 1 .. K, X'_0 and X'_{N/2} as in rfft(S); applied = 1.
+ *   d_report [F][2][5] float64 = {v, kept, post, pre, applied} per (packet, side), or NULL.  post and pre are the measured
+ *   delay spread: whether the cyclic prefix is long enough.
+ *   - gf3_denoise_pilots: the stage on its own (tests, tools): the pilot sums of the two-phase form, then the denoiser.
+ *     d_psum_out [F][2][N] float64.
+ *   - gf3_demod_frames_dn: gf3_demod_frames_ex in its two-phase form, always, with the denoiser run on the workspace's pilot
+ *     sums between the first and the second launch; everything after that (estimate, slope fit, data stage, eq / Hest
+ *     dumps) is the two-phase form as it stands, on the cleaner sums.  There is no fused-LLR variant and no fp32 screen.
+ *     d_work of gf3_demod_workspace_bytes(ctx, F) is required.
+ *   GF3_EINVAL (the text names the function) for a context with P < 2, a threshold that is not finite or <= 0, a NULL
+ *   workspace (gf3_demod_frames_dn), a null pointer with F > 0, F < 0.  F == 0 is a no-op.  One workgroup per (packet,
+ *   side), four transforms each; reductions in a fixed order, no atomics: two runs give identical bytes.
+ */
+int gf3_denoise_pilots(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                       double threshold, double *d_psum_out, double *d_report, void *stream);
+int gf3_demod_frames_dn(gf3_ctx *ctx, const void *d_in, int64_t n_in,
+                        const int64_t *d_frame_offsets, int64_t F,
+                        uint8_t *d_bits_packed, void *d_eq, void *d_Hs, void *d_He,
+                        double *d_slope, void *d_Hest, int32_t *d_status,
+                        void *d_work, double threshold, double *d_report, void *stream);
 /* tests: the screening pass alone.  d_ep32 [F][D][C] complex64: the rotated fp32 symbols (2 X conj(g)) of the data carriers
  * in data_bins order; d_E [F][D] float32: the bound of each symbol; d_cls [F] int32: 0 decided, 1 listed; d_list: AT LEAST
  * gf3_demod_screen_workspace_bytes(ctx, F) bytes, [count | pad to 64 bytes | listed packet numbers]; d_bits_packed gets the
