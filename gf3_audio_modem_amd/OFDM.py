@@ -19,10 +19,11 @@ import os
 import numpy as np
 import torch
 
-from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, check_clock, correct_clock, decode_report, fetch  # noqa: F401  (the tables: importable from here as before)
+from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report  # noqa: F401  (the tables: importable from here as before)
 from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
+from .pipeline import check_clock, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -139,6 +140,11 @@ class CamG:
         # symbol [packets, 2P + D] in `last_blanked` and (baseline, level) [packets, 2] in `last_sample_level`; both are
         # None otherwise.  It cannot see a click under the threshold, does not treat the chirp, and blanks a handful of
         # samples of a clean packet too: opt-in.  NotImplementedError on the piece-wise host path.
+        self.impulse_blanking = False
+        self.blanking_threshold = 4.5
+        self.blanking_guard = 8
+        self.last_blanked = None
+        self.last_sample_level = None
         # "QCLDPC-*", staged path: decoder_feedback = n > 0 lets receive() decode up to n more times.  The codewords that
         # decoded (and, under codeword_crc, whose CRC matches) are re-encoded; the residual channel measured on their symbols,
         # smoothed over +-feedback_window[0] symbols x +-feedback_window[1] bins wherever at least feedback_min_known known
@@ -154,11 +160,6 @@ class CamG:
         self.decoder_feedback = 0
         self.feedback_window = (2, 8)
         self.feedback_min_known = 4
-        self.impulse_blanking = False
-        self.blanking_threshold = 4.5
-        self.blanking_guard = 8
-        self.last_blanked = None
-        self.last_sample_level = None
         # receiver.receive_diversity (several recordings of one transmission, maximal-ratio combined): the packet starts it
         # found in each recording [B, packets] and, under llr_weighting = "noise", each recording's per-carrier SNR estimate
         # [B, packets, C] in dB (`last_snr_db` is then the SNR after combining); None otherwise
@@ -277,6 +278,10 @@ class CamG:
         Member t of group g travels as codeword t NG + g; codewords NG (G + R) .. cap - 1 and the last packet's rest are fill."""
         return self._chain().outer_layout(F)
 
+    def _xor_mask(self, shape):
+        """The whitening mask of encoding "XOR" (OFDM.py:163-166): the known bits of one data symbol, repeated to `shape`."""
+        return np.resize(np.asarray(self.known_sequence[:self.data_bits_per_symbol], dtype=np.uint8), shape)
+
     def map(self, bits):
         """transmitter.map, OFDM.py:196-197 (table lookup)."""
         pts, tb = self._tables()
@@ -290,6 +295,36 @@ def _as_samples(r):
     if r.dtype not in _NP2T:
         r = r.astype(np.float64)
     return np.ascontiguousarray(r)
+
+
+def _as_recordings(signals):
+    """receive_diversity's input -> B = 1 .. GF3_MAX_BRANCHES one-dimensional recordings, as `_as_samples` gives them."""
+    if isinstance(signals, torch.Tensor):
+        signals = signals.detach().cpu().numpy()
+    if isinstance(signals, np.ndarray) and signals.ndim != 2:
+        raise ValueError(f"receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n], not an array of shape {signals.shape}")
+    try:
+        B = len(signals)
+    except TypeError:
+        raise ValueError("receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n]")
+    if not 1 <= B <= GF3_MAX_BRANCHES:
+        raise ValueError(f"receive_diversity: 1 to {GF3_MAX_BRANCHES} recordings, not {B}")
+    rs = [_as_samples(r) for r in signals]
+    if any(r.ndim != 1 for r in rs):
+        raise ValueError("receive_diversity: every recording must be one-dimensional")
+    return rs
+
+
+def _report_rows(iters, status, crc_bad):
+    """What `decode_report` needs on the host (under codeword_crc the flags ride in the same copy)."""
+    return {"iters": iters, "status": status, **({} if crc_bad is None else {"crc_bad": crc_bad})}
+
+
+# the attributes a call sets to the value it produced, or to None: by `diversity` (receive(), receive_diversity())
+_VALUE_OR_NONE = {False: ("last_phase_track", "last_phase_measured", "last_blanked", "last_sample_level", "last_clock_ppm",
+                          "last_clock_ppm_packets", "last_denoise_report"),
+                  True: ("last_branch_starts", "last_branch_snr_db", "last_clock_ppm", "last_clock_ppm_packets",
+                         "last_denoise_report")}
 
 
 class transmitter(CamG):
@@ -307,8 +342,7 @@ class transmitter(CamG):
         if rate is not None:                                           # QC-LDPC (not in the reference): the codewords
             bits = chain.encode(bits, rate)                            # fill packets like uncoded bits (the fill below)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
-            mask = np.resize(np.asarray(self.known_sequence[:self.data_bits_per_symbol]), bits.shape)
-            bits = bits ^ mask.astype(bits.dtype)
+            bits = bits ^ self._xor_mask(bits.shape).astype(bits.dtype)
         # fill the last packet with coin flips (OFDM.py:168-173, 178-185): ONE draw from the legacy global RNG, of
         # exactly the missing length, so a seeded run consumes the generator as the reference does
         missing = -len(bits) % chain.per_packet
@@ -540,12 +574,9 @@ class receiver(transmitter):
                                                     None if bad is None else bad.cpu().numpy())
             return dec.cpu().numpy().astype(np.int64)
         if self.encoding == "XOR":
-            n = len(bits_encoded)
-            known = torch.as_tensor(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.int64))
             dev = torch.device("cuda", torch.cuda.current_device())
             b = torch.as_tensor(np.asarray(bits_encoded, dtype=np.int64)).to(dev)
-            k = known.to(dev).repeat(-(-n // len(known)))[:n]
-            return torch.bitwise_xor(b, k).cpu().numpy()
+            return torch.bitwise_xor(b, torch.from_numpy(self._xor_mask(len(b))).to(dev)).cpu().numpy()
         return bits_encoded
 
     def _decode_packed(self, eng, packed):
@@ -557,98 +588,9 @@ class receiver(transmitter):
         mask = np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.uint8) if self.encoding == "XOR" else None
         return eng.unpack_decode(packed, mask)
 
-    # ---- whole receive chain (OFDM.py:581-657) ----------------------------------------
+    # ---- whole receive chain (OFDM.py:581-657; the order of its steps: DESIGN §12, "The receive pipeline") ----------------
     def receive(self, signal, graph_output=False):
-        print("-" * 42 + "\nReceive \n" + "-" * 42)
-        print("OFDM Paramters:")
-        print(self)
-        chain = self._chain()
-        rate, fused = chain.check_receive()                     # (the refusals: before any GPU work)
-        blanking = Engine.check_blanking(self.blanking_threshold, self.blanking_guard) if self.impulse_blanking else None
-        clock = check_clock(self.clock_correction, self.clock_taps)
-        r = _as_samples(signal)
-        if chain.denoise is not None and not graph_output and (getattr(self, "host_chunk_samples", None) or len(r) > (1 << 27)):
-            raise NotImplementedError("channel_denoising: the piece-wise host path of long recordings (or host_chunk_samples) "
-                                      "has no denoising pass; receive shorter recordings")
-        if chain.loading is not None:                           # (what a loading has no path for: also before any GPU work)
-            if graph_output:
-                raise NotImplementedError("bit_loading: the plots draw one constellation; receive with graph_output = False")
-            if getattr(self, "host_chunk_samples", None) or len(r) > (1 << 27):
-                raise NotImplementedError("bit_loading: the piece-wise host path of long recordings (or host_chunk_samples) "
-                                          "decides by the context's one table; receive shorter recordings")
-        eng = self._engine(r.dtype)
-        # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
-        # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
-        # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
-        # stay on the one-shot path.
-        chunk = getattr(self, "host_chunk_samples", None)
-        if not graph_output and (chunk or len(r) > (1 << 27)):
-            if blanking:
-                raise NotImplementedError("impulse_blanking: the piece-wise host path of long recordings (or "
-                                          "host_chunk_samples) has no blanking pass; receive shorter recordings")
-            if clock:
-                raise NotImplementedError("clock_correction: the piece-wise host path of long recordings (or "
-                                          "host_chunk_samples) has no resampling pass; receive shorter recordings")
-            if rate is not None:
-                raise NotImplementedError(f"encoding {self.encoding!r}: the piece-wise host path of long recordings (or "
-                                          "host_chunk_samples) has no soft-decision decoding; receive shorter recordings")
-            return self._receive_chunked(eng, r, int(chunk or (1 << 25)))
-        # 1. sync
-        x = eng._samples(r)
-        peaks = eng.sync_stream(x)
-        starts = (peaks + 2)[:-1]                               # OFDM.py:393-395
-        self.no_packets = int(starts.numel())
-        if self.no_packets == 0:
-            raise ValueError("need at least one array to concatenate")
-        # 2. demodulate (under impulse_blanking: a copy of the samples with the clicks inside the packets' bodies blanked)
-        blanked = {}
-        if blanking:
-            x, blanked["last_blanked"], blanked["last_sample_level"], _ = eng.blank_impulses(x, starts, *blanking)
-        if clock:                                               # (the packets' bodies at the corrected rate, packed)
-            x, starts, clk = correct_clock(eng, x, starts, clock)
-            blanked.update(clk)
-        o = chain.demodulate(eng, x, starts, rate, fused, graph_output)
-        # 3. the coded chain (weighted LLRs -> layered min-sum -> outer code), or PS + decode of the hard decisions
-        need, snr = {"Hs0": o["Hs"][0], "He0": o["He"][0], "slope": o["slope"]}, {}
-        if "denoise_report" in o:                               # (under channel_denoising only)
-            blanked["last_denoise_report"] = o["denoise_report"]
-        if rate is not None:
-            feedback = None
-            if chain.decoder_feedback:
-                bits_t, need["iters"], need["status"], bad, snr, feedback = chain.decode_feedback(
-                    eng, chain.code(rate, eng.device), o, self._tables()[0])
-            else:
-                llr, snr = chain.llrs(eng, o, self._tables()[0])
-                bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
-            if bad is not None:                                 # (codeword_crc: the flags ride in the same copy)
-                need["crc_bad"] = bad
-        elif chain.loading is not None:                         # "None" under a loading: the raw decisions of every loaded carrier
-            bits_t = (chain.weigh_loaded(eng, o, "csi")[0] < 0).to(torch.int64)
-        else:
-            bits_t = self._decode_packed(eng, o["bits"])
-        # 4. everything else the host needs, in ONE small copy behind the kernels; last in it the ragged-packet flag (a
-        # packet that runs past the recording: the reference's get_symbols fails on it)
-        got = fetch({**need, **snr, **blanked, "ragged": o["status"]})
-        if got["ragged"][0] != 0 or ("clock_status" in got and got["clock_status"].any()):      # (before anything is printed: get_symbols fails first in the reference)
-            raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
-        print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
-        bits = bits_t.cpu().numpy().astype(np.int64) if bits_t.is_cuda else bits_t.numpy()
-        self._last_slope = got["slope"]
-        self.last_phase_track = self.last_phase_measured = None
-        self.last_blanked, self.last_sample_level = got.get("last_blanked"), got.get("last_sample_level")
-        self.last_clock_ppm = float(got["clock_ppm"]) if clock else None
-        self.last_clock_ppm_packets = got.get("clock_ppm_packets")
-        self.last_denoise_report = got.get("last_denoise_report")
-        for name in snr:                                        # last_snr_db, last_symbol_snr_db: under their weightings only;
-            setattr(self, name, got[name])                      # last_phase_track, last_phase_measured: under phase_tracking
-        if rate is not None:
-            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
-            if feedback is not None:                            # (under decoder_feedback only)
-                self.last_decode_report.update(feedback)
-        print("Number of received bits:            " + str(len(bits)))
-        if graph_output:
-            self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())
-        return bits, got["Hs0"], got["He0"]
+        return self._receive(signal, graph_output, diversity=False)
 
     # ---- receive diversity (not in the reference) ------------------------------------------------------------------
     def receive_diversity(self, signals, graph_output=False):
@@ -667,92 +609,123 @@ class receiver(transmitter):
         "noise2d", fused_llr, phase_tracking, decoder_feedback.  Under `channel_denoising` every recording's estimate is
         denoised on its own and `last_denoise_report` is [B, packets, 2, 5].  NotImplementedError: impulse_blanking, graph_output,
         the piece-wise host path of long recordings (or host_chunk_samples)."""
+        return self._receive(signals, graph_output, diversity=True)
+
+    def _plan(self, lengths, graph_output, diversity):
+        """What this call will do with recordings of `lengths` samples, or its refusal (pipeline.plan_receive); no GPU work."""
+        return plan_receive(self, self._chain(), lengths, graph_output, diversity)
+
+    def _receive(self, signals, graph_output, diversity):
+        """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage."""
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
-        if isinstance(signals, torch.Tensor):
-            signals = signals.detach().cpu().numpy()
-        if isinstance(signals, np.ndarray) and signals.ndim != 2:
-            raise ValueError(f"receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n], not an array of shape {signals.shape}")
-        try:
-            B = len(signals)
-        except TypeError:
-            raise ValueError("receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n]")
-        if not 1 <= B <= GF3_MAX_BRANCHES:
-            raise ValueError(f"receive_diversity: 1 to {GF3_MAX_BRANCHES} recordings, not {B}")
-        chain = self._chain()
-        rate = chain.check_diversity()                          # (the refusals: before any GPU work)
-        clock = check_clock(self.clock_correction, self.clock_taps)
-        if self.impulse_blanking:
-            raise NotImplementedError("receive_diversity: impulse_blanking is not combined; blank each recording's samples "
-                                      "with Engine.blank_impulses first")
-        if graph_output:
-            raise NotImplementedError("receive_diversity: no plots; receive() one recording for them")
-        rs = [_as_samples(r) for r in signals]
-        if any(r.ndim != 1 for r in rs):
-            raise ValueError("receive_diversity: every recording must be one-dimensional")
-        if getattr(self, "host_chunk_samples", None) or any(len(r) > (1 << 27) for r in rs):
-            raise NotImplementedError("receive_diversity: the piece-wise host path of long recordings (or host_chunk_samples) "
-                                      "combines nothing; receive shorter recordings")
+        rs = _as_recordings(signals) if diversity else [_as_samples(signals)]
+        plan = self._plan([len(r) for r in rs], graph_output, diversity)
         dtype = np.result_type(*[r.dtype for r in rs])
         eng = self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
-        # 1. sync and 2. demodulate, per branch
-        starts, outs = [], []
-        for r in rs:
-            x = eng._samples(r)
-            st = (eng.sync_stream(x) + 2)[:-1]                  # OFDM.py:393-395
-            starts.append(st)
-            outs.append((x, st))
+        # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
+        # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
+        # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
+        # stay on the one-shot path.
+        if plan.piecewise:
+            return self._receive_chunked(eng, rs[0], plan.chunk)
+        # 1. sync, every recording on its own
+        xs = [eng._samples(r) for r in rs]
+        starts = [(eng.sync_stream(x) + 2)[:-1] for x in xs]   # OFDM.py:393-395
         counts = [int(st.numel()) for st in starts]
         if len(set(counts)) != 1:
             raise ValueError(f"receive_diversity: the recordings hold different numbers of packets: {counts}")
         self.no_packets = counts[0]
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
-        clk = []
-        if clock:                                               # (every recording has its own clock: estimated and corrected on its own)
-            for b, (x, st) in enumerate(outs):
-                x, st, rows_b = correct_clock(eng, x, st, clock)
-                outs[b] = (x, st)
-                clk.append(rows_b)
-        outs = [eng.demod_frames(x, st, want=("eq", "Hs", "He", "slope", "status"), denoise=chain.check_denoise()) for x, st in outs]
-        # 3. combine, then the coded chain or the hard decision and un-whitening
-        pts = self._tables()[0]
-        need = {"Hs0": outs[0]["Hs"][0], "He0": outs[0]["He"][0], "slope": outs[0]["slope"], "starts": torch.stack(starts)}
-        if rate is not None:
-            llr, rows = chain.combine(eng, outs, pts)
-            bits_t, need["iters"], need["status"], bad = chain.decode(chain.code(rate, eng.device), llr)
-            if bad is not None:
-                need["crc_bad"] = bad
+        # 2. demodulate, every recording on its own: under impulse_blanking a copy of the samples with the clicks inside the
+        # packets' bodies blanked, under clock_correction the packets' bodies at the corrected rate, packed (every recording
+        # has its own clock)
+        need_eq = diversity or plan.rate is not None or plan.chain.loading is not None
+        outs, stages, ragged = [], [], []
+        for x, st in zip(xs, starts):
+            stage = {}
+            if plan.blanking:
+                x, stage["last_blanked"], stage["last_sample_level"], _ = eng.blank_impulses(x, st, *plan.blanking)
+            if plan.clock:
+                x, st, clock_status, clock_rows = correct_clock(eng, x, st, plan.clock)
+                stage.update(clock_rows)
+                ragged.append(clock_status)
+            outs.append(demodulate(eng, plan, x, st, need_eq))
+            if "denoise_report" in outs[-1]:                    # (under channel_denoising only)
+                stage["last_denoise_report"] = outs[-1]["denoise_report"]
+            stages.append(stage)
+        # 3. decode: the coded chain (weighted LLRs -> layered min-sum -> outer code), or the hard decisions
+        bits_t, rows, feedback = self._decode_combined(plan, eng, outs) if diversity else self._decode_one(plan, eng, outs[0])
+        # 4. everything else the host needs, in ONE small copy behind the kernels, under the names of the attributes it is
+        # for; last in it the ragged-packet flags (a packet that runs past the recording: the reference's get_symbols fails
+        # on it; an offset the resampler could not apply)
+        rows.update(Hs0=outs[0]["Hs"][0], He0=outs[0]["He"][0], slope=outs[0]["slope"])
+        if diversity:
+            rows["last_branch_starts"] = torch.stack(starts)
+            rows.update({name: torch.stack([stage[name] for stage in stages]) for name in stages[0]})
         else:
+            rows.update(stages[0])
+        ragged = [o["status"] for o in outs] + ragged
+        got = fetch({**rows, "ragged": ragged[0] if len(ragged) == 1 else torch.cat(ragged)})
+        if got["ragged"].any():                                 # (before anything is printed: get_symbols fails first in the reference)
+            raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
+        print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
+        bits = bits_t.cpu().numpy().astype(np.int64) if bits_t.is_cuda else bits_t.numpy()
+        self._publish(got, plan, diversity, feedback)
+        print("Number of received bits:            " + str(len(bits)))
+        if plan.plots:
+            o = outs[0]
+            self._plots(o["Hest"].cpu().numpy(), o["Hs"].cpu().numpy(), o["He"].cpu().numpy(), o["eq"].cpu().numpy())
+        return bits, got["Hs0"], got["He0"]
+
+    def _decode_one(self, plan, eng, o):
+        """The decode stage of receive(): the demodulator's outputs -> (bits, still on the device or behind a pinned copy, the
+        rows the host needs of it, what decoder feedback adds to the report or None)."""
+        chain = plan.chain
+        if plan.rate is None and chain.loading is not None:     # "None" under a loading: the raw decisions of every loaded carrier
+            return (chain.weigh_loaded(eng, o, "csi")[0] < 0).to(torch.int64), {}, None
+        if plan.rate is None:                                   # PS + decode of the hard decisions
+            return self._decode_packed(eng, o["bits"]), {}, None
+        pts = self._tables()[0]
+        if chain.decoder_feedback:
+            bits_t, iters, status, bad, rows, feedback = chain.decode_feedback(eng, chain.code(plan.rate, eng.device), o, pts)
+        else:
+            llr, rows = chain.llrs(eng, o, pts)
+            bits_t, iters, status, bad = chain.decode(chain.code(plan.rate, eng.device), llr)
+            feedback = None
+        return bits_t, {**rows, **_report_rows(iters, status, bad)}, feedback
+
+    def _decode_combined(self, plan, eng, outs):
+        """The decode stage of receive_diversity(): maximal-ratio combining, then the coded chain or the hard decision and
+        un-whitening -> as `_decode_one`."""
+        chain, pts = plan.chain, self._tables()[0]
+        if plan.rate is None:
             eq, rows = chain.combine(eng, outs, pts, want="eq")
             bits_t = eng.demap_hard(eq)[0].reshape(-1)
             if self.encoding == "XOR":
-                mask = torch.from_numpy(np.asarray(self.known_sequence[: self.data_bits_per_symbol], dtype=np.uint8)).to(eng.device)
-                bits_t = bits_t ^ mask.repeat(-(-bits_t.numel() // mask.numel()))[: bits_t.numel()]
-        # 4. one small copy; last in it the ragged-packet flags
-        if clk:
-            need["clock_ppm"] = torch.stack([c["clock_ppm"] for c in clk])
-            if "clock_ppm_packets" in clk[0]:
-                need["clock_ppm_packets"] = torch.stack([c["clock_ppm_packets"] for c in clk])
-        if "denoise_report" in outs[0]:                         # (under channel_denoising only)
-            need["denoise_report"] = torch.stack([o["denoise_report"] for o in outs])
-        got = fetch({**need, **rows, "ragged": torch.cat([o["status"] for o in outs] + [c["clock_status"] for c in clk])})
-        if got["ragged"].any():
-            raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
-        print("Number of received OFDM symbols:    " + str(self.no_packets * self.packet_length))
-        bits = bits_t.cpu().numpy().astype(np.int64)
+                bits_t = bits_t ^ torch.from_numpy(self._xor_mask(bits_t.numel())).to(eng.device)
+            return bits_t, rows, None
+        llr, rows = chain.combine(eng, outs, pts)
+        bits_t, iters, status, bad = chain.decode(chain.code(plan.rate, eng.device), llr)
+        return bits_t, {**rows, **_report_rows(iters, status, bad)}, None
+
+    def _publish(self, got, plan, diversity, feedback):
+        """The attributes a receive call leaves, from the fetched rows.  Each call assigns its own list and touches nothing
+        else (the table and the open point that follows from it: DESIGN §12, "The receive pipeline")."""
         self._last_slope = got["slope"]
-        self.last_branch_starts = got["starts"]
-        self.last_branch_snr_db = got.get("last_branch_snr_db")
-        self.last_clock_ppm, self.last_clock_ppm_packets = got.get("clock_ppm"), got.get("clock_ppm_packets")
-        self.last_denoise_report = got.get("denoise_report")
-        if "last_snr_db" in got:
-            self.last_snr_db = got["last_snr_db"]
-        if rate is not None:
-            self.last_decode_report = decode_report(got["iters"], got["status"], chain.outer(), got.get("crc_bad"))
-        print("Number of received bits:            " + str(len(bits)))
-        return bits, got["Hs0"], got["He0"]
+        for name in _VALUE_OR_NONE[diversity]:
+            setattr(self, name, got.get(name))
+        if plan.clock and not diversity:                        # (one recording: the value, not an array [B])
+            self.last_clock_ppm = float(self.last_clock_ppm)
+        for name in ("last_snr_db", "last_symbol_snr_db"):      # only where the weighting of this call produced them
+            if name in got:
+                setattr(self, name, got[name])
+        if plan.rate is not None:
+            self.last_decode_report = decode_report(got["iters"], got["status"], plan.chain.outer(), got.get("crc_bad"))
+            if feedback is not None:                            # (under decoder_feedback only)
+                self.last_decode_report.update(feedback)
 
     def _receive_chunked(self, eng, r, chunk):
         try:

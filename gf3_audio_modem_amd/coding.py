@@ -1,87 +1,21 @@
 """The coded chain of the "QCLDPC-*" encodings in one place: settings and refusals, message bits -> coded bits, what the
 demodulator must produce, its outputs -> LLRs, LLRs (or hard bits) -> message bits (through the per-codeword CRC where
 `codeword_crc` is set), the decode report.  The façade (OFDM.py) builds a CodedChain from its public attributes at every
-call and keeps what is the reference's: XOR, the coin-flip fill, the prints.  `fetch` is the one small device-to-host copy
-receive() ends with."""
+call and keeps what is the reference's: XOR, the coin-flip fill, the prints."""
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from .crc import CRC_BITS, CodewordCRC
+from .engine import Engine
 from .outer import OuterRS, from_transmitted, layout, packets_for, to_transmitted
+from .pipeline import check_clock, correct_clock, fetch  # noqa: F401  (importable from here as before)
 
 # channel coding beyond the reference's three encodings: the project's quasi-cyclic LDPC codes (ldpc.py), of block
 # length CamG.ldpc_n = 1536 (the default), 3072 or 6144 coded bits
 QCLDPC_ENCODINGS = {"QCLDPC-1/2": "1/2", "QCLDPC-2/3": "2/3", "QCLDPC-3/4": "3/4", "QCLDPC-5/6": "5/6"}
 QCLDPC_LIFTING = {1536: 64, 3072: 128, 6144: 256}          # ldpc_n -> lifting size Z (24 block columns)
-
-
-def fetch(tensors):
-    """{name: tensor}, all on one device -> {name: NumPy array of the tensor's shape and dtype}, through ONE
-    concatenation, ONE copy (pinned and non-blocking from a GPU) and ONE stream synchronisation.  The values travel as
-    float64: complex ones as (re, im) pairs, integers converted, which is exact for the int32 values sent here."""
-    parts = [(torch.view_as_real(t) if t.is_complex() else t).reshape(-1).to(torch.float64) for t in tensors.values()]
-    small = torch.cat(parts)
-    host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=small.is_cuda)
-    host.copy_(small, non_blocking=True)
-    if small.is_cuda:
-        torch.cuda.current_stream(small.device).synchronize()
-    out, at = {}, 0
-    for (name, t), part in zip(tensors.items(), parts):
-        a = host[at: at + part.numel()].numpy().copy()
-        at += part.numel()
-        a = a.view(np.complex128) if t.is_complex() else a
-        out[name] = a.astype(torch.empty(0, dtype=t.dtype).numpy().dtype, copy=False).reshape(tuple(t.shape))
-    return out
-
-
-CLOCK_MAX_PPM = 2000.0                                      # |eps| <= 2e-3: beyond it gf3_resample_frames copies the body
-
-
-def check_clock(clock_correction, clock_taps):
-    """What `clock_correction` / `clock_taps` refuse before any GPU work -> None (off), or ("auto" | the offset in ppm as a float,
-    half_taps).  ValueError for another string, a value that is not a finite number of at most 2000 ppm in magnitude, and a
-    tap count other than 32 or 64."""
-    if clock_correction is None:
-        return None
-    if isinstance(clock_taps, bool) or clock_taps not in (32, 64):
-        raise ValueError(f"clock_taps must be 32 or 64, not {clock_taps!r}")
-    if isinstance(clock_correction, str):
-        if clock_correction != "auto":
-            raise ValueError(f"clock_correction must be None, 'auto' or a number in ppm, not {clock_correction!r}")
-        return "auto", int(clock_taps) // 2
-    try:
-        ppm = float(clock_correction)
-        ok = not isinstance(clock_correction, bool) and np.isfinite(ppm) and abs(ppm) <= CLOCK_MAX_PPM
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError(f"clock_correction must be None, 'auto' or a finite number of at most {CLOCK_MAX_PPM:.0f} ppm in "
-                         f"magnitude, not {clock_correction!r}")
-    return ppm, int(clock_taps) // 2
-
-
-def correct_clock(eng, x, starts, clock):
-    """The clock correction of one recording, shared by receive() and receive_diversity(): clock = check_clock's answer (not
-    None).  "auto": one demodulation for the slopes, eps per packet (Engine.clock_offset), and the median of the finite
-    estimates for every packet -- a sound card has one clock, and one noisy packet must not get its own rate.  A number:
-    that many ppm, no first pass.  -> (rows, offsets: what the demodulator takes in place of (x, starts), {"clock_ppm": the value
-    applied, a 0-d tensor, "clock_ppm_packets": the estimates [F] ("auto" only), "clock_status": int32 [F], non-zero for a
-    packet that runs past the recording or an eps that could not be applied})."""
-    how, half_taps = clock
-    F = starts.numel()
-    rows = {}
-    if how == "auto":
-        est = eng.clock_offset(eng.demod_frames(x, starts, want=("slope", "status"))["slope"])
-        rows["clock_ppm_packets"] = est * 1e6
-        eps = torch.nanmedian(torch.where(torch.isfinite(est), est, torch.full_like(est, float("nan"))))
-        rows["clock_ppm"] = eps * 1e6
-    else:
-        rows["clock_ppm"] = torch.full((), how, dtype=torch.float64, device=eng.device)
-        eps = rows["clock_ppm"] * 1e-6
-    out, offsets, rows["clock_status"] = eng.resample_frames(x, starts, eps.expand(F).contiguous(), half_taps=half_taps)
-    return out, offsets, rows
 
 
 def decode_report(iters, status, outer=None, crc_bad=None):
@@ -203,7 +137,6 @@ class CodedChain:
         finite number > 0 and for fewer than two pilot symbols per side."""
         if self.denoise is None:
             return None
-        from .engine import Engine
         threshold = Engine.check_denoise(self.denoise[0])
         if self.denoise[1] < 2:
             raise ValueError(f"channel_denoising measures the noise from the pilot repeats: no_pilots >= 2, not {self.denoise[1]!r}")
@@ -217,7 +150,6 @@ class CodedChain:
             raise ValueError(f"decoder_feedback must be an integer >= 0 (the extra passes at most), not {n!r}")
         if not n:
             return 0, 0, 0, 1
-        from .engine import Engine
         try:
             hs, hb = self.feedback_window
         except (TypeError, ValueError):
@@ -248,17 +180,6 @@ class CodedChain:
         return code.encode(torch.as_tensor(msg)).cpu().numpy().reshape(-1).astype(np.int64)
 
     # ---- receive side ----------------------------------------------------------------------------------------------------
-    def demodulate(self, eng, x, starts, rate, fused, plots):
-        """receive()'s demodulator call: Hs, He, slopes, ragged flag; eq for the staged soft path, eq and Hest for the plots
-        (which therefore take the staged path); LLRs straight from the samples when fused.  Under `channel_denoising` the
-        estimate behind all of them is the denoised one, and 'denoise_report' comes back too."""
-        fused = fused and not plots
-        soft = (rate is not None and not fused) or self.loading is not None
-        want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plots else ("eq",) if soft else ())
-        if fused:
-            return eng.demod_frames_llr(x, starts, weight="csi", want=want)
-        return eng.demod_frames(x, starts, want=want, denoise=self.check_denoise())
-
     def llrs(self, eng, o, points):
         """Demodulator outputs -> (weighted max-log LLRs in coded order, {attribute name: rows for the host}: the SNR in dB
         of the noise weightings, 10 log10(Es / v') with the demapper's floor, `last_snr_db` [F, C], `last_symbol_snr_db`

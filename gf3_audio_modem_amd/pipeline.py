@@ -1,0 +1,135 @@
+"""What receive() and receive_diversity() share around the decode stage ("The receive pipeline"): the plan --
+every refusal of a receive call, in one order, before any GPU work --, the clock correction of one recording, the one
+demodulator call, and `fetch`, the one small device-to-host copy a receive call ends with."""
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from .engine import Engine
+
+PIECEWISE_ABOVE = 1 << 27                                   # samples: a longer recording is taken from host memory piece by piece
+PIECEWISE_CHUNK = 1 << 25                                   # samples per piece where `host_chunk_samples` names none
+CLOCK_MAX_PPM = 2000.0                                      # |eps| <= 2e-3: beyond it gf3_resample_frames copies the body
+_HOST = "the piece-wise host path of long recordings (or host_chunk_samples)"
+
+
+def fetch(tensors):
+    """{name: tensor}, all on one device -> {name: NumPy array of the tensor's shape and dtype}, through ONE
+    concatenation, ONE copy (pinned and non-blocking from a GPU) and ONE stream synchronisation.  The values travel as
+    float64: complex ones as (re, im) pairs, integers converted, which is exact for the int32 values sent here."""
+    parts = [(torch.view_as_real(t) if t.is_complex() else t).reshape(-1).to(torch.float64) for t in tensors.values()]
+    small = torch.cat(parts)
+    host = torch.empty(small.numel(), dtype=torch.float64, pin_memory=small.is_cuda)
+    host.copy_(small, non_blocking=True)
+    if small.is_cuda:
+        torch.cuda.current_stream(small.device).synchronize()
+    out, at = {}, 0
+    for (name, t), part in zip(tensors.items(), parts):
+        a = host[at: at + part.numel()].numpy().copy()
+        at += part.numel()
+        a = a.view(np.complex128) if t.is_complex() else a
+        out[name] = a.astype(torch.empty(0, dtype=t.dtype).numpy().dtype, copy=False).reshape(tuple(t.shape))
+    return out
+
+
+def check_clock(clock_correction, clock_taps):
+    """What `clock_correction` / `clock_taps` refuse before any GPU work -> None (off), or ("auto" | the offset in ppm as a float,
+    half_taps).  ValueError for another string, a value that is not a finite number of at most 2000 ppm in magnitude, and a
+    tap count other than 32 or 64."""
+    if clock_correction is None:
+        return None
+    if isinstance(clock_taps, bool) or clock_taps not in (32, 64):
+        raise ValueError(f"clock_taps must be 32 or 64, not {clock_taps!r}")
+    if isinstance(clock_correction, str):
+        if clock_correction != "auto":
+            raise ValueError(f"clock_correction must be None, 'auto' or a number in ppm, not {clock_correction!r}")
+        return "auto", int(clock_taps) // 2
+    try:
+        ppm = float(clock_correction)
+        ok = not isinstance(clock_correction, bool) and np.isfinite(ppm) and abs(ppm) <= CLOCK_MAX_PPM
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"clock_correction must be None, 'auto' or a finite number of at most {CLOCK_MAX_PPM:.0f} ppm in "
+                         f"magnitude, not {clock_correction!r}")
+    return ppm, int(clock_taps) // 2
+
+
+class ReceivePlan(NamedTuple):
+    """What one receive call does, decided before any GPU work; everything after `plan_receive` reads these and checks nothing again."""
+    chain: object                           # the CodedChain of this call
+    rate: object                            # rate of a "QCLDPC-*" encoding, else None
+    fused: bool                             # take the sample-to-LLR demodulator (never with the plots, which need eq)
+    blanking: object                        # (threshold, guard) of Engine.blank_impulses, or None
+    clock: object                           # check_clock's answer, or None
+    denoise: object                         # the denoiser's threshold, or None
+    plots: bool
+    piecewise: bool                         # the recording is taken from host memory piece by piece (Engine.receive_host)
+    chunk: int                              # samples per piece
+
+
+def plan_receive(rx, chain, lengths, plots, diversity):
+    """The plan of receive() (diversity False) or receive_diversity() on recordings of `lengths` samples, from the
+    receiver's attributes as they are now and its CodedChain.  Every refusal of a receive call is raised here, in this order:
+    the coded chain's own (CodedChain.check_receive / check_diversity: ValueError), the values of the blanking and the
+    clock correction (ValueError), then what has no path (NotImplementedError)."""
+    chunk = getattr(rx, "host_chunk_samples", None)
+    piecewise = not plots and bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
+    if diversity:
+        rate, fused, blanking = chain.check_diversity(), False, None
+        clock = check_clock(rx.clock_correction, rx.clock_taps)
+        no_path = ((rx.impulse_blanking, "receive_diversity: impulse_blanking is not combined; blank each recording's samples "
+                                         "with Engine.blank_impulses first"),
+                   (plots, "receive_diversity: no plots; receive() one recording for them"),
+                   (piecewise, "receive_diversity: {host} combines nothing; receive shorter recordings"))
+    else:
+        rate, fused = chain.check_receive()
+        blanking = Engine.check_blanking(rx.blanking_threshold, rx.blanking_guard) if rx.impulse_blanking else None
+        clock = check_clock(rx.clock_correction, rx.clock_taps)
+        loaded = chain.loading is not None
+        no_path = ((chain.denoise and piecewise, "channel_denoising: {host} has no denoising pass; receive shorter recordings"),
+                   (loaded and plots, "bit_loading: the plots draw one constellation; receive with graph_output = False"),
+                   (loaded and piecewise, "bit_loading: {host} decides by the context's one table; receive shorter recordings"),
+                   (blanking and piecewise, "impulse_blanking: {host} has no blanking pass; receive shorter recordings"),
+                   (clock and piecewise, "clock_correction: {host} has no resampling pass; receive shorter recordings"),
+                   (rate is not None and piecewise, "encoding {encoding!r}: {host} has no soft-decision decoding; "
+                                                    "receive shorter recordings"))
+    for on, why in no_path:
+        if on:
+            raise NotImplementedError(why.format(host=_HOST, encoding=chain.encoding))
+    denoise = None if chain.denoise is None else float(chain.denoise[0])       # (validated by the chain's checks above)
+    return ReceivePlan(chain, rate, fused and not plots, blanking, clock, denoise, bool(plots), piecewise,
+                       int(chunk or PIECEWISE_CHUNK))
+
+
+def correct_clock(eng, x, starts, clock):
+    """The clock correction of one recording: clock = check_clock's answer (not None).  "auto": one demodulation for the
+    slopes, eps per packet (Engine.clock_offset), and the median of the finite estimates for every packet -- a sound card
+    has one clock, and one noisy packet must not get its own rate.  A number: that many ppm, no first pass.
+    -> (rows, offsets: what the demodulator takes in place of (x, starts), status int32 [F]: non-zero for a packet that runs
+    past the recording or an eps that could not be applied, {"last_clock_ppm": the value applied, a 0-d tensor,
+    "last_clock_ppm_packets": the estimates [F] ("auto" only)})."""
+    how, half_taps = clock
+    F = starts.numel()
+    rows = {}
+    if how == "auto":
+        est = eng.clock_offset(eng.demod_frames(x, starts, want=("slope", "status"))["slope"])
+        rows["last_clock_ppm_packets"] = est * 1e6
+        eps = torch.nanmedian(torch.where(torch.isfinite(est), est, torch.full_like(est, float("nan"))))
+        rows["last_clock_ppm"] = eps * 1e6
+    else:
+        rows["last_clock_ppm"] = torch.full((), how, dtype=torch.float64, device=eng.device)
+        eps = rows["last_clock_ppm"] * 1e-6
+    out, offsets, status = eng.resample_frames(x, starts, eps.expand(F).contiguous(), half_taps=half_taps)
+    return out, offsets, status, rows
+
+
+def demodulate(eng, plan, x, starts, need_eq):
+    """The demodulator call of a receive call, on one recording: Hs, He, slopes, ragged flag; eq where the decode stage works
+    on the equalised symbols (need_eq), eq and Hest for the plots; LLRs straight from the samples when fused.  Under
+    `channel_denoising` the estimate behind all of them is the denoised one, and 'denoise_report' comes back too."""
+    want = ("Hs", "He", "slope", "status") + (("Hest", "eq") if plan.plots else ("eq",) if need_eq and not plan.fused else ())
+    if plan.fused:
+        return eng.demod_frames_llr(x, starts, weight="csi", want=want)
+    return eng.demod_frames(x, starts, want=want, denoise=plan.denoise)
