@@ -57,6 +57,8 @@ def _load_known_sequence(count):
 class CamG:
     """Parameter block: same constructor and attributes as OFDM.py:17-114."""
 
+    last_tx_report = None                       # set by every transmit() (see papr_reduction below)
+
     def __init__(self, mode, encoding="None", no_pilots=20, packet_length=180):
         self.encoding = encoding
         self.fs = 48000
@@ -211,7 +213,28 @@ class CamG:
         self.channel_denoising = False
         self.denoise_threshold = 9.0
         self.last_denoise_report = None
-        self._engines = {}
+        # transmit side, every encoding: papr_reduction = True lowers the peaks of the data symbols by tone reservation
+        # (Engine.tone_reserve).  In the *2 and *3 modes 647 or 1147 of the 2047 carriers lie outside the data band;
+        # the reference fills them with one random QPSK vector that no receiver reads in a data symbol.  Under the option
+        # every data symbol instead carries, on those carriers, the values that papr_iterations steps of clip (at
+        # papr_target_db above the data's rms) and project leave, each held to papr_tone_limit_db relative to a data
+        # point, the best iterate kept -- never worse than a zero filler.  On the air it is compatible with every receiver
+        # and receive option; the pilot symbols, which are fixed on all carriers, stay, so the body's peak becomes theirs.
+        # transmit() still draws random_qpsk() first (a seeded run consumes the legacy RNG as the reference does); the draw
+        # is then simply not sent on data symbols.  body_gain multiplies the x2 of pilots and data, not the chirp, with or
+        # without the option: what a lower peak buys is spent there.  After every transmit() `last_tx_report` holds
+        # chirp_peak, pilot_peak, data_peak, body_rms (as sent, gain included), papr_db of the worst data symbol and
+        # headroom_db = 20 log10(chirp_peak / body peak) -- the gain at which the body, not the chirp, would set the stream's
+        # peak; under the option also data_peak_zero_filler and best_index_mean.  ValueError for a target that is not a
+        # finite number in [3, 13] dB, a tone limit outside [-20, 20] dB, iterations that are not an integer in [0, 64], a
+        # body_gain that is not finite or <= 0, fewer than 8 reserved carriers (the *1 modes); NotImplementedError together
+        # with bit_loading (that path maps on the host).
+        self.papr_reduction = False
+        self.papr_target_db = 6.0
+        self.papr_iterations = 16
+        self.papr_tone_limit_db = 6.0
+        self.body_gain = 1.0                    # (`last_tx_report` is None on the class until a transmit() sets it: a receiver that
+        self._engines = {}                      #  never transmitted has no result of that name among its `last_*` attributes)
 
     def __repr__(self):
         return ("Number of actual Sub Carriers:      {:.0f} \nCyclic prefix length:               {:.0f} \n"
@@ -434,13 +457,51 @@ class transmitter(CamG):
         plt.title("QPSK Constellation with Gray Mapping")
         plt.show()
 
+    def _check_tx(self):
+        """The transmit-side options as they are at this call, refused before any GPU work -> (body_gain, papr), papr =
+        None or (target_db, tone_limit_db, iterations)."""
+        gain = self.body_gain
+        number = isinstance(gain, (int, float, np.integer, np.floating)) and not isinstance(gain, (bool, np.bool_))
+        if not number or not np.isfinite(float(gain)) or float(gain) <= 0.0:
+            raise ValueError(f"body_gain must be a finite number > 0, not {gain!r}")
+        if not self.papr_reduction:
+            return float(gain), None
+        papr = Engine.check_papr(self.papr_target_db, self.papr_tone_limit_db, self.papr_iterations)
+        reserved = self.K - self.data_carriers_per_symbol
+        if reserved < 8:
+            raise ValueError(f"papr_reduction needs at least 8 reserved carriers outside the data band; this mode leaves {reserved} "
+                             "(the *1 modes use every carrier for data)")
+        if self.bit_loading is not None:
+            raise NotImplementedError("papr_reduction with bit_loading: the loaded mapper runs on the host")
+        return float(gain), papr
+
+    def _tx_report(self, rows, papr_report=None, gain=1.0):
+        """`last_tx_report` from the rows as sent ([packets, chirp + (2P+D)(N+CP)], host) and, under papr_reduction, the
+        read-back of Engine.tone_reserve's report [packets, D, 4] (levels before the frame's x2 and the gain)."""
+        S, P, D, Lc = self.ofdm_symbol_size + self.cp_length, self.no_pilots, self.packet_length, self.chirp_length
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, Lc + (2 * P + D) * S)
+        body = rows[:, Lc:].reshape(rows.shape[0], 2 * P + D, S)
+        data = np.abs(body[:, P:P + D, self.cp_length:])
+        pilots = np.abs(np.concatenate([body[:, :P], body[:, P + D:]], axis=1))
+        sym_peak, sym_rms = data.max(axis=2), np.sqrt(np.mean(data ** 2, axis=2))
+        chirp_peak, pilot_peak, data_peak = float(np.abs(rows[:, :Lc]).max()), float(pilots.max()), float(sym_peak.max())
+        report = {"chirp_peak": chirp_peak, "pilot_peak": pilot_peak, "data_peak": data_peak,
+                  "body_rms": float(np.sqrt(np.mean(body ** 2))), "papr_db": float(20 * np.log10((sym_peak / sym_rms).max())),
+                  "headroom_db": float(20 * np.log10(chirp_peak / max(pilot_peak, data_peak)))}
+        if papr_report is not None:
+            papr_report = np.asarray(papr_report)
+            report["data_peak_zero_filler"] = float(2.0 * gain * papr_report[..., 0].max())
+            report["best_index_mean"] = float(papr_report[..., 2].mean())
+        return report
+
     def transmit(self, bits, graph_output=False):
+        gain, papr = self._check_tx()
         print("-" * 42 + "\nTRANSMIT\n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
         bits_encoded = np.asarray(self.encode(np.asarray(bits)), dtype=np.uint8)
         if self.bit_loading is not None:
-            return self._transmit_loaded(bits, bits_encoded, graph_output)
+            return self._transmit_loaded(bits, bits_encoded, graph_output, gain)
         eng = self._engine()
         nbp = self.packet_length * self.data_bits_per_symbol
         self.no_packets = len(bits_encoded) // nbp
@@ -450,8 +511,21 @@ class transmitter(CamG):
         print("Number of bits to transmit:         " + str(len(bits)))
         print("Number of OFDM symbols to transmit: " + str(self.no_packets * self.packet_length))
         packed = np.packbits(bits_encoded.reshape(self.no_packets, nbp), axis=1)
-        rows = eng.tx_frames(packed, filler, out_dtype=torch.float64)   # [packets, chirp + (2P+D)(N+CP)]
-        signal = np.hstack([rows.cpu().numpy().reshape(-1), self.sync_chirp()])     # final chirp (OFDM.py:259)
+        if papr is None:
+            rows = eng.tx_frames(packed, filler, out_dtype=torch.float64, body_gain=gain).cpu().numpy()   # [packets, chirp + (2P+D)(N+CP)]
+            found = None
+        else:                                                           # packets at a time: the tones stay under 256 MB
+            per_packet = 16 * self.packet_length * (self.K - self.data_carriers_per_symbol)
+            step = max(1, (256 << 20) // per_packet)
+            rows, found = [], []
+            for lo in range(0, self.no_packets, step):
+                tones, rep = eng.tone_reserve(packed[lo:lo + step], *papr)
+                rows.append(eng.tx_frames(packed[lo:lo + step], filler, out_dtype=torch.float64, tones=tones, body_gain=gain).cpu().numpy())
+                found.append(rep)
+            rows = np.concatenate(rows) if rows else np.zeros((0, eng.cfg.frame_len))
+            found = torch.cat(found).cpu().numpy() if found else np.zeros((0, self.packet_length, 4))      # the one small read-back
+        self.last_tx_report = self._tx_report(rows, found, gain) if self.no_packets else None
+        signal = np.hstack([rows.reshape(-1), self.sync_chirp()])       # final chirp (OFDM.py:259)
         print("Number of packets to transmit:      " + str(self.no_packets))
         if graph_output:
             self._plot_frame(signal)
@@ -463,9 +537,10 @@ class transmitter(CamG):
         plt.plot(time, 5 * signal, label="Signal")
         plt.title("OFDM Frame"); plt.xlabel("time"); plt.legend(); plt.savefig("OFDM Frame"); plt.show()
 
-    def _transmit_loaded(self, bits, bits_encoded, graph_output):
+    def _transmit_loaded(self, bits, bits_encoded, graph_output, gain=1.0):
         """transmit() under `bit_loading`, on the host (gf3_tx_frames maps one table): the loaded mapper, then the
-        reference's own steps -- build_OFDM_symbol (which draws the unused-carrier filler), ifft, add_cp, send_to_stream."""
+        reference's own steps -- build_OFDM_symbol (which draws the unused-carrier filler), ifft, add_cp, send_to_stream;
+        `gain` (body_gain) then scales every packet's pilot and data symbols."""
         order = self._loading()
         known = self.map(np.asarray(self.known_sequence[:self.bits_per_symbol]).reshape(self.K, self.mu))
         payload = map_loaded(bits_encoded, order, known[np.asarray(self.data_carriers) - 1])
@@ -474,6 +549,10 @@ class transmitter(CamG):
         print("Number of OFDM symbols to transmit: " + str(n_sym))
         time_data = self.add_cp(np.fft.ifft(self.build_OFDM_symbol(payload)))
         signal = self.send_to_stream(time_data, self.sync_chirp())[0]
+        rows = signal[:len(signal) - self.chirp_length].reshape(self.no_packets, -1)        # (a view: the gain lands in `signal`)
+        if gain != 1.0:
+            rows[:, self.chirp_length:] *= gain
+        self.last_tx_report = self._tx_report(rows) if self.no_packets else None
         print("Number of packets to transmit:      " + str(self.no_packets))
         if graph_output:
             self._plot_frame(signal)

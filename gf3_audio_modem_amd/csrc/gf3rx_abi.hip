@@ -161,11 +161,15 @@ extern "C" int gf3_equalise(gf3_ctx* c, const void* d_data, const void* d_start,
     return GF3_OK;
 }
 
-extern "C" int gf3_tx_frames(gf3_ctx* c, const uint8_t* d_bits_packed, const void* d_filler_c128, const int64_t* d_gaps,
-                             int64_t F, void* d_out, int64_t stride, int32_t out_dtype, void* stream) {
+// d_tones [F, D, Ku] (gf3_tone_reserve) replaces the filler on the data symbols; body_gain scales pilots and data, not the chirp
+extern "C" int gf3_tx_frames_ex(gf3_ctx* c, const uint8_t* d_bits_packed, const void* d_filler_c128, const int64_t* d_gaps,
+                                int64_t F, void* d_out, int64_t stride, int32_t out_dtype, const void* d_tones_c128,
+                                double body_gain, void* stream) {
     DeviceGuard dg(c);
+    if (c && !(body_gain > 0.0 && body_gain < INFINITY)) return fail(c, GF3_EINVAL, "gf3_tx_frames: body_gain must be a finite number > 0");
+    if (c && d_tones_c128 && c->Ku == 0) return fail(c, GF3_EINVAL, "gf3_tx_frames: tones given, but every carrier is a data carrier");
     if (c && F == 0) return GF3_OK;
-    if (!c || !d_bits_packed || !d_filler_c128 || !d_out || F < 0 || (out_dtype != GF3_F32 && out_dtype != GF3_F64))
+    if (!c || !d_bits_packed || (!d_filler_c128 && !d_tones_c128) || !d_out || F < 0 || (out_dtype != GF3_F32 && out_dtype != GF3_F64))
         return fail(c, GF3_EINVAL, "gf3_tx_frames: bad argument");
     const gf3_config& g = c->cfg;
     if (stride < (int64_t)c->Lc + (int64_t)(2 * g.P + g.D) * c->S) return fail(c, GF3_EINVAL, "gf3_tx_frames: stride shorter than a packet");
@@ -177,7 +181,12 @@ extern "C" int gf3_tx_frames(gf3_ctx* c, const uint8_t* d_bits_packed, const voi
     a.P = g.P; a.D = g.D; a.C = g.C; a.contig_lo = c->contig_lo; a.filler = (const cplx*)d_filler_c128;
     a.known_time = c->d_known_time; a.bits = d_bits_packed; a.row_bytes = c->row_bytes; a.gaps = d_gaps;
     a.out = d_out; a.stride = stride; a.out_dt = out_dtype == GF3_F32 ? DT_F32 : DT_F64;
+    a.tones = (const cplx*)d_tones_c128; a.rsv = c->d_rsv; a.Ku = c->Ku; a.gain2 = 2.0 * body_gain;
     return tx_launch(c, a, F, st);
+}
+extern "C" int gf3_tx_frames(gf3_ctx* c, const uint8_t* d_bits_packed, const void* d_filler_c128, const int64_t* d_gaps,
+                             int64_t F, void* d_out, int64_t stride, int32_t out_dtype, void* stream) {
+    return gf3_tx_frames_ex(c, d_bits_packed, d_filler_c128, d_gaps, F, d_out, stride, out_dtype, nullptr, 1.0, stream);
 }
 
 // Schmidl & Cox timing metric (receiver.schmidlcox_method, OFDM.py:376-387)

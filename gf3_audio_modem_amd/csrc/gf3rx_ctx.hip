@@ -71,6 +71,7 @@ static int build_known_time(gf3_ctx* c) {
     HIPCHK(c, hipMemset(c->d_known_time, 0, c->S * sizeof(double)));
     a.P = 0; a.D = 1; a.C = 0; a.pos = d_nopos; a.contig_lo = 0; a.filler = d_kn; a.known_time = c->d_known_time;
     a.bits = d_nobits; a.row_bytes = 0; a.gaps = nullptr; a.out = d_row; a.stride = rowlen; a.out_dt = DT_F64;
+    a.gain2 = 2.0;
     int rc = tx_launch(c, a, 1, 0);
     if (rc != GF3_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(0));
@@ -267,6 +268,11 @@ extern "C" int gf3_ctx_create(const gf3_config* cfg, gf3_ctx** out) {
     }
     CK(dev_new(c->owned, &c->d_known, known));
     CK(dev_new(c->owned, &c->d_pos, pos));
+    {
+        std::vector<int> rsv(K, -1);                                    // the carriers no data symbol uses, numbered in ascending order
+        for (int k = 0; k < K; ++k) if (pos[k] < 0) rsv[k] = c->Ku++;
+        CK(dev_new(c->owned, &c->d_rsv, rsv));
+    }
     CK(dev_new(c->owned, &c->d_clab, clab));
     {
         const std::vector<int> bins(cfg->data_bins, cfg->data_bins + cfg->C);

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(NC / 8, 2) void tx_kernel(TxArgs a) {
     }
     for (int p = 0; p < 2 * P; ++p) {                       // known symbols, x2 gain (OFDM.py:253-256)
         const int64_t s0 = body + (int64_t)(p < P ? p : D + p) * S;
-        for (int i = tid; i < S; i += T) put(s0 + i, 2.0 * a.known_time[i]);
+        for (int i = tid; i < S; i += T) put(s0 + i, a.gain2 * a.known_time[i]);
     }
     FftTw<NC> ft;
     ft.init(tid, a.t.tw);
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(NC / 8, 2) void tx_kernel(TxArgs a) {
         int ps;
         if (a.contig_lo > 0) ps = (bn >= a.contig_lo && bn < a.contig_lo + a.C) ? bn - a.contig_lo : -1;
         else ps = a.pos[bn - 1];
-        if (ps < 0) return a.filler[bn - 1];
+        if (ps < 0) return a.tones ? a.tones[(f * a.D + l) * (int64_t)a.Ku + a.rsv[bn - 1]] : a.filler[bn - 1];
         const int o = (l * a.C + ps) * a.mu;                // first bit of the label, MSB-first stream
         const int b0 = o >> 3, bl = a.row_bytes - 1;          // a label never extends past the row; clamp the look-ahead
         uint32_t w = ((uint32_t)brow[b0] << 16) | ((uint32_t)brow[min(b0 + 1, bl)] << 8) | (uint32_t)brow[min(b0 + 2, bl)];
@@ -113,8 +113,8 @@ __global__ __launch_bounds__(NC / 8, 2) void tx_kernel(TxArgs a) {
         lds_barrier();
         ft.refresh();
         cplx* yb = fft_core<NC>(v, lds, ft, launder(tid));
-        // y[2n] = Re z / NC, y[2n+1] = -Im z / NC (z = conj of the forward FFT of conj Z); gain 2
-        const double sc = 2.0 / (double)NC;
+        // y[2n] = Re z / NC, y[2n+1] = -Im z / NC (z = conj of the forward FFT of conj Z); gain 2 (x body_gain)
+        const double sc = a.gain2 / (double)NC;
         const int64_t s0 = body + (int64_t)(P + l) * S;
         for (int i = tid; i < NC; i += T) {
             const cplx z = yb[i];

@@ -25,6 +25,8 @@
 //   gf3rx_resample.hip       resample_kernel + gf3_resample_frames, gf3_resample_coefficients (sampling-clock correction of the packet
 //                            bodies; the storage rounding it shares with gf3rx_blank.hip is gf3rx_storage.h)
 //   gf3rx_denoise.hip        denoise_kernel + gf3_denoise_pilots (delay-domain denoising of the pilot sums ahead of the estimate stage)
+//   gf3rx_papr.hip           papr_kernel + gf3_tone_reserve (transmit side: per data symbol, values for the carriers outside the
+//                            data band that lower the symbol's peak; gf3_tx_frames_ex sends them in the filler's place)
 //   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
@@ -176,6 +178,8 @@ struct OlsArgs {
 // transmitter.map / build_OFDM_symbol / ifft / add_cp / send_to_stream (OFDM.py:196-259)
 //   row f = [gap_f zeros | chirp Lc | P known symbols | D data symbols | P known symbols | zeros]
 //   data symbol = 2 * irfft(X), X[bin] = point(label) on data carriers, filler on the others
+// gf3_tx_frames_ex: `tones` given, data symbol (f, l) takes tones[f, l, rsv[bin - 1]] on the others instead; gain2 = 2 * body_gain
+// is the gain of pilots and data (2.0 exactly for gf3_tx_frames: the same products as before it existed)
 // ============================================================================
 struct TxArgs {
     FftTables t;
@@ -189,6 +193,10 @@ struct TxArgs {
     const uint8_t* bits; int row_bytes;       // [F, row_bytes] packed payload (np.packbits order)
     const int64_t* gaps;          // [F] leading zeros of each row (may be null)
     void* out; int64_t stride; int out_dt;    // [F, stride] samples, f32 or f64
+    const cplx* tones;            // [F, D, Ku] or null
+    const int* rsv;               // [K] number of a carrier among the reserved ones (ascending bins) or -1 for a data carrier
+    int Ku;
+    double gain2;
 };
 
 // ============================================================================
@@ -215,6 +223,8 @@ struct gf3_ctx {
     CorrPlan frames_plan, stream_plan;
     double qpsk_q = 0.0;
     int* d_idx_of_label = nullptr;
+    int* d_rsv = nullptr;               // [K] number of a carrier among the Ku = K - C carriers outside data_bins, ascending, or -1 (gf3_tone_reserve)
+    int Ku = 0;
     double* d_chirp = nullptr;
     double* d_chirp_t = nullptr;  // the same taps in the order scr_refine_kernel's lanes consume them (RefineArgs::chirp_t)
     double* d_known_time = nullptr;     // one pilot symbol in the time domain (transmit side)

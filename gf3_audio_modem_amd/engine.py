@@ -500,11 +500,14 @@ class Engine:
         nblk = -(-plen // hop.value)
         return p32, blk[:nblk], blk[nblk: 2 * nblk], hop.value
 
-    def tx_frames(self, bits_packed, filler, stride=None, gaps=None, out_dtype=torch.float32):
+    def tx_frames(self, bits_packed, filler, stride=None, gaps=None, out_dtype=torch.float32, tones=None, body_gain=1.0):
         """Synthesise chirp-prefixed packets (transmit side of the reference, OFDM.py:196-259).
         bits_packed: uint8 [F, bytes_per_frame] (the format demod_frames writes); filler: complex [K],
         value of every non-data carrier.  Returns [F, stride] samples: row f =
-        [gaps[f] zeros | chirp | P known symbols | D data symbols | P known symbols | zeros]."""
+        [gaps[f] zeros | chirp | P known symbols | D data symbols | P known symbols | zeros].
+        tones: complex [F, D, Ku] (tone_reserve) -- the carriers outside data_bins of data symbol (f, l) then carry
+        tones[f, l] instead of the filler; pilots and chirp are untouched.  body_gain (finite, > 0) multiplies the x2 of
+        the pilot and data symbols, not the chirp.  The defaults are gf3_tx_frames as it always was."""
         bits = self._dev(bits_packed, torch.uint8)
         if bits.dim() != 2 or bits.shape[1] != self.bytes_per_frame:
             raise ValueError("bits_packed must be [F, bytes_per_frame]")
@@ -517,9 +520,51 @@ class Engine:
         if g is not None and F and int(g.max()) + self.cfg.frame_len > stride:
             raise ValueError("gap + packet does not fit the row stride")
         out = self._new((F, stride), out_dtype)
-        self._check(self.lib.gf3_tx_frames(self._h, _ptr(bits), _ptr(fill), _ptr(g), F, _ptr(out), stride,
-                                           _DT_OF[out_dtype], self._stream()))
+        if tones is None and body_gain == 1.0:
+            self._check(self.lib.gf3_tx_frames(self._h, _ptr(bits), _ptr(fill), _ptr(g), F, _ptr(out), stride,
+                                               _DT_OF[out_dtype], self._stream()))
+            return out
+        if tones is not None:
+            tones = self._dev(tones)
+            if tuple(tones.shape) != (F, self.cfg.D, self.cfg.K - self.cfg.C):
+                raise ValueError("tones must be [F, D, Ku] (Ku = K - C, the carriers outside data_bins)")
+        self._check(self.lib.gf3_tx_frames_ex(self._h, _ptr(bits), _ptr(fill), _ptr(g), F, _ptr(out), stride,
+                                              _DT_OF[out_dtype], _ptr(tones), float(body_gain), self._stream()))
         return out
+
+    @staticmethod
+    def check_papr(target_db, tone_limit_db, iterations):
+        """ValueError for a peak target that is not a finite number in [3, 13] dB, a tone limit not in [-20, 20] dB or
+        iterations that are not an integer in [0, 64] -> (target_db, tone_limit_db, iterations) as float, float, int."""
+        def number(x, lo, hi):
+            ok = isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_))
+            return ok and math.isfinite(float(x)) and lo <= float(x) <= hi
+        if not number(target_db, 3.0, 13.0):
+            raise ValueError(f"papr target must be a finite number of dB in [3, 13], not {target_db!r}")
+        if not number(tone_limit_db, -20.0, 20.0):
+            raise ValueError(f"papr tone limit must be a finite number of dB in [-20, 20], not {tone_limit_db!r}")
+        if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= 64:
+            raise ValueError(f"papr iterations must be an integer in [0, 64], not {iterations!r}")
+        return float(target_db), float(tone_limit_db), int(iterations)
+
+    def tone_reserve(self, bits_packed, target_db=6.0, tone_limit_db=6.0, iterations=16):
+        """Tone reservation (gf3_tone_reserve): for every data symbol of the packets bits_packed (uint8 [F, bytes_per_frame]),
+        values for the Ku = K - C carriers outside data_bins -- which no receiver reads in a data symbol -- that lower the
+        symbol's peak: `iterations` steps of clip at target_db above the data's rms, project the clipped part on the
+        reserved carriers, limit every tone to tone_limit_db (relative to a unit-energy point), and keep the iterate of
+        the smallest peak, zero tones included.  -> (tones complex128 [F, D, Ku] for tx_frames(tones=...), report float64
+        [F, D, 4] = (peak with zero tones, best peak, its iterate, rms of the best symbol), all before the frame's x2).
+        ValueError when there is no reserved carrier.  Fixed reduction order: two calls give identical bytes."""
+        target_db, tone_limit_db, iterations = self.check_papr(target_db, tone_limit_db, iterations)
+        bits = self._dev(bits_packed, torch.uint8)
+        if bits.dim() != 2 or bits.shape[1] != self.bytes_per_frame:
+            raise ValueError("bits_packed must be [F, bytes_per_frame]")
+        F = bits.shape[0]
+        tones = self._new((F, self.cfg.D, self.cfg.K - self.cfg.C), torch.complex128)
+        report = self._new((F, self.cfg.D, 4), torch.float64)
+        self._check(self.lib.gf3_tone_reserve(self._h, _ptr(bits), F, target_db, tone_limit_db, iterations, _ptr(tones),
+                                              _ptr(report), self._stream()))
+        return tones, report
 
     def schmidl_cox(self, x, search_length=None):
         """receiver.schmidlcox_method (OFDM.py:376-387): first arg-max of |P| + N - 1, as a Python int."""

@@ -429,6 +429,33 @@ int gf3_tx_frames(gf3_ctx *ctx, const uint8_t *d_bits_packed, const void *d_fill
                   int32_t out_dtype, void *stream);
 
 /*
+ * gf3_tx_frames with two more arguments.  gf3_tx_frames is this call with d_tones_c128 = NULL and body_gain = 1.0.
+ *   d_tones_c128  [F, D, Ku] complex128 or NULL: the reserved carriers (carriers 1..K outside data_bins, ascending; Ku = K - C)
+ *                 of data symbol (f, l) take tones[f, l] instead of the filler (which may then be NULL).  The pilot
+ *                 symbols and the chirp are what they are without it.  GF3_EINVAL when given with Ku = 0.
+ *   body_gain     finite, > 0: multiplies the x2 of the pilot and data symbols, not the chirp
+ */
+int gf3_tx_frames_ex(gf3_ctx *ctx, const uint8_t *d_bits_packed, const void *d_filler_c128,
+                     const int64_t *d_gaps, int64_t F, void *d_out, int64_t stride,
+                     int32_t out_dtype, const void *d_tones_c128, double body_gain, void *stream);
+
+/*
+ * Tone reservation: per data symbol, values for the reserved carriers that lower the symbol's peak (no receiver reads
+ * them in a data symbol).  With X the data-carrier values gf3_tx_frames would send and x(R) the real N-sample symbol
+ * of X and the tones R (DC and Nyquist zero, np.fft.ifft scaling, without the frame's x2):
+ *   sigma = sqrt(2 sum |X_k|^2) / N,  A = sigma 10^(target_db/20),  L = 10^(tone_limit_db/20)
+ *   R = 0; for i = 1..iterations: c = x(R) - clip(x(R), -A, A); stop if c == 0; R -= N / (2 Ku) fft(c) on the reserved
+ *   bins; |R_k| > L is scaled back to L; the iterate of the smallest max|x(R)| is kept (iterate 0, R = 0, included; the
+ *   first minimum wins) -- so the result is never worse than a zero filler.
+ *   d_tones_c128 [F, D, Ku] complex128;  d_report_f64 [F, D, 4] = (peak at R = 0, best peak, its iterate, rms of the best symbol)
+ * One workgroup per symbol, fixed reduction order: two calls give identical bytes.  GF3_EINVAL for Ku = 0, null
+ * pointers, parameters that are not finite and iterations outside [0, 64].
+ */
+int gf3_tone_reserve(gf3_ctx *ctx, const uint8_t *d_bits_packed, int64_t F, double target_db,
+                     double tone_limit_db, int32_t iterations, void *d_tones_c128,
+                     double *d_report_f64, void *stream);
+
+/*
  * Known-channel zero forcing, the reference's older receive flow (`Weekend Challenge.ipynb` cells 9-19:
  * H = np.fft.fft(h, N); symbols = FFT(rx_no_cp) / H; demap of the data carriers): an optional extra mode with
  * sample-exact timing supplied by the caller, not part of receive() (OFDM.py:581-657 estimates the channel from
