@@ -139,9 +139,8 @@ extern "C" int gf3_demod_frames_llr(gf3_ctx* c, const void* d_in, int64_t n_in, 
     a.in = d_in; a.n_in = n_in; a.off = d_off; a.stamps = c->stamps;
     a.Hs = (cplx*)d_Hs; a.He = (cplx*)d_He; a.slope = d_slope; a.status = d_status;
     a.bits = (uint8_t*)d_llr; a.row_bytes = (int)sizeof(float) * c->cfg.D * c->cfg.C * c->cfg.mu; a.ring = 0;
-    int hI = 0, hQ = 0;
     a.soft = 1; a.soft_weight = weight; a.sep = c->sep; a.soft_stage = demod_soft_stages(c) ? 1 : 0;
-    a.soft_kind = (c->sep.nI > 0 && sep_is_binary(c->sep, c->cfg.mu, hI, hQ) && hI <= 3) ? hI : 0;
+    a.soft_kind = grid_bits(c);
     if (d_work && demod_wants_split(c, F, mode)) return demod_split(c, a, F, d_work, (hipStream_t)stream);
     HIPCHK(c, launch_demod_soft(c, a, F, (hipStream_t)stream));
     return GF3_OK;

@@ -3,9 +3,9 @@
 //
 //   z[f,l,c]  = (sum_b w_b z_b) / W,  W = sum_b w_b,  b ascending;  0 + 0i where W = 0
 //   LLR       = maxlog(z; sigma^2 = 1) * W   (float32; +0 where W = 0)
-//   csi:    w_b[f,l,c] = csi_mag(|Hs_b|, |He_b|, l)^2 at the carrier's bin (the weight of gf3_soft_demap_csi)
+//   csi:    w_b[f,l,c] = csi_weight_mag(|Hs_b|, |He_b|, l) at the carrier's bin (gf3rx_demap.h: the weight of gf3_soft_demap_csi)
 //   noise:  vbar[f] = mean over b and c of var_b[f,c];  w_b[f,c] = 1 / max(var_b, 1e-6 vbar), 1 for the whole packet where
-//           vbar is 0 or not finite (the rule of gf3_soft_demap_nw, taken over all branches)
+//           vbar is 0 or not finite (noise_weight of gf3rx_demap.h, with packet_vbar taken over all branches)
 //   w_b = 0 where the weight's input or the weight itself is not finite or z_b is not finite in either part: that symbol
 //   of that branch is left out of both sums.
 //
@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int CB_THREADS = 256;
+constexpr int CB_THREADS = VBAR_THREADS;
 
 struct CombineArgs {
     const cplx* eq[GF3_MAX_BRANCHES];
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     // per-carrier weight factors: noise -- the weight itself; csi -- |Hs_b| and |He_b| (NaN marks a non-finite input)
     double w0[B], w1[B];
     if constexpr (NOISE) {
-        // vbar: thread t adds var_b[t], var_b[t + 256], ... for b ascending, a binary tree adds the 256 partial sums: the same
+        // vbar: thread t adds var_b[t], var_b[t + 256], ... for b ascending, packet_vbar adds the 256 partial sums: the same
         // number in every workgroup of the packet
         double s = 0.0;
 #pragma unroll
@@ -49,20 +49,10 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
             const double* v = a.var[b] + f * C;
             for (int k = t; k < C; k += CB_THREADS) s += v[k];
         }
-        red[t] = s;
-        __syncthreads();
-#pragma unroll
-        for (int h = CB_THREADS / 2; h > 0; h >>= 1) {
-            if (t < h) red[t] += red[t + h];
-            __syncthreads();
-        }
-        const double vbar = red[0] / ((double)B * (double)C);
-        const bool flat = !(vbar > 0.0) || !(vbar < INFINITY);          // 0, NaN, Inf: the packet's weights are 1
-        const double floor_v = 1e-6 * vbar;
+        const PacketNoise pn = packet_vbar(red, s, (double)B * (double)C);
 #pragma unroll
         for (int b = 0; b < B; ++b) {
-            const double x = c < C ? a.var[b][f * C + c] : 0.0;
-            const double w = !is_fin(x) ? 0.0 : flat ? 1.0 : 1.0 / fmax(x, floor_v);
+            const double w = noise_weight(c < C ? a.var[b][f * C + c] : 0.0, pn);
             w0[b] = is_fin(w) ? w : 0.0;
             w1[b] = 0.0;
         }
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
         for (int b = 0; b < B; ++b) {
             double w;
             if constexpr (NOISE) w = w0[b];
-            else { const double mag = csi_mag(w0[b], w1[b], l, a.P, a.D); w = mag * mag; }
+            else w = csi_weight_mag(w0[b], w1[b], l, a.P, a.D);
             if (!is_fin(w) || !is_fin(z[b].x) || !is_fin(z[b].y)) w = 0.0;
             sx += w == 0.0 ? 0.0 : w * z[b].x;
             sy += w == 0.0 ? 0.0 : w * z[b].y;
@@ -101,41 +91,17 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
         const cplx e = W == 0.0 ? cmk(0.0, 0.0) : cmk(sx / W, sy / W);
         if (a.eq_out) a.eq_out[i] = e;
         if (a.wsum) a.wsum[i] = W;
-        if (a.llr) {
-            if constexpr (HI > 0) {
-                constexpr int MU = 2 * HI;
-                double diff[MU];
-                maxlog_bin<HI, HI>(e, lv.lvI, lv.lvQ, diff);
-                float out[MU];
-#pragma unroll
-                for (int b = 0; b < MU; ++b) out[b] = W == 0.0 ? 0.0f : (float)(diff[b] * W);
-                store_llr<MU>(a.llr, i, out);
-            } else {
-                float* dst = a.llr + i * a.t.mu;
-                if (W == 0.0) { for (int b = 0; b < a.t.mu; ++b) dst[b] = 0.0f; }
-                else maxlog_table(e, a.t, W, dst);
-            }
-        }
+        if (a.llr) emit_llr<HI, true>(e, lv, a.t, W, [llr = a.llr, i, mu = a.t.mu](const auto& out) { store_llr_any(llr, i, mu, out); });
     }
 }
 
-template <int B, bool NOISE>
-void launch_combine_hi(int hi, dim3 grid, hipStream_t st, const CombineArgs& a) {
-    switch (hi) {
-        case 1: hipLaunchKernelGGL((combine_kernel<B, NOISE, 1>), grid, dim3(CB_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((combine_kernel<B, NOISE, 2>), grid, dim3(CB_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((combine_kernel<B, NOISE, 3>), grid, dim3(CB_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((combine_kernel<B, NOISE, 0>), grid, dim3(CB_THREADS), 0, st, a); break;
-    }
-}
-
-template <bool NOISE>
-void launch_combine(int B, int hi, dim3 grid, hipStream_t st, const CombineArgs& a) {
+template <bool NOISE, int HI>
+void launch_combine(int B, dim3 grid, hipStream_t st, const CombineArgs& a) {
     switch (B) {
-        case 1: launch_combine_hi<1, NOISE>(hi, grid, st, a); break;
-        case 2: launch_combine_hi<2, NOISE>(hi, grid, st, a); break;
-        case 3: launch_combine_hi<3, NOISE>(hi, grid, st, a); break;
-        default: launch_combine_hi<4, NOISE>(hi, grid, st, a); break;
+        case 1: hipLaunchKernelGGL((combine_kernel<1, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((combine_kernel<2, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((combine_kernel<3, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
+        default: hipLaunchKernelGGL((combine_kernel<4, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
     }
 }
 
@@ -154,7 +120,7 @@ extern "C" int gf3_combine_branches(gf3_ctx* c, int32_t B, const void* const* d_
     if (!ok)
         return fail(c, GF3_EINVAL, "gf3_combine_branches: bad argument (1 <= B <= %d branches, mode 0 or 1 with its weight inputs, "
                                    "at least one output, eq_out none of the inputs)", GF3_MAX_BRANCHES);
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_combine_branches: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_combine_branches")) return rc;
     CombineArgs a{};
     for (int b = 0; b < B; ++b) {
         a.eq[b] = (const cplx*)d_eq[b];
@@ -166,16 +132,13 @@ extern "C" int gf3_combine_branches(gf3_ctx* c, int32_t B, const void* const* d_
     a.D = c->cfg.D; a.C = c->cfg.C; a.K = c->K; a.P = c->cfg.P;
     a.ntile = (a.C + CB_THREADS - 1) / CB_THREADS;
     a.t = demap_tab(c);
-    // about 8 workgroups per compute unit when there are packets enough; a handful of long packets is cut down to
-    // single symbols (as gf3_soft_demap_nw)
-    const int64_t per = F * a.ntile;
-    int64_t nchunk = (8 * (int64_t)c->n_cu + per - 1) / per;
-    if (nchunk > a.D) nchunk = a.D;
-    if (nchunk < 1) nchunk = 1;
-    a.Dc = (int)((a.D + nchunk - 1) / nchunk);
+    a.Dc = symbols_per_group(c, F * a.ntile, a.D);
     const dim3 grid((unsigned)(a.ntile * ((a.D + a.Dc - 1) / a.Dc)), (unsigned)F);
-    if (noise) launch_combine<true>(B, grid_bits(c), grid, (hipStream_t)stream, a);
-    else launch_combine<false>(B, grid_bits(c), grid, (hipStream_t)stream, a);
+    with_grid_bits(c, [&](auto hi) {
+        constexpr int HI = decltype(hi)::value;
+        if (noise) launch_combine<true, HI>(B, grid, (hipStream_t)stream, a);
+        else launch_combine<false, HI>(B, grid, (hipStream_t)stream, a);
+    });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }

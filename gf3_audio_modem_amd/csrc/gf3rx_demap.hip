@@ -1,5 +1,5 @@
-// libgf3rx -- the stand-alone demappers (gf3_demap_hard, gf3_soft_demap, gf3_soft_demap_csi) and the known-channel zero
-// forcing, which ends in the hard demapper.  The per-symbol arithmetic is gf3rx_demap.h's.
+// libgf3rx -- the stand-alone demappers (gf3_demap_hard, gf3_soft_demap, gf3_soft_demap_csi with its weighting kernel) and
+// the known-channel zero forcing, which ends in the hard demapper.  The per-symbol arithmetic is gf3rx_demap.h's.
 #include "gf3rx_demod.h"
 #include "gf3rx_demap.h"
 
@@ -79,32 +79,55 @@ __global__ __launch_bounds__(256) void soft_demap_bin_kernel(DemapArgs a) {
     for (int k = 0; k < NI; ++k) lvI[k] = a.t.sep.lvI[k];
 #pragma unroll
     for (int k = 0; k < NQ; ++k) lvQ[k] = a.t.sep.lvQ[k];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
-        double diff[MU];
-        maxlog_bin<HI, HQ>(a.sym[i], lvI, lvQ, diff);
-        float out[MU];
-#pragma unroll
-        for (int b = 0; b < MU; ++b) out[b] = (float)(diff[b] * a.inv_nv);
-        store_llr<MU>(a.llr, i, out);
-    }
+    // (inv_nv is a scale, never an erasure mark: ERASE = false, see emit_grid_llr)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x)
+        emit_grid_llr<HI, HQ, false>(a.sym[i], lvI, lvQ, a.inv_nv, [llr = a.llr, i](const float (&out)[MU]) { store_llr<MU>(llr, i, out); });
 }
 
 typedef void (*DemapKernel)(DemapArgs);
 static int run_demap(gf3_ctx* c, const void* d_sym, int64_t n, uint8_t* bits, uint8_t* idx, float* llr, double nv, void* stream) {
-    // QPSK, 16-QAM, 64-QAM (hI = 1, 2, 3): straight-line minima; any other separable table by its mu = 1 .. 8
-    static const DemapKernel bin_k[3] = {soft_demap_bin_kernel<1, 1>, soft_demap_bin_kernel<2, 2>, soft_demap_bin_kernel<3, 3>};
+    // any separable table that is no binary-indexed grid, by its mu = 1 .. 8
     static const DemapKernel sep_k[8] = {soft_demap_sep_kernel<1>, soft_demap_sep_kernel<2>, soft_demap_sep_kernel<3>, soft_demap_sep_kernel<4>,
                                          soft_demap_sep_kernel<5>, soft_demap_sep_kernel<6>, soft_demap_sep_kernel<7>, soft_demap_sep_kernel<8>};
     DemapArgs a{(const cplx*)d_sym, n, demap_tab(c), bits, llr, nv > 0 ? 1.0 / nv : 0.0, idx};
     int64_t grid = (n + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
-    int hI = 0, hQ = 0;
-    DemapKernel k = soft_demap_kernel;
+    DemapKernel k = soft_demap_kernel;                               // literal scan
     if (bits) k = demap_hard_kernel;
-    else if (c->sep.nI > 0 && sep_is_binary(c->sep, c->cfg.mu, hI, hQ) && hI <= 3) k = bin_k[hI - 1];
-    else if (c->sep.nI > 0) k = sep_k[c->cfg.mu - 1];
+    else if (c->sep.nI > 0)                                          // QPSK, 16-QAM, 64-QAM (HI = 1, 2, 3): straight-line minima
+        k = with_grid_bits(c, [&](auto hi) -> DemapKernel {
+            constexpr int HI = decltype(hi)::value;
+            if constexpr (HI > 0) return soft_demap_bin_kernel<HI, HI>;
+            else return sep_k[c->cfg.mu - 1];
+        });
     HIPCHK(c, launch(k, grid, 256, 0, (hipStream_t)stream, a));
     return GF3_OK;
+}
+
+// CSI weighting of max-log LLRs (computed with sigma^2 = 1 by the soft demapper): LLR *= |H^|^2 with the reference's
+// magnitude model (csi_weight, gf3rx_demap.h), from Hs / He [F, K] directly.  A thread owns carrier k of symbol (f, l);
+// carriers that carry no data (pos[k] < 0) have nothing to do.
+struct CsiArgs { float* llr; const cplx* Hs; const cplx* He; const int* pos; int64_t F; int K, D, P, C, mu; };
+__global__ __launch_bounds__(256) void csi_weight_kernel(CsiArgs a) {
+    const int64_t total = a.F * a.D * a.K, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+        const int kk = (int)(t % a.K);
+        const int pos = a.pos[kk];
+        if (pos < 0) continue;
+        const int64_t fl = t / a.K, f = fl / a.D;
+        const int l = (int)(fl - f * a.D);
+        const double wgt = csi_weight(a.Hs[f * a.K + kk], a.He[f * a.K + kk], l, a.P, a.D);
+        float* p = a.llr + (fl * a.C + pos) * a.mu;
+        for (int b = 0; b < a.mu; ++b) p[b] = (float)((double)p[b] * wgt);
+    }
+}
+static hipError_t launch_csi_weight(const gf3_ctx* c, float* d_llr, const void* d_Hs, const void* d_He, int64_t F, hipStream_t st) {
+    CsiArgs a{d_llr, (const cplx*)d_Hs, (const cplx*)d_He, c->d_pos, F, c->K, c->cfg.D, c->cfg.P, c->cfg.C, c->cfg.mu};
+    int64_t grid = (F * c->cfg.D * c->K + 255) / 256;
+    if (grid > 16 * (int64_t)c->n_cu) grid = 16 * (int64_t)c->n_cu;
+    if (grid < 1) return hipSuccess;
+    hipLaunchKernelGGL(csi_weight_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 extern "C" int gf3_demap_hard(gf3_ctx* c, const void* d_sym, int64_t n, uint8_t* d_bits, uint8_t* d_idx, void* stream) {

@@ -103,32 +103,26 @@ GF3_DEV double rcp_n1(double x) {
 // MODE_SOFT : no bits: weighted max-log LLRs of every data carrier (gf3_demod_frames_llr), float32 in the reference's
 //             bit order, from the un-normalised symbol and the magnitude model the table modes hold anyway
 enum { MODE_FULL = 0, MODE_SCAN = 1, MODE_QPSK = 2, MODE_SOFT = 3 };
-// MODE_SOFT, one data carrier: e = ep / mag as MODE_FULL forms it, the max-log differences of gf3rx_demap.h, times w in
-// fp64, rounded to float32 once.  kind (wave-uniform) = h of a binary-indexed 2^h x 2^h grid (sep_is_binary), 0: any table.
+// MODE_SOFT, one data carrier: e = ep / mag as MODE_FULL forms it, through the weighted emitter of gf3rx_demap.h (the
+// max-log differences times w in fp64, rounded to float32 once; w = |H^|^2 or 1 is a scale, not an erasure mark: ERASE =
+// false, see emit_grid_llr, and maxlog_table has no other form).  The arm is chosen at run time, wave-uniformly:
+// soft_kind = grid_bits of the context, the HI of a binary-indexed 2^HI x 2^HI grid, 0: any table.  dst: the symbol's row
+// in LDS or in the output.
+template <int HI>
+GF3_DEV void soft_llr_grid(cplx e, const SepTab& sep, double w, float* dst) {
+    double lvI[1 << HI], lvQ[1 << HI];
+#pragma unroll
+    for (int k = 0; k < (1 << HI); ++k) { lvI[k] = sep.lvI[k]; lvQ[k] = sep.lvQ[k]; }
+    emit_grid_llr<HI, HI, false>(e, lvI, lvQ, w, [dst](const float (&out)[2 * HI]) {
+#pragma unroll
+        for (int b = 0; b < 2 * HI; ++b) dst[b] = out[b];
+    });
+}
 GF3_DEV void soft_llr(cplx e, const DemodArgs& a, double w, float* dst) {
-    if (a.soft_kind == 1) {
-        const double lvI[2] = {a.sep.lvI[0], a.sep.lvI[1]}, lvQ[2] = {a.sep.lvQ[0], a.sep.lvQ[1]};
-        double diff[2];
-        maxlog_bin<1, 1>(e, lvI, lvQ, diff);
-#pragma unroll
-        for (int b = 0; b < 2; ++b) dst[b] = (float)(diff[b] * w);
-    } else if (a.soft_kind == 2) {
-        double lvI[4], lvQ[4], diff[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { lvI[k] = a.sep.lvI[k]; lvQ[k] = a.sep.lvQ[k]; }
-        maxlog_bin<2, 2>(e, lvI, lvQ, diff);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) dst[b] = (float)(diff[b] * w);
-    } else if (a.soft_kind == 3) {
-        double lvI[8], lvQ[8], diff[6];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { lvI[k] = a.sep.lvI[k]; lvQ[k] = a.sep.lvQ[k]; }
-        maxlog_bin<3, 3>(e, lvI, lvQ, diff);
-#pragma unroll
-        for (int b = 0; b < 6; ++b) dst[b] = (float)(diff[b] * w);
-    } else {
-        maxlog_table(e, DemapTab{a.M, a.mu, a.cre, a.cim, a.clab, a.sep}, w, dst);
-    }
+    if (a.soft_kind == 1) soft_llr_grid<1>(e, a.sep, w, dst);
+    else if (a.soft_kind == 2) soft_llr_grid<2>(e, a.sep, w, dst);
+    else if (a.soft_kind == 3) soft_llr_grid<3>(e, a.sep, w, dst);
+    else maxlog_table(e, DemapTab{a.M, a.mu, a.cre, a.cim, a.clab, a.sep}, w, dst);
 }
 // sizes whose lean layout holds two FFT buffers: the transform's own ping-pong sizes, and 4096 (DemodOcc::PP_SIZE below)
 constexpr bool demod_pp_size(int NC) { return NC == 1024 || NC == 2048 || NC == 4096; }

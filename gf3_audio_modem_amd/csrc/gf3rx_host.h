@@ -10,12 +10,12 @@
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
 //   gf3rx_stamp.cpp          the build stamp (source hash), recompiled on every change
 //   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide (the peak rule they share with corr_kernel: gf3rx_peak.h)
-//   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel, csi_weight_kernel + gf3_ldpc_*
+//   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel + gf3_ldpc_*
 //   gf3rx_outer.hip          rs_encode_kernel, rs_recover_kernel + gf3_outer_encode, gf3_outer_recover (field arithmetic: gf3rx_outer.h)
 //   gf3rx_crc.hip            crc_kernel + gf3_crc_attach, gf3_crc_check (per-codeword CRC-32)
 //   gf3rx_noise.hip          noise_estimate_kernel, soft_demap_nw_kernel + gf3_noise_estimate, gf3_soft_demap_nw; their
 //                            carrier x symbol forms and interleave_kernel + gf3_noise_estimate_cs, gf3_soft_demap_nw_cs, gf3_interleave
-//                            (the per-symbol demapper arithmetic they share with gf3rx_demap.hip is gf3rx_demap.h)
+//                            (the soft-output arithmetic every unit from here to gf3rx_demap.hip shares is gf3rx_demap.h)
 //   gf3rx_loading.hip        noise_estimate_loaded_kernel, soft_demap_loaded_kernel + gf3_loading_*, gf3_noise_estimate_loaded,
 //                            gf3_soft_demap_loaded (adaptive bit loading: a QAM order per carrier, the noise pair for such a packet)
 //   gf3rx_combine.hip        combine_kernel + gf3_combine_branches (receive diversity: maximal-ratio combining of B branches' symbols)
@@ -27,7 +27,7 @@
 //   gf3rx_denoise.hip        denoise_kernel + gf3_denoise_pilots (delay-domain denoising of the pilot sums ahead of the estimate stage)
 //   gf3rx_papr.hip           papr_kernel + gf3_tone_reserve (transmit side: per data symbol, values for the carriers outside the
 //                            data band that lower the symbol's peak; gf3_tx_frames_ex sends them in the filler's place)
-//   gf3rx_demap.hip          the stand-alone demapper kernels + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
+//   gf3rx_demap.hip          the stand-alone demapper kernels, csi_weight_kernel + gf3_demap_hard, gf3_soft_demap(_csi); zero forcing (gf3_equalise_known_h)
 //   gf3rx_sync_frames.hip    gf3_sync_frames*: the dispatch between corr_kernel and the fp32 screen, and its workspaces
 //   gf3rx_ctx.hip            error text, gf3_ctx_create / gf3_ctx_destroy (table classification, plans; host arithmetic: gf3rx_plans.h), getters
 //   gf3rx_abi.hip            the rest: gf3_rfft_batch, gf3_demod_frames(_ex, _dn), gf3_demod_frames_llr, gf3_equalise, gf3_tx_frames, Schmidl-Cox, gf3_unpack_bits
@@ -304,6 +304,20 @@ static hipError_t launch(Kern k, int64_t grid, int threads, size_t lds, hipStrea
     return hipGetLastError();
 }
 
+// Kernels whose grid carries the packet in y: the refusal of a call with more packets than a grid's y extent.
+inline int too_many_packets(const gf3_ctx* c, int64_t F, const char* who) {
+    return F > 65535 ? fail(c, GF3_EINVAL, "%s: at most 65535 packets per call", who) : GF3_OK;
+}
+// Data symbols per workgroup of a kernel that streams a packet's D symbols, `per` workgroups per chunk of symbols (the
+// packets, times the carrier tiles where a packet has several): about 8 workgroups per compute unit when there are
+// packets enough; a handful of long packets is cut down to single symbols.
+inline int symbols_per_group(const gf3_ctx* c, int64_t per, int D) {
+    int64_t nchunk = (8 * (int64_t)c->n_cu + per - 1) / per;
+    if (nchunk > D) nchunk = D;
+    if (nchunk < 1) nchunk = 1;
+    return (int)((D + nchunk - 1) / nchunk);
+}
+
 #ifdef GF3_DEV_BUILD   /* developer iteration: only N=4096 with f32/f64 samples */
 #define DISPATCH_DT(DTv, CALL)                                            \
     switch (DTv) {                                                        \
@@ -404,5 +418,3 @@ hipError_t run_spec_ols(const CorrPlan& pl, OlsArgs a, int64_t nwin, int64_t nbl
 // gf3rx_screen.hip
 hipError_t launch_screen(const gf3_ctx* c, ScreenArgs a, bool general, hipStream_t st);
 hipError_t launch_refine(const gf3_ctx* c, const RefineArgs& a, int64_t cap_cells, hipStream_t st);
-// gf3rx_ldpc.hip: LLR *= |H^|^2 (gf3_soft_demap_csi, after the soft demapper)
-hipError_t launch_csi_weight(const gf3_ctx* c, float* d_llr, const void* d_Hs, const void* d_He, int64_t F, hipStream_t st);

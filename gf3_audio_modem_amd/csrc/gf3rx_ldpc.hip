@@ -1,12 +1,11 @@
 // libgf3rx -- quasi-cyclic LDPC coding (lifting Z = 64, 128 or 256): the code object, the dual-diagonal encoder, the
-// layered normalised min-sum decoder and the channel-state weighting of gf3_soft_demap_csi.  See DESIGN.md §12.
+// layered normalised min-sum decoder.  See DESIGN.md §12.
 //
 // Bit j*Z + t of a codeword is bit t of block column j; a non-zero block (i, j) with shift s is the circulant whose row z
 // has its one in column (z + s) mod Z.  Thread z owns check row z of every block row (decoder) or bit z of every block
 // (encoder).  Z = 64: one wave is one codeword and the waves of a workgroup are independent (no barrier anywhere).
 // Z = 128, 256 (the *_wide kernels): the Z/64 waves of one workgroup share one codeword and meet at workgroup barriers.
 #include "gf3rx_host.h"
-#include "gf3rx_demap.h"
 
 // The decoder's parity contract is bit-exactness with a float32 NumPy restatement of the same schedule
 // (tests/ldpc_ref.py): no multiply-add may be contracted into an FMA in this unit.
@@ -269,37 +268,7 @@ __global__ __launch_bounds__(LZ_MAX) void ldpc_encode_wide_kernel(LdpcArgs a) {
     }
 }
 
-// CSI weighting of max-log LLRs (computed with sigma^2 = 1 by the soft demapper): LLR *= |H^|^2 with the reference's
-// magnitude model |Hs| + (|He| - |Hs|) (l + P/2) / (D + P) (OFDM.py:469), from Hs / He [F, K] directly.  A thread owns
-// carrier k of symbol (f, l); carriers that carry no data (pos[k] < 0) have nothing to do.
-struct CsiArgs { float* llr; const cplx* Hs; const cplx* He; const int* pos; int64_t F; int K, D, P, C, mu; };
-__global__ __launch_bounds__(256) void csi_weight_kernel(CsiArgs a) {
-    const int64_t total = a.F * a.D * a.K, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-        const int kk = (int)(t % a.K);
-        const int pos = a.pos[kk];
-        if (pos < 0) continue;
-        const int64_t fl = t / a.K, f = fl / a.D;
-        const int l = (int)(fl - f * a.D);
-        const cplx hs = a.Hs[f * a.K + kk], he = a.He[f * a.K + kk];
-        const double s = hypot(hs.x, hs.y), e = hypot(he.x, he.y);
-        const double mag = csi_mag(s, e, l, a.P, a.D);
-        const double wgt = mag * mag;
-        float* p = a.llr + (fl * a.C + pos) * a.mu;
-        for (int b = 0; b < a.mu; ++b) p[b] = (float)((double)p[b] * wgt);
-    }
-}
-
 }  // namespace
-
-hipError_t launch_csi_weight(const gf3_ctx* c, float* d_llr, const void* d_Hs, const void* d_He, int64_t F, hipStream_t st) {
-    CsiArgs a{d_llr, (const cplx*)d_Hs, (const cplx*)d_He, c->d_pos, F, c->K, c->cfg.D, c->cfg.P, c->cfg.C, c->cfg.mu};
-    int64_t grid = (F * c->cfg.D * c->K + 255) / 256;
-    if (grid > 16 * (int64_t)c->n_cu) grid = 16 * (int64_t)c->n_cu;
-    if (grid < 1) return hipSuccess;
-    hipLaunchKernelGGL(csi_weight_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
 
 // ============================================================================
 // the code object and its entry points (include/gf3rx.h)

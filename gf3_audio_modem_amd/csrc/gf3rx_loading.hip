@@ -9,10 +9,11 @@
 //   v[f, c]            = (1/D) sum_l |eq[f, l, c] - s|^2, s the point of carrier c's table that the hard decision picks;
 //                        the pilot symbol on a carrier of order 0
 //   LLR[f, l, off[c]+b] = (float)(maxlog(eq[f, l, c]; table of order[c])[b] * w), +0 where w = 0
-//   w                  = gf3_soft_demap_nw's (var) | gf3_soft_demap_csi's (Hs, He) | 1
+//   w                  = noise_weight (var) | csi_weight (Hs, He) | 1          (gf3rx_demap.h, as every other weight rule)
 //
-// The kernels are noise_estimate_kernel and soft_demap_nw_kernel (gf3rx_noise.hip) with the table chosen per carrier:
-// the same work split, the same order of every sum, so that an all-m loading gives the bits the uniform kernels give.
+// The kernels have the shape of noise_estimate_kernel and soft_demap_nw_kernel (gf3rx_noise.hip) with the table chosen
+// per carrier: the same work split, the same order of every sum, and the same pieces of gf3rx_demap.h (grid_min_d2,
+// packet_vbar, noise_weight, csi_weight_mag, emit_grid_llr), so that an all-m loading gives the bits the uniform kernels give.
 #include "gf3rx_demap.h"
 
 // The three families' axis levels, by value in the kernel arguments.
@@ -30,7 +31,7 @@ struct gf3_loading {
 namespace {
 
 constexpr int LE_WAVES = 8;             // as NE_WAVES of noise_estimate_kernel
-constexpr int LD_THREADS = 256;         // as NW_THREADS of soft_demap_nw_kernel
+constexpr int LD_THREADS = VBAR_THREADS; // as NW_THREADS of soft_demap_nw_kernel
 enum { W_UNIT = 0, W_VAR = 1, W_CSI = 2 };
 
 struct LoadArgs {
@@ -44,10 +45,7 @@ struct LoadArgs {
 template <int H>
 GF3_DEV double grid_residual(const cplx* p, int w, int D, int C, const double (&lv)[1 << H]) {
     double acc = 0.0;
-    for (int l = w; l < D; l += LE_WAVES) {
-        const cplx e = p[(int64_t)l * C];
-        acc += axis_min_d2<(1 << H)>(e.x, lv) + axis_min_d2<(1 << H)>(e.y, lv);
-    }
+    for (int l = w; l < D; l += LE_WAVES) acc += grid_min_d2<(1 << H)>(p[(int64_t)l * C], lv, lv);
     return acc;
 }
 
@@ -86,22 +84,19 @@ __global__ __launch_bounds__(64 * LE_WAVES) void noise_estimate_loaded_kernel(Lo
     }
 }
 
-// one carrier-symbol of order 2 H: straight-line minima, the product with the weight in fp64; off is even, so a
-// carrier's LLRs start on an 8-byte boundary: 8-byte stores, and 16-byte stores declared at that alignment
+// one carrier-symbol of order 2 H through the weighted emitter (w = 0 erases, as in soft_demap_nw_kernel); off is even,
+// so a carrier's LLRs start on an 8-byte boundary: 8-byte stores, and 16-byte stores declared at that alignment
 typedef float llr_quad __attribute__((ext_vector_type(4), aligned(8)));
 template <int H>
 GF3_DEV void demap_store(cplx e, const double (&lv)[1 << H], double w, float* dst) {
-    double diff[2 * H];
-    maxlog_bin<H, H>(e, lv, lv, diff);
-    float out[2 * H];
-#pragma unroll
-    for (int b = 0; b < 2 * H; ++b) out[b] = w == 0.0 ? 0.0f : (float)(diff[b] * w);
-    if constexpr (H >= 2) *(llr_quad*)dst = llr_quad{out[0], out[1], out[2], out[3]};
-    if constexpr (H != 2) *(float2*)(dst + 2 * H - 2) = make_float2(out[2 * H - 2], out[2 * H - 1]);
+    emit_grid_llr<H, H, true>(e, lv, lv, w, [dst](const float (&out)[2 * H]) {
+        if constexpr (H >= 2) *(llr_quad*)dst = llr_quad{out[0], out[1], out[2], out[3]};
+        if constexpr (H != 2) *(float2*)(dst + 2 * H - 2) = make_float2(out[2 * H - 2], out[2 * H - 1]);
+    });
 }
 
 // soft_demap_loaded: soft_demap_nw_kernel's shape -- a workgroup owns Dc consecutive symbols of one packet, prepares the
-// per-carrier state in LDS once (W_VAR: the weight, from the same 256-partial tree over all C variances; W_CSI: |Hs| and
+// per-carrier state in LDS once (W_VAR: the weight, from packet_vbar over all C variances; W_CSI: |Hs| and
 // |He| at the carrier's bin; always off[c] and order[c] in one int) and streams its symbols: thread = carrier, one
 // 16-byte load per carrier and symbol, a switch on the carrier's order.  Real loadings are long runs of one order, so a
 // wave takes one case except where a run ends.
@@ -118,20 +113,8 @@ __global__ __launch_bounds__(LD_THREADS) void soft_demap_loaded_kernel(LoadArgs 
         const double* v = a.var_in + f * C;
         double s = 0.0;
         for (int c = t; c < C; c += LD_THREADS) s += v[c];
-        red[t] = s;
-        __syncthreads();
-#pragma unroll
-        for (int h = LD_THREADS / 2; h > 0; h >>= 1) {
-            if (t < h) red[t] += red[t + h];
-            __syncthreads();
-        }
-        const double vbar = red[0] / (double)C;
-        const bool flat = !(vbar > 0.0) || !(vbar < INFINITY);          // 0, NaN, Inf: the packet's weights are 1
-        const double floor_v = 1e-6 * vbar;
-        for (int c = t; c < C; c += LD_THREADS) {
-            const double x = v[c];
-            wa[c] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : 1.0 / fmax(x, floor_v);
-        }
+        const PacketNoise pn = packet_vbar(red, s, (double)C);
+        for (int c = t; c < C; c += LD_THREADS) wa[c] = noise_weight(v[c], pn);
     }
     if constexpr (WM == W_CSI) {
         for (int c = t; c < C; c += LD_THREADS) {
@@ -153,7 +136,7 @@ __global__ __launch_bounds__(LD_THREADS) void soft_demap_loaded_kernel(LoadArgs 
             const int st = oo[c];
             double w = 1.0;
             if constexpr (WM == W_VAR) w = wa[c];
-            if constexpr (WM == W_CSI) { const double mag = csi_mag(wa[c], wb[c], l, a.P, a.D); w = mag * mag; }
+            if constexpr (WM == W_CSI) w = csi_weight_mag(wa[c], wb[c], l, a.P, a.D);
             float* dst = out + (st >> 3);
             switch (st & 7) {
                 case 2: demap_store<1>(e, a.lv.lv1, w, dst); break;
@@ -243,7 +226,7 @@ extern "C" int gf3_noise_estimate_loaded(gf3_ctx* c, const gf3_loading* q, const
     if (c && q && F == 0) return GF3_OK;
     if (!c || !q || !d_eq || !d_var || F < 0) return fail(c, GF3_EINVAL, "gf3_noise_estimate_loaded: bad argument");
     if (q->ctx != c) return fail(c, GF3_EINVAL, "gf3_noise_estimate_loaded: the loading was made for another context");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_noise_estimate_loaded: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_noise_estimate_loaded")) return rc;
     LoadArgs a = load_args(c, q);
     a.eq = (const cplx*)d_eq; a.var = d_var;
     const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)F), block(64 * LE_WAVES);
@@ -261,13 +244,10 @@ extern "C" int gf3_soft_demap_loaded(gf3_ctx* c, const gf3_loading* q, const voi
     if ((d_Hs != nullptr) != (d_He != nullptr)) return fail(c, GF3_EINVAL, "gf3_soft_demap_loaded: d_Hs and d_He go together");
     if (d_var && d_Hs) return fail(c, GF3_EINVAL, "gf3_soft_demap_loaded: give d_var or d_Hs / d_He, not both");
     if (((uintptr_t)d_llr & 7) != 0) return fail(c, GF3_EINVAL, "gf3_soft_demap_loaded: d_llr must be 8-byte aligned");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_soft_demap_loaded: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_soft_demap_loaded")) return rc;
     LoadArgs a = load_args(c, q);
     a.eq = (const cplx*)d_eq; a.var_in = d_var; a.Hs = (const cplx*)d_Hs; a.He = (const cplx*)d_He; a.llr = d_llr;
-    int64_t nchunk = (8 * (int64_t)c->n_cu + F - 1) / F;            // as gf3_soft_demap_nw
-    if (nchunk > a.D) nchunk = a.D;
-    if (nchunk < 1) nchunk = 1;
-    a.Dc = (int)((a.D + nchunk - 1) / nchunk);
+    a.Dc = symbols_per_group(c, F, a.D);
     const dim3 grid((unsigned)((a.D + a.Dc - 1) / a.Dc), (unsigned)F), block(LD_THREADS);
     const size_t lds = (size_t)(LD_THREADS + (d_Hs ? 2 : 1) * (size_t)a.C) * sizeof(double) + (size_t)a.C * sizeof(int);
     hipStream_t st = (hipStream_t)stream;

@@ -6,7 +6,8 @@
 //   vbar[f]   = mean_c v[f, c]
 //   w[f, c]   = 0 where v is not finite; 1 for the whole packet where vbar is 0 or not finite; else 1 / max(v, 1e-6 vbar)
 //   LLR       = maxlog(eq; sigma^2 = 1) * w   (float32; +0 where w = 0: an erasure, whatever the symbol held)
-//
+// The decided point's distance (nearest_d2), the tree behind vbar (packet_vbar), the weight rule (noise_weight) and the
+// weighted emitter (emit_llr) are gf3rx_demap.h's: these kernels hold the work split and the order of the sums.
 //
 // carrier x symbol form (clicks, dropouts: a few whole symbols are garbage):
 //   vs[f, l]  = (1/C) sum_c |eq[f, l, c] - s|^2
@@ -21,7 +22,7 @@
 namespace {
 
 constexpr int NE_WAVES = 8;             // waves of a noise_estimate workgroup: the D symbols are dealt out to them
-constexpr int NW_THREADS = 256;
+constexpr int NW_THREADS = VBAR_THREADS;
 
 struct NoiseArgs {
     const cplx* eq; double* var; const double* var_in; float* llr;
@@ -42,11 +43,7 @@ __global__ __launch_bounds__(64 * NE_WAVES) void noise_estimate_kernel(NoiseArgs
     double acc = 0.0;
     if (c < a.C) {
         const cplx* p = a.eq + (f * a.D) * (int64_t)a.C + c;
-        for (int l = w; l < a.D; l += NE_WAVES) {
-            const cplx e = p[(int64_t)l * a.C];
-            if constexpr (HI > 0) acc += axis_min_d2<(1 << HI)>(e.x, lv.lvI) + axis_min_d2<(1 << HI)>(e.y, lv.lvQ);
-            else acc += table_min_d2(e, a.t.cre, a.t.cim, a.t.M);
-        }
+        for (int l = w; l < a.D; l += NE_WAVES) acc += nearest_d2<HI>(p[(int64_t)l * a.C], lv, a.t);
     }
     part[w][lane] = acc;
     __syncthreads();
@@ -59,9 +56,9 @@ __global__ __launch_bounds__(64 * NE_WAVES) void noise_estimate_kernel(NoiseArgs
 }
 
 // soft_demap_nw: a workgroup owns Dc consecutive symbols of one packet.  It first turns the packet's variances into
-// weights in LDS (thread t adds v[t], v[t + 256], ... in ascending order, a binary tree over the 256 partial sums gives
-// vbar: the same number in every workgroup of the packet), then streams its symbols: thread = carrier, 16 bytes read
-// and 4 mu bytes written per symbol, the weight from LDS.
+// weights in LDS (thread t adds v[t], v[t + 256], ... in ascending order, packet_vbar's tree over the 256 partial sums
+// gives vbar: the same number in every workgroup of the packet), then streams its symbols: thread = carrier, 16 bytes
+// read and 4 mu bytes written per symbol, the weight from LDS.
 template <int HI>
 __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_kernel(NoiseArgs a) {
     extern __shared__ double nw_lds[];              // [256] partial sums, then [C] weights
@@ -72,20 +69,8 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_kernel(NoiseArgs a) 
     const double* v = a.var_in + f * C;
     double s = 0.0;
     for (int c = t; c < C; c += NW_THREADS) s += v[c];
-    red[t] = s;
-    __syncthreads();
-#pragma unroll
-    for (int h = NW_THREADS / 2; h > 0; h >>= 1) {
-        if (t < h) red[t] += red[t + h];
-        __syncthreads();
-    }
-    const double vbar = red[0] / (double)C;
-    const bool flat = !(vbar > 0.0) || !(vbar < INFINITY);          // 0, NaN, Inf: the packet's weights are 1
-    const double floor_v = 1e-6 * vbar;
-    for (int c = t; c < C; c += NW_THREADS) {
-        const double x = v[c];
-        wgt[c] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : 1.0 / fmax(x, floor_v);
-    }
+    const PacketNoise pn = packet_vbar(red, s, (double)C);
+    for (int c = t; c < C; c += NW_THREADS) wgt[c] = noise_weight(v[c], pn);
     __syncthreads();
     const Levels<HI> lv(a.t);
     const int l0 = blockIdx.x * a.Dc, l1 = min(l0 + a.Dc, a.D);
@@ -94,19 +79,8 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_kernel(NoiseArgs a) 
         for (int c = t; c < C; c += NW_THREADS) {
             const cplx e = a.eq[row + c];
             const double w = wgt[c];
-            if constexpr (HI > 0) {
-                constexpr int MU = 2 * HI;
-                double diff[MU];
-                maxlog_bin<HI, HI>(e, lv.lvI, lv.lvQ, diff);
-                float out[MU];
-#pragma unroll
-                for (int b = 0; b < MU; ++b) out[b] = w == 0.0 ? 0.0f : (float)(diff[b] * w);
-                store_llr<MU>(a.llr, row + c, out);
-            } else {
-                float* dst = a.llr + (row + c) * a.t.mu;
-                if (w == 0.0) { for (int b = 0; b < a.t.mu; ++b) dst[b] = 0.0f; }
-                else maxlog_table(e, a.t, w, dst);
-            }
+            // (the store captures by value: by reference the address arithmetic of the row comes out longer)
+            emit_llr<HI, true>(e, lv, a.t, w, [llr = a.llr, i = row + c, mu = a.t.mu](const auto& out) { store_llr_any(llr, i, mu, out); });
         }
     }
 }
@@ -155,9 +129,7 @@ __global__ __launch_bounds__(CS_THREADS) void noise_estimate_cs_kernel(NoiseCsAr
             for (int k = 0; k < NB; ++k) e[k] = row[c0 + 64 * (k0 + k) < cend ? c0 + 64 * (k0 + k) : 0];
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-                double d2;
-                if constexpr (HI > 0) d2 = axis_min_d2<(1 << HI)>(e[k].x, lv.lvI) + axis_min_d2<(1 << HI)>(e[k].y, lv.lvQ);
-                else d2 = table_min_d2(e[k], a.t.cre, a.t.cim, a.t.M);
+                double d2 = nearest_d2<HI>(e[k], lv, a.t);
                 d2 = c0 + 64 * (k0 + k) < cend ? d2 : 0.0;
                 acc[k0 + k] += d2;
                 srow += d2;
@@ -222,9 +194,12 @@ __global__ __launch_bounds__(IL_THREADS) void interleave_kernel(const T* in, T* 
 // ---- carrier x symbol demapper ---------------------------------------------------------------------------------
 // soft_demap_nw_cs: soft_demap_nw_kernel with the weight 1 / max(v vs / vbar, floor) formed per symbol from two factors
 // kept in LDS: ic[c] = vbar / v[c] and is[l] = 1 / vs[l] (0 marks an erasure, 1 a flat packet), w = ic is capped at
-// 1 / floor -- one multiply and a compare per symbol, no division in the stream.  vbar comes from the same tree as in
-// soft_demap_nw_kernel: the same bits there, here, and in every workgroup of the packet.  DEINT: each LLR goes to its
-// coded position pi^-1(p) of the packet instead of its transmitted position p.
+// 1 / floor -- one multiply and a compare per symbol, no division in the stream.  This is noise_weight(x, pn) of
+// gf3rx_demap.h for x = v vs / vbar, factored (equal in exact arithmetic; the roundings are this kernel's own and its
+// restatement's): 1 / max(x, floor) = min(1 / x, 1 / floor) for x > 0, and 1 / x = (vbar / v) (1 / vs); a variance that
+// is not finite gives a zero factor and so the weight 0; in a flat packet both factors and the cap are 1.  vbar comes
+// from packet_vbar as in soft_demap_nw_kernel: the same bits there, here, and in every workgroup of the packet.
+// DEINT: each LLR goes to its coded position pi^-1(p) of the packet instead of its transmitted position p.
 struct NwCsArgs {
     const cplx* eq; const double* var_c; const double* var_s; float* llr;
     int D, C, Dc;
@@ -244,23 +219,15 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_cs_kernel(NwCsArgs a
     const int l0 = blockIdx.x * a.Dc, l1 = min(l0 + a.Dc, a.D);
     double s = 0.0;
     for (int c = t; c < C; c += NW_THREADS) s += v[c];
-    red[t] = s;
-    __syncthreads();
-#pragma unroll
-    for (int h = NW_THREADS / 2; h > 0; h >>= 1) {
-        if (t < h) red[t] += red[t + h];
-        __syncthreads();
-    }
-    const double vbar = red[0] / (double)C;
-    const bool flat = !(vbar > 0.0) || !(vbar < INFINITY);          // 0, NaN, Inf: the packet's weights are 1
-    const double wmax = flat ? 1.0 : 1.0 / (1e-6 * vbar);
+    const PacketNoise pn = packet_vbar(red, s, (double)C);
+    const double wmax = pn.flat ? 1.0 : 1.0 / pn.floor_v;
     for (int c = t; c < C; c += NW_THREADS) {
         const double x = v[c];
-        ic[c] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : vbar / x;
+        ic[c] = !(fabs(x) < INFINITY) ? 0.0 : pn.flat ? 1.0 : pn.vbar / x;
     }
     for (int l = l0 + t; l < l1; l += NW_THREADS) {
         const double x = a.var_s[f * a.D + l];
-        is[l - l0] = !(fabs(x) < INFINITY) ? 0.0 : flat ? 1.0 : 1.0 / x;
+        is[l - l0] = !(fabs(x) < INFINITY) ? 0.0 : pn.flat ? 1.0 : 1.0 / x;
     }
     __syncthreads();
     const Levels<HI> lv(a.t);
@@ -278,35 +245,17 @@ __global__ __launch_bounds__(NW_THREADS) void soft_demap_nw_cs_kernel(NwCsArgs a
             // a zero factor: erasure; pr not below the cap (v vs / vbar under the floor, Inf from a zero variance) or not
             // positive: the cap
             const double w = (cf == 0.0 || sl == 0.0) ? 0.0 : (pr > 0.0 && pr < wmax) ? pr : wmax;
-            if constexpr (HI > 0) {
-                constexpr int MU = 2 * HI;
-                double diff[MU];
-                maxlog_bin<HI, HI>(e, lv.lvI, lv.lvQ, diff);
-                float out[MU];
-#pragma unroll
-                for (int b = 0; b < MU; ++b) out[b] = w == 0.0 ? 0.0f : (float)(diff[b] * w);
-                if constexpr (DEINT) {
+            // (the stores capture by value: by reference the address arithmetic of the row comes out longer)
+            if constexpr (DEINT)                                    // bit b goes to coded position i0 + b s^-1 (mod nbp)
+                emit_llr<HI, true>(e, lv, a.t, w, [pk, i0, mu, sinv = a.sinv, nbp = a.nbp](const auto& out) {
+                    constexpr int NB = sizeof(out) / sizeof(float);    // 2 HI on a grid (= mu), 8 of which mu are valid for any table
                     uint32_t i = i0;
 #pragma unroll
-                    for (int b = 0; b < MU; ++b) { pk[i] = out[b]; i = addmod(i, a.sinv, a.nbp); }
-                } else store_llr<MU>(a.llr, row + c, out);
-            } else {
-                float out[8];
-#pragma unroll
-                for (int b = 0; b < 8; ++b) out[b] = 0.0f;
-                if (w != 0.0) maxlog_table(e, a.t, w, out);
-                if constexpr (DEINT) {
-                    uint32_t i = i0;
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        if (b < mu) { pk[i] = out[b]; i = addmod(i, a.sinv, a.nbp); }
-                } else {
-                    float* dst = a.llr + (row + c) * mu;
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        if (b < mu) dst[b] = out[b];
-                }
-            }
+                    for (int b = 0; b < NB; ++b)
+                        if (NB < 8 || b < mu) { pk[i] = out[b]; i = addmod(i, sinv, nbp); }
+                });
+            else
+                emit_llr<HI, true>(e, lv, a.t, w, [llr = a.llr, i = row + c, mu](const auto& out) { store_llr_any(llr, i, mu, out); });
             if constexpr (DEINT) i0 = addmod(i0, a.step_c, a.nbp);
         }
         if constexpr (DEINT) irow = addmod(irow, a.step_l, a.nbp);
@@ -319,16 +268,11 @@ extern "C" int gf3_noise_estimate(gf3_ctx* c, const void* d_eq, int64_t F, doubl
     DeviceGuard dg(c);
     if (c && F == 0) return GF3_OK;
     if (!c || !d_eq || !d_var || F < 0) return fail(c, GF3_EINVAL, "gf3_noise_estimate: bad argument");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_noise_estimate: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_noise_estimate")) return rc;
     NoiseArgs a{(const cplx*)d_eq, d_var, nullptr, nullptr, F, c->cfg.D, c->cfg.C, 0, demap_tab(c)};
     const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)F), block(64 * NE_WAVES);
     hipStream_t st = (hipStream_t)stream;
-    switch (grid_bits(c)) {
-        case 1: hipLaunchKernelGGL(noise_estimate_kernel<1>, grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(noise_estimate_kernel<2>, grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(noise_estimate_kernel<3>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(noise_estimate_kernel<0>, grid, block, 0, st, a); break;
-    }
+    with_grid_bits(c, [&](auto hi) { hipLaunchKernelGGL(noise_estimate_kernel<decltype(hi)::value>, grid, block, 0, st, a); });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }
@@ -337,53 +281,39 @@ extern "C" int gf3_soft_demap_nw(gf3_ctx* c, const void* d_eq, const double* d_v
     DeviceGuard dg(c);
     if (c && F == 0) return GF3_OK;
     if (!c || !d_eq || !d_var || !d_llr || F < 0) return fail(c, GF3_EINVAL, "gf3_soft_demap_nw: bad argument");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_soft_demap_nw: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_soft_demap_nw")) return rc;
     NoiseArgs a{(const cplx*)d_eq, nullptr, d_var, d_llr, F, c->cfg.D, c->cfg.C, 0, demap_tab(c)};
-    // about 8 workgroups per compute unit when there are packets enough; a handful of long packets is cut down to
-    // single symbols
-    int64_t nchunk = (8 * (int64_t)c->n_cu + F - 1) / F;
-    if (nchunk > a.D) nchunk = a.D;
-    if (nchunk < 1) nchunk = 1;
-    a.Dc = (int)((a.D + nchunk - 1) / nchunk);
+    a.Dc = symbols_per_group(c, F, a.D);
     const dim3 grid((unsigned)((a.D + a.Dc - 1) / a.Dc), (unsigned)F), block(NW_THREADS);
     const size_t lds = (size_t)(NW_THREADS + a.C) * sizeof(double);
     hipStream_t st = (hipStream_t)stream;
-    switch (grid_bits(c)) {
-        case 1: hipLaunchKernelGGL(soft_demap_nw_kernel<1>, grid, block, lds, st, a); break;
-        case 2: hipLaunchKernelGGL(soft_demap_nw_kernel<2>, grid, block, lds, st, a); break;
-        case 3: hipLaunchKernelGGL(soft_demap_nw_kernel<3>, grid, block, lds, st, a); break;
-        default: hipLaunchKernelGGL(soft_demap_nw_kernel<0>, grid, block, lds, st, a); break;
-    }
+    with_grid_bits(c, [&](auto hi) { hipLaunchKernelGGL(soft_demap_nw_kernel<decltype(hi)::value>, grid, block, lds, st, a); });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }
 
 // (NCG in steps of 4: a slot beyond the half's columns costs a repeated load of carrier 0)
-template <int HI>
-hipError_t launch_noise_cs(const NoiseCsArgs& a, int64_t F, size_t lds, hipStream_t st) {
-    if (a.ncg <= 4) return launch(noise_estimate_cs_kernel<HI, 4>, F, CS_THREADS, lds, st, a);
-    if (a.ncg <= 8) return launch(noise_estimate_cs_kernel<HI, 8>, F, CS_THREADS, lds, st, a);
-    if (a.ncg <= 12) return launch(noise_estimate_cs_kernel<HI, 12>, F, CS_THREADS, lds, st, a);
-    return launch(noise_estimate_cs_kernel<HI, 16>, F, CS_THREADS, lds, st, a);
+hipError_t launch_noise_cs(const gf3_ctx* c, const NoiseCsArgs& a, int64_t F, size_t lds, hipStream_t st) {
+    return with_grid_bits(c, [&](auto hi) {
+        constexpr int HI = decltype(hi)::value;
+        if (a.ncg <= 4) return launch(noise_estimate_cs_kernel<HI, 4>, F, CS_THREADS, lds, st, a);
+        if (a.ncg <= 8) return launch(noise_estimate_cs_kernel<HI, 8>, F, CS_THREADS, lds, st, a);
+        if (a.ncg <= 12) return launch(noise_estimate_cs_kernel<HI, 12>, F, CS_THREADS, lds, st, a);
+        return launch(noise_estimate_cs_kernel<HI, 16>, F, CS_THREADS, lds, st, a);
+    });
 }
 
 extern "C" int gf3_noise_estimate_cs(gf3_ctx* c, const void* d_eq, int64_t F, double* d_var_c, double* d_var_s, void* stream) {
     DeviceGuard dg(c);
     if (c && F == 0) return GF3_OK;
     if (!c || !d_eq || !d_var_c || !d_var_s || F < 0) return fail(c, GF3_EINVAL, "gf3_noise_estimate_cs: bad argument");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_noise_estimate_cs: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_noise_estimate_cs")) return rc;
     NoiseCsArgs a{(const cplx*)d_eq, d_var_c, d_var_s, c->cfg.D, c->cfg.C, 0, demap_tab(c)};
     a.ncg = ((a.C + 63) / 64 + 1) / 2;
     const size_t lds = (8 * (size_t)a.C + 2 * (size_t)a.D) * sizeof(double);
     if (a.ncg > CS_MAX_NCG || lds > 160 * 1024)
         return fail(c, GF3_ERANGE, "gf3_noise_estimate_cs: a packet's partial sums (64 C + 16 D bytes) must fit 160 KB of LDS, C <= 2048");
-    hipStream_t st = (hipStream_t)stream;
-    switch (grid_bits(c)) {
-        case 1: HIPCHK(c, launch_noise_cs<1>(a, F, lds, st)); break;
-        case 2: HIPCHK(c, launch_noise_cs<2>(a, F, lds, st)); break;
-        case 3: HIPCHK(c, launch_noise_cs<3>(a, F, lds, st)); break;
-        default: HIPCHK(c, launch_noise_cs<0>(a, F, lds, st)); break;
-    }
+    HIPCHK(c, launch_noise_cs(c, a, F, lds, (hipStream_t)stream));
     return GF3_OK;
 }
 
@@ -393,28 +323,21 @@ extern "C" int gf3_soft_demap_nw_cs(gf3_ctx* c, const void* d_eq, const double* 
     if (c && F == 0) return GF3_OK;
     if (!c || !d_eq || !d_var_c || !d_var_s || !d_llr || F < 0 || (deinterleave != 0 && deinterleave != 1))
         return fail(c, GF3_EINVAL, "gf3_soft_demap_nw_cs: bad argument");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_soft_demap_nw_cs: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_soft_demap_nw_cs")) return rc;
     Perm pm;
     if (!perm_of(c, pm)) return fail(c, GF3_ERANGE, "gf3_soft_demap_nw_cs: D C mu must be below 2^31");
     NwCsArgs a{(const cplx*)d_eq, d_var_c, d_var_s, d_llr, c->cfg.D, c->cfg.C, 0, pm.nbp, pm.sinv, 0, 0, demap_tab(c)};
     a.step_c = (uint32_t)((uint64_t)NW_THREADS * c->cfg.mu % pm.nbp * pm.sinv % pm.nbp);
     a.step_l = (uint32_t)((uint64_t)a.C * c->cfg.mu % pm.nbp * pm.sinv % pm.nbp);
-    int64_t nchunk = (8 * (int64_t)c->n_cu + F - 1) / F;            // as gf3_soft_demap_nw
-    if (nchunk > a.D) nchunk = a.D;
-    if (nchunk < 1) nchunk = 1;
-    a.Dc = (int)((a.D + nchunk - 1) / nchunk);
+    a.Dc = symbols_per_group(c, F, a.D);
     const dim3 grid((unsigned)((a.D + a.Dc - 1) / a.Dc), (unsigned)F), block(NW_THREADS);
     const size_t lds = (size_t)(NW_THREADS + a.C + a.Dc) * sizeof(double);
     hipStream_t st = (hipStream_t)stream;
-#define GF3_NWCS(HI) do { if (deinterleave) hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, true>), grid, block, lds, st, a); \
-                          else hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, false>), grid, block, lds, st, a); } while (0)
-    switch (grid_bits(c)) {
-        case 1: GF3_NWCS(1); break;
-        case 2: GF3_NWCS(2); break;
-        case 3: GF3_NWCS(3); break;
-        default: GF3_NWCS(0); break;
-    }
-#undef GF3_NWCS
+    with_grid_bits(c, [&](auto hi) {
+        constexpr int HI = decltype(hi)::value;
+        if (deinterleave) hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, true>), grid, block, lds, st, a);
+        else hipLaunchKernelGGL((soft_demap_nw_cs_kernel<HI, false>), grid, block, lds, st, a);
+    });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }
@@ -424,7 +347,7 @@ extern "C" int gf3_interleave(gf3_ctx* c, const void* d_in, void* d_out, int64_t
     if (c && F == 0) return GF3_OK;
     if (!c || !d_in || !d_out || d_in == d_out || F < 0 || (elem_bytes != 1 && elem_bytes != 4) || (inverse != 0 && inverse != 1))
         return fail(c, GF3_EINVAL, "gf3_interleave: bad argument (elem_bytes 1 or 4, inverse 0 or 1, out of place)");
-    if (F > 65535) return fail(c, GF3_EINVAL, "gf3_interleave: at most 65535 packets per call");
+    if (const int rc = too_many_packets(c, F, "gf3_interleave")) return rc;
     Perm pm;
     if (!perm_of(c, pm)) return fail(c, GF3_ERANGE, "gf3_interleave: D C mu must be below 2^31");
     const uint32_t m = inverse ? pm.s : pm.sinv;

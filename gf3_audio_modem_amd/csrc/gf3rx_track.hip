@@ -3,6 +3,7 @@
 // Two numbers per data symbol, a common phase a and a phase slope b around the centre of the data band
 // (kappa_c = data_bins[c] - mean(data_bins)), follow a decision-directed loop with a velocity term:
 //   pa = a + va, pb = b + vb;  z_c = eq[l, c] exp(-i (pa + pb kappa_c));  s_c the point the hard decision picks for z_c
+//   (nearest_point of gf3rx_demap.h: the in-order scan with strict <, the twin of the noise estimate's nearest_d2)
 //   r_c = z_c conj(s_c);  S0 = sum r, S1 = sum kappa r, S2 = sum kappa^2 r, E = sum |z - s|^2, P = sum |s|^2
 //   da = atan2(Im S0, Re S0), u = exp(-i da), den = Re(u S2);  measured <=> sums finite, den > 0, E <= P
 //   measured: a' = pa + da, b' = pb + Im(u S1) / den;  else a' = pa, b' = pb;  va = a' - a, vb = b' - b
@@ -29,31 +30,6 @@ struct TrackArgs {
     int D, C;
     DemapTab t;
 };
-
-// the level the in-order scan with strict < picks on one axis
-template <int N>
-GF3_DEV double axis_nearest(double x, const double (&lv)[N]) {
-    double t = x - lv[0], bd = t * t, bl = lv[0];
-#pragma unroll
-    for (int k = 1; k < N; ++k) {
-        t = x - lv[k];
-        const double d = t * t;
-        if (d < bd) { bd = d; bl = lv[k]; }
-    }
-    return bl;
-}
-GF3_DEV cplx table_nearest(cplx e, const double* cre, const double* cim, int M) {
-    cplx p = cmk(cre[0], cim[0]);
-    double dx = e.x - p.x, dy = e.y - p.y;
-    double bd = dx * dx + dy * dy;
-    for (int c = 1; c < M; ++c) {
-        const cplx q = cmk(cre[c], cim[c]);
-        dx = e.x - q.x; dy = e.y - q.y;
-        const double d = dx * dx + dy * dy;
-        if (d < bd) { bd = d; p = q; }
-    }
-    return p;
-}
 
 // e exp(-i x)
 GF3_DEV cplx derotate(cplx e, double x) {
@@ -102,9 +78,7 @@ __global__ __launch_bounds__(TR_THREADS) void track_phase_kernel(TrackArgs a) {
         for (int k = 0; k < CPT; ++k) {
             const cplx z = derotate(cur[k], pa + pb * kap[k]);
             const bool ok = t + k * TR_THREADS < C && fabs(z.x) < INFINITY && fabs(z.y) < INFINITY;
-            cplx s;
-            if constexpr (HI > 0) s = cmk(axis_nearest<(1 << HI)>(z.x, lv.lvI), axis_nearest<(1 << HI)>(z.y, lv.lvQ));
-            else s = table_nearest(z, a.t.cre, a.t.cim, a.t.M);
+            const cplx s = nearest_point<HI>(z, lv, a.t);
             const cplx r = cmul_conj(z, s);
             const double dx = z.x - s.x, dy = z.y - s.y, kp = kap[k], k2 = kp * kp;
             acc[0] += ok ? r.x : 0.0;
@@ -158,14 +132,16 @@ __global__ __launch_bounds__(TR_THREADS) void track_phase_kernel(TrackArgs a) {
     }
 }
 
-template <int HI>
-hipError_t launch_track(const TrackArgs& a, int64_t F, hipStream_t st) {
+hipError_t launch_track(const gf3_ctx* c, const TrackArgs& a, int64_t F, hipStream_t st) {
     const int cpt = (a.C + TR_THREADS - 1) / TR_THREADS;
-    if (cpt <= 1) return launch(track_phase_kernel<HI, 1>, F, TR_THREADS, 0, st, a);
-    if (cpt <= 2) return launch(track_phase_kernel<HI, 2>, F, TR_THREADS, 0, st, a);
-    if (cpt <= 3) return launch(track_phase_kernel<HI, 3>, F, TR_THREADS, 0, st, a);
-    if (cpt <= 4) return launch(track_phase_kernel<HI, 4>, F, TR_THREADS, 0, st, a);
-    return launch(track_phase_kernel<HI, TR_MAX_CPT>, F, TR_THREADS, 0, st, a);
+    return with_grid_bits(c, [&](auto hi) {
+        constexpr int HI = decltype(hi)::value;
+        if (cpt <= 1) return launch(track_phase_kernel<HI, 1>, F, TR_THREADS, 0, st, a);
+        if (cpt <= 2) return launch(track_phase_kernel<HI, 2>, F, TR_THREADS, 0, st, a);
+        if (cpt <= 3) return launch(track_phase_kernel<HI, 3>, F, TR_THREADS, 0, st, a);
+        if (cpt <= 4) return launch(track_phase_kernel<HI, 4>, F, TR_THREADS, 0, st, a);
+        return launch(track_phase_kernel<HI, TR_MAX_CPT>, F, TR_THREADS, 0, st, a);
+    });
 }
 
 }  // namespace
@@ -178,12 +154,6 @@ extern "C" int gf3_track_phase(gf3_ctx* c, const void* d_eq, int64_t F, void* d_
     if (F > 0x7fffffff) return fail(c, GF3_EINVAL, "gf3_track_phase: at most 2^31 - 1 packets per call");
     if (c->cfg.C > TR_MAX_CPT * TR_THREADS) return fail(c, GF3_ERANGE, "gf3_track_phase: C <= 4096");
     TrackArgs a{(const cplx*)d_eq, (cplx*)d_out, d_phase, d_measured, c->d_bins, c->bin_mean, c->cfg.D, c->cfg.C, demap_tab(c)};
-    hipStream_t st = (hipStream_t)stream;
-    switch (grid_bits(c)) {
-        case 1: HIPCHK(c, launch_track<1>(a, F, st)); break;
-        case 2: HIPCHK(c, launch_track<2>(a, F, st)); break;
-        case 3: HIPCHK(c, launch_track<3>(a, F, st)); break;
-        default: HIPCHK(c, launch_track<0>(a, F, st)); break;
-    }
+    HIPCHK(c, launch_track(c, a, F, (hipStream_t)stream));
     return GF3_OK;
 }
