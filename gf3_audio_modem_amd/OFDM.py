@@ -58,6 +58,7 @@ class CamG:
     """Parameter block: same constructor and attributes as OFDM.py:17-114."""
 
     last_tx_report = None                       # set by every transmit() (see papr_reduction below)
+    sync_report = None                          # set by every receive call (see sync_rule below)
 
     def __init__(self, mode, encoding="None", no_pilots=20, packet_length=180):
         self.encoding = encoding
@@ -229,6 +230,19 @@ class CamG:
         # finite number in [3, 13] dB, a tone limit outside [-20, 20] dB, iterations that are not an integer in [0, 64], a
         # body_gain that is not finite or <= 0, fewer than 8 reserved carriers (the *1 modes); NotImplementedError together
         # with bit_loading (that path maps on the host).
+        # receive side, every encoding: sync_rule chooses how receive() and receive_diversity() find the chirps.  "global" is
+        # the reference's rule: the matched filter against 0.4 x its maximum over the WHOLE recording (OFDM.py:359), so
+        # anything 8 dB above a packet's chirp -- a louder second transmission, a door slam -- removes that packet.  "local"
+        # (Engine.detect_stream) thresholds the correlation COEFFICIENT of every window with the chirp at
+        # detect_threshold and keeps the largest within a chirp length to either side: the statistic carries its own scale,
+        # so quiet and loud transmissions in one recording are found alike, an offset (8-bit audio) changes nothing, and a
+        # chirp at the very end of the recording is a detection like any other.  Everything after the sync is the same.
+        # A receive call under "local" leaves {"rho": the coefficient of every detection (a list per recording for
+        # receive_diversity), "threshold"} in `sync_report`; it is None under "global".  ValueError for another rule or a
+        # threshold that is not a finite number inside (0, 1); NotImplementedError on the piece-wise host path -- a stream
+        # that does not end is what live.LiveReceiver takes.
+        self.sync_rule = "global"
+        self.detect_threshold = 0.3
         self.papr_reduction = False
         self.papr_target_db = 6.0
         self.papr_iterations = 16
@@ -694,14 +708,20 @@ class receiver(transmitter):
         """What this call will do with recordings of `lengths` samples, or its refusal (pipeline.plan_receive); no GPU work."""
         return plan_receive(self, self._chain(), lengths, graph_output, diversity)
 
-    def _receive(self, signals, graph_output, diversity):
-        """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage."""
+    def _receive(self, signals, graph_output, diversity, located=None):
+        """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage.
+        located (live.LiveReceiver): (samples on the engine's device, their detections under the local rule, the detections'
+        coefficients) -- step 1 is then skipped: the stream it was cut from has been through it already."""
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
         print(self)
-        rs = _as_recordings(signals) if diversity else [_as_samples(signals)]
+        if located is None:
+            rs = _as_recordings(signals) if diversity else [_as_samples(signals)]
+            dtype = np.result_type(*[r.dtype for r in rs])
+        else:
+            rs = [located[0]]
+            dtype = torch.empty(0, dtype=located[0].dtype).numpy().dtype
         plan = self._plan([len(r) for r in rs], graph_output, diversity)
-        dtype = np.result_type(*[r.dtype for r in rs])
         eng = self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
         # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
@@ -711,7 +731,14 @@ class receiver(transmitter):
             return self._receive_chunked(eng, rs[0], plan.chunk)
         # 1. sync, every recording on its own
         xs = [eng._samples(r) for r in rs]
-        starts = [(eng.sync_stream(x) + 2)[:-1] for x in xs]   # OFDM.py:393-395
+        sync_rho = None
+        if located is not None:
+            peaks, sync_rho = [located[1]], [located[2]]
+        elif plan.detect is None:
+            peaks = [eng.sync_stream(x) for x in xs]
+        else:
+            peaks, sync_rho = zip(*[eng.detect_stream(x, plan.detect, want_peak_rho=True) for x in xs])
+        starts = [(p + 2)[:-1] for p in peaks]                  # OFDM.py:393-395
         counts = [int(st.numel()) for st in starts]
         if len(set(counts)) != 1:
             raise ValueError(f"receive_diversity: the recordings hold different numbers of packets: {counts}")
@@ -741,6 +768,8 @@ class receiver(transmitter):
         # for; last in it the ragged-packet flags (a packet that runs past the recording: the reference's get_symbols fails
         # on it; an offset the resampler could not apply)
         rows.update(Hs0=outs[0]["Hs"][0], He0=outs[0]["He"][0], slope=outs[0]["slope"])
+        if sync_rho is not None:                                # (the recordings hold the same number of detections by now)
+            rows["sync_rho"] = torch.stack(list(sync_rho)) if diversity else sync_rho[0]
         if diversity:
             rows["last_branch_starts"] = torch.stack(starts)
             rows.update({name: torch.stack([stage[name] for stage in stages]) for name in stages[0]})
@@ -794,6 +823,7 @@ class receiver(transmitter):
         """The attributes a receive call leaves, from the fetched rows.  Each call assigns its own list and touches nothing
         else (the table and the open point that follows from it: DESIGN §12, "The receive pipeline")."""
         self._last_slope = got["slope"]
+        self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
         for name in _VALUE_OR_NONE[diversity]:
             setattr(self, name, got.get(name))
         if plan.clock and not diversity:                        # (one recording: the value, not an array [B])

@@ -9,6 +9,7 @@ Layout
   ldpc.py    QCLDPC: the project's quasi-cyclic LDPC codes (GPU encoder + layered min-sum decoder)
   outer.py   OuterRS: Reed-Solomon erasure code across codewords (repairs the codewords the LDPC decoder gives up on)
   loading.py adaptive bit loading: a QAM order per carrier from the measured SNR, the loaded mapper (host, NumPy)
+  live.py    LiveReceiver: receive while the stream is still arriving (the self-normalised detection, piece by piece)
   crc.py     CodewordCRC: CRC-32 per codeword (catches the codewords the LDPC decoder converged on wrongly)
   dist.py    frame sharding across GPUs + the all-gather of packed bits (overlapped per chunk)
 """
@@ -16,5 +17,6 @@ from .engine import Engine, RxConfig, qpsk_table, square_qam_table  # noqa: F401
 from .ldpc import QCLDPC  # noqa: F401
 from .outer import OuterRS  # noqa: F401
 from .crc import CodewordCRC  # noqa: F401
+from .live import LiveReceiver, Segmenter, Transmission  # noqa: F401
 
 __version__ = "0.1.0"

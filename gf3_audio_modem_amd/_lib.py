@@ -109,6 +109,11 @@ _SIGS = {
     "gf3_sync_decide_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int64]),
     "gf3_sync_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                   c_i64_p, C.c_void_p, C.c_void_p]),
+    "gf3_detect_chunk_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "gf3_detect_chunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int64, c_i64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gf3_detect_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_i64_p,
+                                    C.c_void_p, C.c_void_p]),
     "gf3_sync_stream_mode": (C.c_int, [C.c_void_p, C.c_int32]),
     "gf3_sync_stream_info": (C.c_int, [C.c_void_p, c_i64_p]),
     "gf3_debug_stream_screen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

@@ -257,6 +257,12 @@ extern "C" int gf3_ctx_create(const gf3_config* cfg, gf3_ctx** out) {
         const double ph = 2 * M_PI * (cfg->f0 * t + 0.5 * beta * t * t);
         c->chirp[i] = cos(ph) / 5;
     }
+    {   // the replica's sum and its centred energy Ec - Sc^2 / Lc (gf3_detect_chunk's normaliser)
+        long double s = 0.0L, e = 0.0L;
+        for (double v : c->chirp) { s += v; e += (long double)v * v; }
+        c->chirp_sum = (double)s;
+        c->chirp_var = (double)(e - s * s / c->Lc);
+    }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { int rc_ = fail(nullptr, GF3_EHIP, "%s: %s", #x, hipGetErrorString(e_)); gf3_ctx_destroy(c); return rc_; } } while (0)
     CK(dev_new(c->owned, &c->d_tw, tw.tw));
     CK(dev_new(c->owned, &c->d_twn, tw.twn));

@@ -10,6 +10,8 @@
 //   gf3rx_fscreen.hip        corr_screen_kernel: the fp32 screen of the frames-mode sync (gf3rx_fscreen.h)
 //   gf3rx_stamp.cpp          the build stamp (source hash), recompiled on every change
 //   gf3rx_sync.hip           pk_*, ck_*, scr list kernels + gf3_sync_stream*, gf3_sync_chunk, gf3_sync_decide (the peak rule they share with corr_kernel: gf3rx_peak.h)
+//   gf3rx_detect.hip         det_* + gf3_detect_chunk, gf3_detect_decide: the self-normalised chirp detection (Pearson correlation of every
+//                            window with the replica; on P of gf3rx_sync.hip's all-fp64 overlap-save)
 //   gf3rx_ldpc.hip           ldpc_encode_kernel, ldpc_decode_kernel + gf3_ldpc_*
 //   gf3rx_outer.hip          rs_encode_kernel, rs_recover_kernel + gf3_outer_encode, gf3_outer_recover (field arithmetic: gf3rx_outer.h)
 //   gf3rx_crc.hip            crc_kernel + gf3_crc_attach, gf3_crc_check (per-codeword CRC-32)
@@ -226,6 +228,7 @@ struct gf3_ctx {
     int* d_rsv = nullptr;               // [K] number of a carrier among the Ku = K - C carriers outside data_bins, ascending, or -1 (gf3_tone_reserve)
     int Ku = 0;
     double* d_chirp = nullptr;
+    double chirp_sum = 0.0, chirp_var = 0.0;   // Sc and Ec - Sc^2 / Lc of the replica (gf3rx_detect.hip)
     double* d_chirp_t = nullptr;  // the same taps in the order scr_refine_kernel's lanes consume them (RefineArgs::chirp_t)
     double* d_known_time = nullptr;     // one pilot symbol in the time domain (transmit side)
     SepTab sep{};
@@ -415,6 +418,13 @@ hipError_t run_corr(const gf3_ctx* c, const CorrPlan& pl, const CorrArgs& a, int
 struct FScreenArgs;
 hipError_t launch_fscreen(const gf3_ctx* c, const FScreenArgs& a, int64_t F, hipStream_t st);
 hipError_t run_spec_ols(const CorrPlan& pl, OlsArgs a, int64_t nwin, int64_t nblk, hipStream_t st);   // spec_kernel, then ols_kernel
+// gf3rx_sync.hip, for gf3rx_detect.hip: P of d_in [n] by the all-fp64 overlap-save of gf3_sync_stream, in a workspace of
+// gf3_sync_stream_workspace_bytes(c, n) bytes (*P: where in it, n + Lc - 1 doubles); pk_scan on `n` counts; the read-back of a
+// call's result words (valid until the calling thread's next one); {count, status} of a peak list -> *n_peaks or GF3_ERANGE
+int stream_corr(const gf3_ctx* c, const void* d_in, int64_t n, void* d_work, double** P, hipStream_t st);
+void launch_pk_scan(const int64_t* counts, int64_t n, int64_t* offsets, int64_t* total, hipStream_t st);
+int read_back(const gf3_ctx* c, hipStream_t st, const void** h, const void* d_src, size_t bytes, const void* d_src2 = nullptr, size_t bytes2 = 0);
+int finish_peaks(const gf3_ctx* c, const char* who, const int64_t* h, int64_t cap, int64_t* n_peaks);
 // gf3rx_screen.hip
 hipError_t launch_screen(const gf3_ctx* c, ScreenArgs a, bool general, hipStream_t st);
 hipError_t launch_refine(const gf3_ctx* c, const RefineArgs& a, int64_t cap_cells, hipStream_t st);

@@ -19,8 +19,7 @@ struct ReadbackPage {
 };
 // The read-back of a call: `bytes` from d_src -- and, behind them, bytes2 from d_src2 when given -- to the calling thread's
 // page, the stream synchronised; *h = the host copy (valid until the thread's next read-back).
-static int read_back(const gf3_ctx* c, hipStream_t st, const void** h, const void* d_src, size_t bytes,
-                     const void* d_src2 = nullptr, size_t bytes2 = 0) {
+int read_back(const gf3_ctx* c, hipStream_t st, const void** h, const void* d_src, size_t bytes, const void* d_src2, size_t bytes2) {
     static thread_local ReadbackPage page;
     char* dst = page.p ? (char*)page.p : page.local;
     HIPCHK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
@@ -30,7 +29,7 @@ static int read_back(const gf3_ctx* c, hipStream_t st, const void** h, const voi
     return GF3_OK;
 }
 // {count, status} of the suppression walk (pk_nms) -> *n_peaks, and GF3_ERANGE when the peaks did not fit
-static int finish_peaks(const gf3_ctx* c, const char* who, const int64_t* h, int64_t cap, int64_t* n_peaks) {
+int finish_peaks(const gf3_ctx* c, const char* who, const int64_t* h, int64_t cap, int64_t* n_peaks) {
     *n_peaks = h[0];
     if (h[1] == 2) return fail(c, GF3_ERANGE, "%s: %lld peaks exceed capacity %lld", who, (long long)h[0], (long long)cap);
     return GF3_OK;
@@ -279,6 +278,17 @@ static OlsArgs ols_args(const gf3_ctx* c, const StreamWs& w, const StreamPtrs& p
     a.Hq = pl.d_Hq; a.Q = pl.Q; a.H = pl.Lp; a.Lc = c->Lc;
     a.spec = p.spec; a.nwin = w.nwin; a.plen = w.plen; a.corr = P; a.part = p.part;
     return a;
+}
+// (gf3rx_host.h: what gf3rx_detect.hip takes from this unit)
+int stream_corr(const gf3_ctx* c, const void* d_in, int64_t n, void* d_work, double** P, hipStream_t st) {
+    const StreamWs w = stream_ws(c, n);
+    const StreamPtrs p = stream_ptrs(w, d_work);
+    *P = p.P;
+    HIPCHK(c, run_spec_ols(c->stream_plan, ols_args(c, w, p, d_in, n, p.P), w.nwin, w.nblk, st));
+    return GF3_OK;
+}
+void launch_pk_scan(const int64_t* counts, int64_t n, int64_t* offsets, int64_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, st, counts, n, offsets, total, (const long long*)nullptr, (const long long*)nullptr);
 }
 extern "C" int64_t gf3_sync_stream_workspace_bytes(const gf3_ctx* c, int64_t n) {
     if (!c || n < 1) return 0;

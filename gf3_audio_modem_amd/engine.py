@@ -106,6 +106,14 @@ class RxConfig:
         return map_bits(kb, self.const_points, self.const_bits)
 
 
+class ListOverflow(Gf3Error):
+    """GF3_ERANGE of Engine.detect_chunk: `wanted` entries did not fit the list."""
+
+    def __init__(self, text, wanted):
+        super().__init__(text)
+        self.wanted = wanted
+
+
 class Loading:
     """One gf3_loading of an engine (Engine.loading): handle, the order table (uint8 [C]) and bits = Bs."""
 
@@ -486,6 +494,74 @@ class Engine:
         """Of the calling thread's last sync_stream call: dict(path=0 screened | 1 fp64 after a non-selective screen |
         2 fp64, cells = cells of 14 lags re-evaluated in fp64, cells_hit = those holding a candidate, candidates)."""
         return dict(getattr(self._tls, "sync_info", dict(path=2, cells=0, cells_hit=0, candidates=0)))
+
+    # ------------------------------------------------------------------ self-normalised detection (DESIGN 3.6)
+    @staticmethod
+    def check_detect(threshold):
+        """ValueError for a detection threshold that is not a finite number inside (0, 1) -> the threshold as a float."""
+        number = isinstance(threshold, (int, float, np.integer, np.floating)) and not isinstance(threshold, (bool, np.bool_))
+        if not number or not math.isfinite(float(threshold)) or not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f"detection threshold must be a finite number inside (0, 1), not {threshold!r}")
+        return float(threshold)
+
+    def detect_chunk(self, buf, lag_lo, lag_hi, lag_offset, vrun, threshold=0.3, cap=1024, rho_all=None):
+        """gf3_detect_chunk on one buffer (a piece of a stream with Lc - 1 samples of what came before in front): the
+        correlation coefficient rho of every owned full-window lag with the chirp, the lags with rho > threshold listed.
+        vrun: float64 device tensor of one element, the largest window variance so far (zero before the first piece),
+        updated in place.  rho_all: optional float64 [n + Lc - 1] device tensor; rho[g] of every owned lag is written at [g].
+        -> (idx int64 [m] = g - 1 + lag_offset, rho float64 [m]), ascending.  ListOverflow (a Gf3Error; .wanted = the
+        entries to make room for) when more than `cap` lags are to be listed: nothing was listed, vrun is unchanged."""
+        threshold = self.check_detect(threshold)
+        buf = self._samples(buf).reshape(-1)
+        n = buf.numel()
+        idx, rho = self._new((max(cap, 1),), torch.int64), self._new((max(cap, 1),), torch.float64)
+        work = self._new((int(self.lib.gf3_detect_chunk_workspace_bytes(self._h, n)),), torch.uint8)
+        cnt = C.c_int64(0)
+        rc = self.lib.gf3_detect_chunk(self._h, _ptr(buf), n, int(lag_lo), int(lag_hi), int(lag_offset), threshold, _ptr(vrun),
+                                       _ptr(idx), _ptr(rho), int(cap), C.byref(cnt), _ptr(rho_all), _ptr(work), self._stream())
+        if rc == _lib.GF3_ERANGE:
+            raise ListOverflow(f"gf3rx error {rc}: {_lib.last_error()}", int(cnt.value))
+        self._check(rc)
+        return idx[: cnt.value], rho[: cnt.value]
+
+    def detect_decide(self, idx, rho, final_below=(1 << 62) - 1, cap=None):
+        """gf3_detect_decide: the windowed-maximum rule on a list as detect_chunk returns it -> the detections (int64 device
+        tensor) whose neighbourhood of Lc - 1 indices to either side lies below `final_below` (the default: the stream has
+        ended, INT64_MAX / 2)."""
+        idx, rho = self._dev(idx, torch.int64), self._dev(rho, torch.float64)
+        m = idx.numel()
+        if rho.numel() != m:
+            raise ValueError("detect_decide: idx and rho must have the same length")
+        cap = cap or max(4, m)
+        peaks = self._new((cap,), torch.int64)
+        work = self._new((64,), torch.uint8)
+        cnt = C.c_int64(0)
+        self._check(self.lib.gf3_detect_decide(self._h, _ptr(idx) if m else None, _ptr(rho) if m else None, m, int(final_below),
+                                               _ptr(peaks), cap, C.byref(cnt), _ptr(work), self._stream()))
+        return peaks[: cnt.value]
+
+    def detect_stream(self, x, threshold=0.3, want_rho=False, want_peak_rho=False):
+        """The self-normalised chirp detection on one whole stream, as a single piece: indices i = g - 1 of the detected
+        lags (int64 tensor, what sync_stream returns under the reference's rule), with want_rho the coefficient of every
+        lag, float64 [n + Lc - 1] (0 on the partial windows at both ends), and with want_peak_rho the coefficients of the
+        detections.  A list that overflows is retried once with the reported size; ValueError if it overflows again."""
+        threshold = self.check_detect(threshold)
+        x = self._samples(x).reshape(-1)
+        n, Lc = x.numel(), self.cfg.chirp_length
+        rho_all = torch.zeros((n + Lc - 1,), dtype=torch.float64, device=self.device) if want_rho else None
+        cap = 64 * (n // Lc + 4)
+        for attempt in (0, 1):
+            vrun = torch.zeros((1,), dtype=torch.float64, device=self.device)
+            try:
+                idx, rho = self.detect_chunk(x, 0, n + Lc - 1, 0, vrun, threshold, cap, rho_all)
+                break
+            except ListOverflow as e:
+                if attempt:
+                    raise ValueError(f"detect_stream: the list overflowed twice ({e.wanted} lags above the threshold)")
+                cap = e.wanted
+        peaks = self.detect_decide(idx, rho)
+        out = (peaks,) + ((rho_all,) if want_rho else ()) + ((rho[torch.searchsorted(idx, peaks)],) if want_peak_rho else ())
+        return out[0] if len(out) == 1 else out
 
     def debug_stream_screen(self, x):
         """The fp32 screening pass alone (tests): (P32 [n+Lc-1] float32, block maxima, block error bounds, hop)."""

@@ -12,6 +12,7 @@ PIECEWISE_ABOVE = 1 << 27                                   # samples: a longer 
 PIECEWISE_CHUNK = 1 << 25                                   # samples per piece where `host_chunk_samples` names none
 CLOCK_MAX_PPM = 2000.0                                      # |eps| <= 2e-3: beyond it gf3_resample_frames copies the body
 _HOST = "the piece-wise host path of long recordings (or host_chunk_samples)"
+_LOCAL = "sync_rule 'local': {host} decides by the reference's global rule; feed the stream to a LiveReceiver"
 
 
 def fetch(tensors):
@@ -56,6 +57,16 @@ def check_clock(clock_correction, clock_taps):
     return ppm, int(clock_taps) // 2
 
 
+def check_sync_rule(sync_rule, detect_threshold):
+    """What `sync_rule` / `detect_threshold` refuse before any GPU work -> None under "global" (the reference's rule), the
+    threshold as a float under "local" (Engine.detect_stream).  ValueError for another rule and for a threshold that is not a
+    finite number inside (0, 1)."""
+    if not isinstance(sync_rule, str) or sync_rule not in ("global", "local"):
+        raise ValueError(f"sync_rule must be 'global' or 'local', not {sync_rule!r}")
+    tau = Engine.check_detect(detect_threshold)
+    return tau if sync_rule == "local" else None
+
+
 class ReceivePlan(NamedTuple):
     """What one receive call does, decided before any GPU work; everything after `plan_receive` reads these and checks nothing again."""
     chain: object                           # the CodedChain of this call
@@ -67,26 +78,30 @@ class ReceivePlan(NamedTuple):
     plots: bool
     piecewise: bool                         # the recording is taken from host memory piece by piece (Engine.receive_host)
     chunk: int                              # samples per piece
+    detect: object = None                   # the threshold of the self-normalised detection (sync_rule "local"), or None
 
 
 def plan_receive(rx, chain, lengths, plots, diversity):
     """The plan of receive() (diversity False) or receive_diversity() on recordings of `lengths` samples, from the
     receiver's attributes as they are now and its CodedChain.  Every refusal of a receive call is raised here, in this order:
     the coded chain's own (CodedChain.check_receive / check_diversity: ValueError), the values of the blanking and the
-    clock correction (ValueError), then what has no path (NotImplementedError)."""
+    clock correction and of the sync rule (ValueError), then what has no path (NotImplementedError)."""
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = not plots and bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
     if diversity:
         rate, fused, blanking = chain.check_diversity(), False, None
         clock = check_clock(rx.clock_correction, rx.clock_taps)
+        detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
         no_path = ((rx.impulse_blanking, "receive_diversity: impulse_blanking is not combined; blank each recording's samples "
                                          "with Engine.blank_impulses first"),
                    (plots, "receive_diversity: no plots; receive() one recording for them"),
-                   (piecewise, "receive_diversity: {host} combines nothing; receive shorter recordings"))
+                   (piecewise, "receive_diversity: {host} combines nothing; receive shorter recordings"),
+                   (detect and piecewise, _LOCAL))
     else:
         rate, fused = chain.check_receive()
         blanking = Engine.check_blanking(rx.blanking_threshold, rx.blanking_guard) if rx.impulse_blanking else None
         clock = check_clock(rx.clock_correction, rx.clock_taps)
+        detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
         loaded = chain.loading is not None
         no_path = ((chain.denoise and piecewise, "channel_denoising: {host} has no denoising pass; receive shorter recordings"),
                    (loaded and plots, "bit_loading: the plots draw one constellation; receive with graph_output = False"),
@@ -94,13 +109,14 @@ def plan_receive(rx, chain, lengths, plots, diversity):
                    (blanking and piecewise, "impulse_blanking: {host} has no blanking pass; receive shorter recordings"),
                    (clock and piecewise, "clock_correction: {host} has no resampling pass; receive shorter recordings"),
                    (rate is not None and piecewise, "encoding {encoding!r}: {host} has no soft-decision decoding; "
-                                                    "receive shorter recordings"))
+                                                    "receive shorter recordings"),
+                   (detect and piecewise, _LOCAL))
     for on, why in no_path:
         if on:
             raise NotImplementedError(why.format(host=_HOST, encoding=chain.encoding))
     denoise = None if chain.denoise is None else float(chain.denoise[0])       # (validated by the chain's checks above)
     return ReceivePlan(chain, rate, fused and not plots, blanking, clock, denoise, bool(plots), piecewise,
-                       int(chunk or PIECEWISE_CHUNK))
+                       int(chunk or PIECEWISE_CHUNK), detect)
 
 
 def correct_clock(eng, x, starts, clock):

@@ -393,6 +393,50 @@ int gf3_sync_decide(const gf3_ctx *ctx, const int64_t *d_idx, const double *d_va
                     const double *d_max, int64_t nz_total,
                     int64_t *d_peaks, int64_t cap, int64_t *n_peaks, void *d_work, void *stream);
 
+/*
+ * Self-normalised chirp detection: a rule of this library's own, next to the reference's (opt-in).  Where
+ * chirp_method thresholds the matched filter against the maximum of the WHOLE stream, this rule thresholds the Pearson
+ * correlation of every full window with the replica c (Lc samples, Sc = sum c, Ec = sum c^2):
+ *     V[g]   = S2[g] - S1[g]^2 / Lc                        (S1, S2: the window's sums of r and r^2)
+ *     rho[g] = (P[g] - S1[g] Sc / Lc) / sqrt((Ec - Sc^2 / Lc) V[g])         in [-1, 1], unchanged under a r + b
+ * with rho[g] = 0 where V[g] <= 2^-36 Vrun[g], Vrun[g] = the largest V over the lags <= g of the stream (exact-zero gaps,
+ * constant stretches), and rho[g] = NaN exactly where the window holds a sample that is not finite.  A lag g is detected
+ * iff rho[g] > tau and rho[g] is the largest rho over the full-window lags in (g - Lc, g + Lc), the smallest lag winning a
+ * tie.  Nothing in it looks further than Lc - 1 lags to either side, so a stream may be cut anywhere: the detections do not
+ * depend on the cut, and a terminating chirp at the very end of a stream is a detection like any other (no except-branch).
+ * Detections are reported as g - 1, the reference's zeros-index: + 2 is the packet's first sample, as after gf3_sync_stream.
+ * All three calls read the context only, so any number of threads may call them on one context at once.
+ *
+ * gf3_detect_chunk: rho of d_buf[0..n) -- a piece of the stream with Lc - 1 samples of what came before in front of it
+ * (none at the stream's start) -- on the lags [lag_lo, lag_hi) of the buffer's own full convolution (0 <= lag_lo <= lag_hi
+ * <= n+Lc-1), restricted to the full windows of the buffer, Lc-1 <= g <= n-1.  Every storage type of the context.
+ *   tau: the threshold; GF3_EINVAL unless it is a finite number inside (0, 1).  0.3 is the rule's constant.
+ *   d_vrun (device, one double): in  = Vrun behind the earlier pieces (0 before the first);  out = with this piece's lags
+ *   listed: every owned lag with rho > tau: d_idx[k] = g - 1 + lag_offset, d_rho[k] = rho[g]; ascending; *n_listed (host).
+ *   GF3_ERANGE with *n_listed = the number wanted when cap is too small: no list is written and *d_vrun keeps its value;
+ *   call again with a larger list.  (cap == 0 with no list buffers only counts.)
+ *   d_rho_all (optional, n+Lc-1 doubles): rho[g] of every owned lag at [g]; the other entries are not written.
+ *   d_work: gf3_detect_chunk_workspace_bytes(ctx, n) bytes.  Synchronises the stream (it returns a count).  The sums
+ *   have a fixed order: two calls on the same buffer give identical bytes.
+ */
+int64_t gf3_detect_chunk_workspace_bytes(const gf3_ctx *ctx, int64_t n);
+int gf3_detect_chunk(const gf3_ctx *ctx, const void *d_buf, int64_t n,
+                     int64_t lag_lo, int64_t lag_hi, int64_t lag_offset, double tau,
+                     double *d_vrun, int64_t *d_idx, double *d_rho, int64_t cap,
+                     int64_t *n_listed, double *d_rho_all_or_null, void *d_work, void *stream);
+/*
+ * gf3_detect_decide: the windowed-maximum rule on a list as gf3_detect_chunk writes it (d_idx ascending; lists of several
+ * pieces simply follow one another): entry k is a detection iff no entry within Lc - 1 of d_idx[k] has a larger rho, or
+ * the same rho at a smaller index.  Emitted are the detections whose whole neighbourhood (d_idx[k] - Lc, d_idx[k] + Lc)
+ * lies below final_below, the first index (in d_idx's numbering) that has not been through gf3_detect_chunk yet; the
+ * others are withheld until a later call knows their neighbourhood.  Pass INT64_MAX / 2 at the end of a stream.  An
+ * entry further than 2 Lc below final_below can no longer change a decision and may be dropped from the list.
+ *   d_peaks (capacity cap), *n_peaks (host), GF3_ERANGE: as gf3_sync_decide.  d_work: 64 bytes.  Synchronises the stream.
+ */
+int gf3_detect_decide(const gf3_ctx *ctx, const int64_t *d_idx, const double *d_rho, int64_t n_listed,
+                      int64_t final_below, int64_t *d_peaks, int64_t cap, int64_t *n_peaks,
+                      void *d_work, void *stream);
+
 /* tests: the fp32 screening pass alone.  d_p32 [n+Lc-1] float; d_blk [2*nblk] float: per block of *h_hop lags its
  * maximum, then the bound on |P32 - P| of its lags (nblk = ceil((n+Lc-1) / hop)) */
 int gf3_debug_stream_screen(gf3_ctx *ctx, const void *d_r, int64_t n, float *d_p32, float *d_blk,
