@@ -387,10 +387,104 @@ def make_peak_rule(OFDM):
     np.savez_compressed(os.path.join(HERE, "g11_peak_rule.npz"), **out)
 
 
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA in place of deflate: an .npz is a zip archive of .npy members, and np.load reads whatever
+    method zipfile does.  On the g12 fixtures (int16 audio, float64 spectra) it is 8 % smaller, which the nine of them need
+    to stay under their cap with the transmit probes stored in full."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            z.writestr(name + ".npy", buf.getvalue())
+
+
+STANDARD_MODES = ("A1", "A2", "A3", "B1", "B2", "B3", "C1", "C2", "C3")
+# seed offset per mode (0 everywhere: no mode needed another input to pass the asserts below)
+STANDARD_MODE_SEED = {m: 0 for m in STANDARD_MODES}
+
+
+def make_standard_modes(OFDM):
+    """One loopback per mode of the standard, the reference objects built BY NAME (OFDM.py:30-40; no reparam): two packets
+    of P = 2, D = 2 through a three-tap channel whose last echo sits at 0.8 CP, clock drift + noise on the banded modes,
+    noise alone on the full-band ones (linear-interpolation drift wrecks the carriers near Nyquist), stored as int16 PCM.
+    The reference runs on those integers as float64, so one fixture feeds int16, float32 and float64 storage with
+    identical values.  Every assert below is on the reference (and the oracle) alone: no test built on these fixtures
+    hides a failure behind a near tie."""
+    from scipy.signal import lfilter
+    F, P, D, lead, tail = 2, 2, 2, 37, 5
+    pts, bits_tbl = orc.qpsk_table()
+    known = orc.load_known_bits(os.path.join(REF, "Handouts", "random_bits.txt"), 4096)
+    total = 0
+    for i, M in enumerate(STANDARD_MODES):
+        seed = i + STANDARD_MODE_SEED[M]
+        tx = OFDM.transmitter(mode=M, encoding="None", no_pilots=P, packet_length=D)
+        rx = OFDM.receiver(mode=M, encoding="None", no_pilots=P, packet_length=D)
+        N, CP, lo, hi = int(tx.ofdm_symbol_size), int(tx.cp_length), int(tx.lowest_bin), int(tx.highest_bin)
+        assert np.array_equal(rx.known_sequence, known)
+        p = orc.RxParams(N=N, CP=CP, P=P, D=D, lo=lo, hi=hi, const_points=pts, const_bits=bits_tbl, known_bits=known)
+        assert p.Lc == tx.chirp_length and p.C == tx.data_carriers_per_symbol
+        payload = np.random.RandomState(100 + seed).randint(0, 2, F * D * p.C * p.mu)
+        np.random.seed(seed)
+        fill = np.random.choice(np.array([1 + 1j, 1 - 1j, -1 + 1j, -1 - 1j]) / np.sqrt(2),
+                                size=(p.K - p.C), replace=True)       # what random_qpsk will draw
+        np.random.seed(seed)
+        s = quiet(tx.transmit, payload)
+        # the oracle's transmitter restates the reference's clean stream
+        s2 = orc.tx_stream(payload, fill, p, lead=0, tail=0)
+        assert s2.shape == s.shape and np.abs(s2 - s).max() <= 1e-12 * np.abs(s).max(), M
+        r = np.concatenate([np.zeros(lead), s, np.zeros(tail)])
+        h = np.zeros(int(0.8 * CP) + 1)
+        h[0], h[150], h[int(0.8 * CP)] = 1.0, -0.3, 0.2
+        r = lfilter(h, 1.0, r)
+        if M.endswith("1"):
+            r = r + 0.001 * np.abs(r).max() * np.random.RandomState(7 + seed).randn(len(r))
+        else:
+            r = drift_awgn(r, 2e-5, 0.01 * np.abs(r).max() / 3, 7 + seed)
+        r16 = np.round(r * 20000.0 / np.abs(r).max()).astype(np.int16)
+        rf = r16.astype(np.float64)
+        out = ref_stages(OFDM, rx, rf)
+        assert len(out["peaks"]) == F + 1, (M, out["peaks"])
+        ber = float(np.mean(out["bits"] != payload))
+        assert ber == 0.0, (M, ber)
+        margin = float(min(np.abs(out["eq"].real).min(), np.abs(out["eq"].imag).min()))
+        assert margin >= 1e-3 * max(1.0, float(np.abs(out["eq"]).max())), (M, margin)
+        # the oracle's receiver on the same integers: peaks and bits exact, the rest at test_loopback_stages' bars
+        o = orc.receive(rf, p)
+        assert np.array_equal(np.flatnonzero(o["zeros"]), out["peaks"]) and np.array_equal(o["bits"], out["bits"]), M
+        eq_err = float(np.abs(o["eq"] - out["eq"]).max())
+        assert eq_err <= 1e-10 * max(1.0, float(np.abs(out["eq"]).max())), (M, eq_err)
+        for k in ("Hs", "He"):
+            assert np.abs(o[k] - out[k]).max() <= 1e-12 * np.abs(out[k]).max(), (M, k)
+        assert np.abs(o["slope"] - out["slope"]).max() <= 1e-13, M
+        S, Lc = p.S, p.Lc
+        path = os.path.join(HERE, f"g12_mode_{M}.npz")
+        savez_lzma(
+            path, r=r16, mode=M, payload=np.packbits(payload.astype(np.uint8)), n_payload=len(payload),
+            fill=fill, gaps=np.zeros(F, dtype=np.int64), lead=lead, tail=tail,
+            N=N, CP=CP, P=P, D=D, lo=lo, hi=hi, mu=p.mu, seed=seed, F=F,
+            const_points=pts, const_bits=bits_tbl, known_bits=known, channel=h,
+            peaks=out["peaks"], eq=out["eq"], Hs=out["Hs"], He=out["He"], slope=out["slope"],
+            bits=np.packbits(out["bits"]), n_bits=len(out["bits"]), ber=ber,
+            Hest0=out["Hest"][0, :, ::64], X0=out["X"][0, :, 1:65],
+            tx_probe=s[::97], tx_probe_sym=s[Lc + P * S: Lc + (P + 1) * S])
+        size = os.path.getsize(path)
+        total += size
+        assert size <= 600_000, (M, size)
+        print(f"g12_mode_{M}: n={len(r16)} CP={CP} band={lo}..{hi} peaks={out['peaks']} slope={out['slope']} BER={ber:.1e} "
+              f"margin={margin:.3f} eq_err={eq_err:.1e} bytes={size}")
+    assert total <= 4_500_000, total
+    print("g12 total bytes:", total)
+
+
 def main():
     OFDM = import_reference()
+    which = set(sys.argv[1:]) or {"g1", "g1b", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12"}
+    if "g12" in which:
+        make_standard_modes(OFDM)
+    if which == {"g12"}:
+        return
     make_known_bits()
-    which = set(sys.argv[1:]) or {"g1", "g1b", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11"}
     h = np.loadtxt(os.path.join(REF, "Handouts", "gr5channel.csv")).reshape(-1)
     if "g1" in which:
         make_loopback(OFDM, "g1_n1024_qpsk", 1024, 128, 2, 8, 2, 2, seed=1)

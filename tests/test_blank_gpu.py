@@ -33,12 +33,12 @@ TORCH_OF = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float
 ENGINES = {}
 
 
-def engine_of(N, CP, P, D, dtype=np.float64):
+def engine_of(N, CP, P, D, dtype=np.float64, band=(10, 200)):
     from gf3_audio_modem_amd import Engine, RxConfig
-    key = (N, CP, P, D, np.dtype(dtype))
+    key = (N, CP, P, D, np.dtype(dtype), band)
     if key not in ENGINES:
         pts, bits = orc.qpsk_table()
-        ENGINES[key] = Engine(RxConfig(N=N, CP=CP, P=P, D=D, data_bins=np.arange(10, 200), const_points=pts, const_bits=bits,
+        ENGINES[key] = Engine(RxConfig(N=N, CP=CP, P=P, D=D, data_bins=np.arange(*band), const_points=pts, const_bits=bits,
                                        known_bits=np.zeros((N // 2 - 1) * 2, np.uint8), in_dtype=TORCH_OF[np.dtype(dtype)],
                                        fit_lo=10, fit_hi=100))
     return ENGINES[key]
@@ -202,6 +202,22 @@ def test_real_symbol_length():
         put(x, starts, base, plant, f, [0, S - 1, S, 3 * S + 31, 3 * S + 32, 3 * S + 33, 4 * S - 9, 7 * S + 2000, M * S - 1])
     compare("real_S", eng, x, starts)
     compare("real_S_g64", eng, x, starts, guard=64)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.int16])
+def test_longest_prefix_symbol_length(dtype):
+    """The standard's C modes: N = 4096, CP = 1184, P = 2, D = 2, carriers 100 .. 999.  S = 5280 = 82.5 words -- every other
+    symbol starts in the middle of a word, as at S = 4320, but 15 words further on -- and M = 6: rank (M - 1) // 4 = 1."""
+    eng = engine_of(4096, 1184, 2, 2, dtype, band=(100, 1000))
+    S, M = eng.cfg.S, eng.cfg.M
+    assert (S, M, S % 64) == (5280, 6, 32)
+    x, starts, base, plant = synth(dtype, S, M, 3, seed=S + np.dtype(dtype).itemsize, lead=3, gap=11)
+    for f in range(3):
+        put(x, starts, base, plant, f, [0, S - 1, S, 3 * S + 31, 3 * S + 32, 3 * S + 33, 4 * S - 9, 5 * S + 2000, M * S - 1],
+            sign=-1 if f == 1 else 1)
+    _, counts, level, _ = compare(f"longest_S_{np.dtype(dtype).name}", eng, x, starts)
+    assert (counts.sum(axis=1) >= 9).all() and np.allclose(level[:, 0], base, atol=0.02 * np.abs(plant[0]))
+    compare(f"longest_S_g64_{np.dtype(dtype).name}", eng, x, starts, guard=64)
 
 
 # ---- storage types --------------------------------------------------------------------------------------------------

@@ -178,6 +178,56 @@ def test_demod_frames_dn_against_the_oracle(storage):
     assert "denoise_report" not in plain and not torch.equal(plain["Hs"], o["Hs"])
 
 
+# ---- the standard's longest prefix: mode C3 --------------------------------------------------------------------------
+_C3 = {}
+
+
+def c3_case():
+    """The reference-made fixture of mode C3 (N = 4096, CP = 1184, P = 2, D = 2, carriers 100 .. 999; int16 samples): its
+    channel's last echo lies 0.8 CP = 947 samples behind the direct path, a delay no prefix of the A column holds.
+    -> (p, x int16, starts, restatement of the kernel, the oracle on the restatement's pilot sums); made once."""
+    if not _C3:
+        g = load("g12_mode_C3")
+        p = params_of(g)
+        assert (p.N, p.CP, p.P, p.D, p.lo, p.hi) == (4096, 1184, 2, 2, 100, 1000) and int(np.flatnonzero(g["channel"])[-1]) == 947
+        x, starts = g["r"], np.asarray(g["peaks"][:-1]) + 2
+        _C3["case"] = (p, x, starts, DR.denoise_frames(x, starts, p.N, p.CP, p.P, p.D, p.known_symbols()), oracle_denoised(x, starts, p))
+    return _C3["case"]
+
+
+@pytest.mark.parametrize("storage", ["int16", "float32"])
+def test_longest_prefix_kernel_and_demod_against_restatement_and_oracle(storage):
+    """denoise_kernel and gf3_demod_frames_dn at S = 5280 (symbol offsets from CP = 1184), at the bars of
+    test_kernel_against_the_restatement and test_demod_frames_dn_against_the_oracle; the echo at 947 samples is a kept tap."""
+    p, x16, starts, (want, rep, plain, margin), ref = c3_case()
+    assert margin >= 1e-6 and rep[:, :, 4].all() and (np.abs(rep[:, :, 2] - 947) <= 1).all()
+    x = x16.astype(np.dtype(storage))                                # (the same values in either storage)
+    eng = engine_for(p, in_dtype=TORCH_OF[storage])
+    xt = torch.from_numpy(x).cuda()
+    psum, report = eng.denoise_pilots(xt, starts)
+    got, grep = psum.cpu().numpy(), report.cpu().numpy()
+    assert same_bytes(xt.cpu().numpy(), x)
+    np.testing.assert_array_equal(grep[:, :, 1:], rep[:, :, 1:])
+    np.testing.assert_allclose(grep[:, :, 0], rep[:, :, 0], rtol=1e-10, atol=0.0)
+    worst = max(float(np.abs(got[f, s] - want[f, s]).max() / np.abs(want[f, s]).max()) for f in range(len(starts)) for s in range(2))
+    print(f"C3 {storage}: largest |psum' - restatement| / max|row| = {worst:.2e} (bound 4e-12)")
+    assert worst <= 4e-12
+    o = eng.demod_frames(xt, starts, want=("eq", "Hs", "He", "slope", "Hest", "status"), denoise=9.0)
+    assert torch.equal(o["denoise_report"], report) and int(o["status"].item()) == 0
+    figures = {}
+    for k in ("Hs", "He", "eq", "Hest"):
+        figures[k] = float(np.abs(o[k].cpu().numpy().reshape(ref[k].shape) - ref[k]).max() / np.abs(ref[k]).max())
+    figures["slope"] = float(np.abs(o["slope"].cpu().numpy() - ref["slope"]).max())
+    print(f"C3 {storage}: largest differences from the oracle {figures}")
+    assert figures["Hs"] <= 1e-11 and figures["He"] <= 1e-11 and figures["slope"] <= 1e-11
+    assert figures["eq"] <= 1e-12 and figures["Hest"] <= 1e-12
+    bits = eng.unpack_bits(o["bits"]).cpu().numpy()
+    sure = off_ties(ref["eq"])
+    assert sure.mean() > 0.999 and np.array_equal(bits[sure], ref["bits"][sure])
+    lean = eng.demod_frames(xt, starts, denoise=9.0)
+    assert torch.equal(lean["bits"], o["bits"]) and torch.equal(lean["denoise_report"], report)
+
+
 # ---- the two-phase form without the denoiser: what it gave before the feature ----------------------------------------
 def test_split_path_without_denoise_is_what_it_was():
     """SHA-256 of every output of demod_frames(split=True) on the g1 loop-back fixture, recorded from the commit before the

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import gf3_oracle as orc
-from tests.util import LOOPBACKS, load, modeA2_params, params_of, unpack
+from tests.util import LOOPBACKS, STANDARD_MODES, load, load_mode, modeA2_params, params_of, unpack
 
 
 @pytest.mark.parametrize("name", LOOPBACKS)
@@ -25,6 +25,33 @@ def test_loopback_stages(name):
     assert np.abs(out["eq"] - g["eq"]).max() <= 1e-10 * scale
     np.testing.assert_allclose(out["Hest"][0, :, ::64], g["Hest0"], rtol=1e-11, atol=1e-13)
     np.testing.assert_allclose(out["X"][0, :, 1:65], g["X0"], rtol=0, atol=1e-12 * np.abs(g["X0"]).max())
+
+
+@pytest.mark.parametrize("mode", STANDARD_MODES)
+def test_standard_mode_stages(mode):
+    """The nine modes of the standard, built by name in the reference (g12): every stage of the oracle at the bars of
+    test_loopback_stages, on the int16 samples as float64; the parameter block is the mode's own (N = 4096, the prefix
+    and band of OFDM.py:30-40); the oracle's transmitter rebuilds the probed samples of the reference's clean stream."""
+    g = load_mode(mode)
+    p = params_of(g)
+    assert (p.N, p.CP) == (4096, {"A": 224, "B": 704, "C": 1184}[mode[0]])
+    assert (p.lo, p.hi) == {"1": (1, 2047), "2": (100, 1500), "3": (100, 1000)}[mode[1]] and p.Lc == 5 * (4096 + p.CP)
+    assert g["r"].dtype == np.int16
+    out = orc.receive(g["r"].astype(np.float64), p)
+    assert np.array_equal(np.flatnonzero(out["zeros"]), g["peaks"]) and len(g["peaks"]) == int(g["F"]) + 1
+    assert np.array_equal(out["bits"], unpack(g)) and np.array_equal(out["bits"], unpack(g, "payload", "n_payload"))
+    np.testing.assert_allclose(out["Hs"], g["Hs"], rtol=0, atol=1e-12 * np.abs(g["Hs"]).max())
+    np.testing.assert_allclose(out["He"], g["He"], rtol=0, atol=1e-12 * np.abs(g["He"]).max())
+    np.testing.assert_allclose(out["slope"], g["slope"], rtol=0, atol=1e-13)
+    scale = max(1.0, float(np.abs(g["eq"]).max()))
+    assert np.abs(out["eq"] - g["eq"]).max() <= 1e-10 * scale
+    np.testing.assert_allclose(out["Hest"][0, :, ::64], g["Hest0"], rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(out["X"][0, :, 1:65], g["X0"], rtol=0, atol=1e-12 * np.abs(g["X0"]).max())
+    s = orc.tx_stream(unpack(g, "payload", "n_payload"), g["fill"], p, lead=0, tail=0)
+    amp = np.abs(g["tx_probe"]).max()
+    assert np.abs(s[::97] - g["tx_probe"]).max() <= 1e-12 * amp
+    o = p.Lc + p.P * p.S
+    assert np.abs(s[o: o + p.S] - g["tx_probe_sym"]).max() <= 1e-12 * amp
 
 
 @pytest.mark.parametrize("name", LOOPBACKS)

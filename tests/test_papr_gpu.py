@@ -34,6 +34,8 @@ def _params(name):
         return small_params(carriers=np.delete(np.arange(1, 512), 199)), F_SMALL
     import dataclasses
     a2 = dataclasses.replace(modeA2_params(load("g6_realrec")["known_bits"]), P=1, D=4)
+    if name == "c3_qpsk":                                                # the standard's longest prefix and narrowest band: S = 5280,
+        return dataclasses.replace(a2, CP=1184, hi=1000, P=2, D=2), 2    # Ku = 1147 reserved tones against C = 900 data carriers
     if name == "a2_qpsk":
         return a2, 2
     pts, bt = orc.square_qam_table(4)
@@ -57,7 +59,7 @@ def same_bytes(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
-NAMES = ["contig", "scattered", "one_tone", "a2_qpsk", "a2_qam16"]
+NAMES = ["contig", "scattered", "one_tone", "a2_qpsk", "a2_qam16", "c3_qpsk"]
 
 
 # ---- 1. against the restatement, 4. the peak report, 5. determinism -----------------------------------------------------
@@ -97,7 +99,7 @@ def test_kernel_against_the_restatement(name, iterations):
 
 
 # ---- 2. the receiver is unaffected, 3. the untouched parts -------------------------------------------------------------
-@pytest.mark.parametrize("name", ["contig", "scattered", "a2_qam16"])
+@pytest.mark.parametrize("name", ["contig", "scattered", "a2_qam16", "c3_qpsk"])
 def test_receiver_unaffected_and_untouched_parts(name):
     p, F, packed, _, eng = case(name)
     rs = np.random.RandomState(len(name))

@@ -99,6 +99,50 @@ def test_kernel_against_the_restatement(dtype, T, which):
             assert np.array_equal(out[f].view(np.uint8), x[STARTS[f]: STARTS[f] + N_BODY].view(np.uint8))
 
 
+LONG = {}
+
+
+def longest_prefix_case(dtype):
+    """The standard's C modes with short packets: N = 4096, CP = 1184, P = 2, D = 2, carriers 100 .. 999.  A body has
+    M S = 6 x 5280 = 31 680 samples: 30 tiles of 1024 outputs and a last one of 960 (exactly 15 waves, where the small shape's
+    last tile ends inside a wave); at the caps the read position drifts 63 samples over a body instead of 9.  The same four
+    packets as above.  -> (engine, x, starts, body), made once per storage type."""
+    key = np.dtype(dtype)
+    if key not in LONG:
+        from gf3_audio_modem_amd import Engine, RxConfig
+        pts, bits = orc.qpsk_table()
+        eng = Engine(RxConfig(N=4096, CP=1184, P=2, D=2, data_bins=np.arange(100, 1000), const_points=pts, const_bits=bits,
+                              known_bits=np.zeros(4094, np.uint8), in_dtype=TORCH_OF[key]))
+        body = eng.cfg.M * eng.cfg.S
+        assert body == 31680 and body % 1024 == 960
+        starts = np.array([3, 3 + body + 17, 3 + 2 * body + 46, 3 + 2 * body + 47])
+        rng = np.random.default_rng(5280)
+        n = 3 + 3 * body + 46
+        x = rng.normal(0.0, 3.0, n).astype(key) if key.kind == "f" else rng.integers(-10000, 10001, n).astype(key)
+        LONG[key] = (eng, x, starts, body)
+    return LONG[key]
+
+
+@pytest.mark.parametrize("T", [16, 32])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int16])
+def test_kernel_at_the_longest_prefix(dtype, T):
+    """The comparison of test_kernel_against_the_restatement, at its tolerances, on bodies of 31 680 samples; float64 is the
+    storage in which the call emits what it computed, unrounded."""
+    eng, x, starts, body = longest_prefix_case(dtype)
+    eps = np.array([-2e-3, -50e-6, 2e-3, 1e-6])
+    rows, raw, status = RR.resample_rows(x, starts, body, eps, T)
+    xt = torch.from_numpy(x).cuda()
+    out, off, st = eng.resample_frames(xt, starts, eps, half_taps=T)
+    assert out.dtype == xt.dtype and tuple(out.shape) == (4, body) and off.tolist() == [0, body, 2 * body, 3 * body]
+    assert st.cpu().numpy().tolist() == status.tolist() == [0, 0, 0, 1]
+    assert np.array_equal(xt.cpu().numpy().view(np.uint8), x.view(np.uint8))
+    out = out.cpu().numpy()
+    err, bound = check(out, rows, raw, x)
+    print(f"longest prefix, {np.dtype(dtype).name} T {T}: largest error {err:.3e} (bound {bound:.3e})")
+    assert err <= bound
+    assert not out[3].any()
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32, np.int16, np.uint8])
 def test_zero_offset_returns_the_bodies_and_two_runs_agree(dtype):
     eng = engine_of(dtype)

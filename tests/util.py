@@ -44,3 +44,10 @@ def engine_for(p, in_dtype=None, **kw):
 
 LOOPBACKS = ["g1_n1024_qpsk", "g2_n4096_qpsk", "g3_n4096_16qam_gr5",
              "g7_n4096_qpsk_drift", "g8_n4096_qpsk_gr5_drift"]
+
+STANDARD_MODES = ["A1", "A2", "A3", "B1", "B2", "B3", "C1", "C2", "C3"]
+
+
+def load_mode(mode):
+    """The reference-made fixture of one standard mode (tests/golden/make_golden.py: make_standard_modes)."""
+    return load("g12_mode_" + mode)
