@@ -52,7 +52,7 @@ def _tables():
     t["qam16_scaled_axes"] = _grid(0.4 * lv4 + 0.3, 0.2 * lv4, GRAY4, GRAY4, 2)
     lvu = 0.3 * np.array([-3.0, -1.0, 1.0, 4.0])
     t["qam16_unequal"] = _grid(lvu, lvu, GRAY4, GRAY4, 2)        # separable, unequal level spacing: `sep` accepted, `ug` refused -> scan
-    p16 = orc.square_qam_table(4)[0]
+    p16, p16_bits = orc.square_qam_table(4)
     t["qam16_nonsep"] = (p16, _bits_of(np.random.RandomState(16).permutation(16), 4))     # grid points, labels of no axis -> scan
     t["psk8"] = (np.exp(2j * np.pi * np.arange(8) / 8), _bits_of(np.arange(8) ^ (np.arange(8) >> 1), 3))      # no grid -> scan, mu = 3
     t["ring8"] = (np.exp(2j * np.pi * (np.arange(8) + 0.25) / 8) * (1.0 + 0.3 * (np.arange(8) % 2)), _bits_of(np.arange(8), 3))   # two rings -> scan
@@ -64,6 +64,14 @@ def _tables():
     # only: it is kept out of the soft-decision tests (SOFT_TABLES).  (Any three distinct 2-bit labels show both values
     # of both bits, so the oracle's max-log formula has no empty set here; the exclusion is one of scope, not of need.)
     t["tri3"] = (np.array([1.0, np.exp(2j * np.pi / 3), np.exp(-2j * np.pi / 3)]), _bits_of([0, 1, 3], 2))
+    # mu = 8, the widest label gf3_ctx_create accepts, on 16 points: the square 16-QAM with each 4-bit label repeated in both
+    # nibbles.  Uniform grid -> per-axis fast path of the fused kernel with full 8-bit axis labels (0xcc / 0x33 masks);
+    # hI + hQ = 4 != mu, so every soft path takes the literal "any table" emitter with all of its float[8] valid
+    lab16 = (p16_bits * (1 << np.arange(3, -1, -1))).sum(axis=1)
+    t["grid16_mu8"] = (p16, _bits_of(lab16 * 17, 8))
+    # mu = 7 on ring8's points (no grid -> scan): labels (i << 4) | ((7 - i) << 1) | (i & 1), every bit takes both values
+    i8 = np.arange(8)
+    t["ring8_mu7"] = (t["ring8"][0], _bits_of((i8 << 4) | ((7 - i8) << 1) | (i8 & 1), 7))
     return t
 
 
@@ -71,7 +79,8 @@ TABLES = _tables()
 SOFT_TABLES = [k for k in TABLES if k != "tri3"]
 EXPECTED_CLASS = dict(qpsk_ref="qpsk", qpsk_reordered="uniform", qpsk_relabelled="scan", qpsk_rot="scan", bpsk="sep",
                       pam4x1="sep", rect8="uniform", qam16_scaled_axes="uniform", qam16_unequal="sep", qam16_nonsep="scan",
-                      psk8="scan", ring8="scan", cross32="scan", qam64="uniform", tri3="scan")
+                      psk8="scan", ring8="scan", cross32="scan", qam64="uniform", tri3="scan", grid16_mu8="uniform",
+                      ring8_mu7="scan")
 
 
 def classify(points, bits):
@@ -213,6 +222,13 @@ CASES = [
     ("cross32",           "shuffled",     2048, 2, 3,  2, "float64"),     # mu = 5
     ("cross32",           "single_top",   4096, 2, 13, 2, "float64"),     # 5 bits per symbol, D C mu = 65
     ("tri3",              "two_bands",    1024, 2, 3,  2, "float64"),     # M < 2^mu
+    # (appended: demod_case seeds by index, other files look rows up by index and id)
+    ("grid16_mu8",        "shuffled",     1024, 2, 3,  2, "float64"),     # mu = 8: whole bytes per label
+    ("grid16_mu8",        "two_bands",    4096, 2, 3,  2, "float32"),
+    ("grid16_mu8",        "single_top",   1024, 2, 13, 2, "float64"),     # D C mu = 104: no multiple of 32 (of 8 it always is)
+    ("ring8_mu7",         "comb2",        2048, 2, 3,  2, "float64"),     # mu = 7: labels straddle bytes and words
+    ("ring8_mu7",         "all_reversed", 1024, 1, 3,  2, "float64"),     # C mu = 3577 odd, D C mu = 10731, P = 1
+    ("ring8_mu7",         "single_top",   2048, 2, 13, 2, "float64"),     # D C mu = 91
 ]
 CASE_IDS = [f"{t}-{m}-{N}-P{P}-D{D}-{st}" for t, m, N, P, D, F, st in CASES]
 NOISE_REL = 0.01                                                   # white noise, fraction of the stream's rms
@@ -251,7 +267,8 @@ def decision_gap(eq, points):
     return float((d[:, 1] - d[:, 0]).min())
 
 
-NEAR_TIE_TABLES = ["psk8", "ring8", "cross32", "rect8", "qam16_unequal", "qam16_scaled_axes", "bpsk", "pam4x1"]
+NEAR_TIE_TABLES = ["psk8", "ring8", "cross32", "rect8", "qam16_unequal", "qam16_scaled_axes", "bpsk", "pam4x1", "grid16_mu8",
+                   "ring8_mu7"]
 # Tables on whose near-tie symbols a squared-distance argmin and the reference's argmin(abs(.)) differ somewhere.  For bpsk
 # they cannot: its one boundary is Re = 0, and a symbol within a few ulp (of zero: denormals) or 1e-13 of it is at exactly
 # the same rounded distance from +1 and -1 in either form, or on the same side in both.

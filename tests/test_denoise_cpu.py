@@ -77,6 +77,18 @@ def test_ragged_packet_is_a_zero_row():
     assert not out[1].any() and not plain[1].any() and rep[1].tolist() == [[0, 0, -1, 0, 0]] * 2
 
 
+@pytest.mark.parametrize("N", [1024, 2048, 4096, 8192])
+def test_kernel_cases_keep_clear_of_the_threshold(N):
+    """The condition under which tests/test_denoise_gpu.py compares keep decisions as integers, by the restatement alone:
+    no tap of any kernel case (P in 2, 3, 9; four sample storages) lies within 1e-6 (relative) of the keep threshold."""
+    for P in (2, 3, 9):
+        for dtype in ("float64", "float32", "int16", "uint8"):
+            p, x, starts = DR.kernel_case(N, P, dtype, seed=N + P)
+            margin = DR.denoise_frames(x, starts, p.N, p.CP, p.P, p.D, p.known_symbols())[3]
+            print(f"N {N} {dtype} P {P}: nearest tap to the threshold {margin:.1e}")
+            assert margin >= 1e-6, (P, dtype)
+
+
 def test_delay_spread_of_a_planted_channel():
     """One causal tap at 17 and one precursor at N - 3, of opposite signs (both odd: no response at DC and Nyquist); 5 sigma,
     so that no noise tap survives (1024 taps x 5.7e-7)."""

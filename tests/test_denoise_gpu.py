@@ -5,7 +5,8 @@ recorded before the feature, the façade end to end, and the real recording.
 Tolerance of psum'.  The kernel runs four fp64 transforms; one is held to 1e-12 of the row's maximum (test_rfft_batch), so
 |psum' - restatement| <= 4e-12 max|row|.  The keep decisions are compared as integers: the test first asserts, with the
 restatement alone, that no tap of its inputs lies within 1e-6 (relative) of the threshold, six orders above the rounding
-of either side.  v to 1e-10 relative (two summation orders of ~1e4 .. 1e5 squares: ~1e-14)."""
+of either side.  v to 1e-10 relative (two summation orders of ~1e4 .. 1e5 squares: ~1e-14).  Measured on the MI355X at
+N = 2048 and 4096 (all four storages, P = 2, 3, 9): |psum' - restatement| / max|row| 6.0e-16 .. 1.7e-15."""
 import dataclasses
 import hashlib
 import json
@@ -41,7 +42,7 @@ def same_bytes(a, b):
 
 @pytest.mark.parametrize("P", [2, 3, 9])
 @pytest.mark.parametrize("dtype", ["float64", "float32", "int16", "uint8"])
-@pytest.mark.parametrize("N", [1024, 8192])
+@pytest.mark.parametrize("N", [1024, 2048, 4096, 8192])                # every denoise_kernel<NC, DT> of the dispatch
 def test_kernel_against_the_restatement(N, dtype, P):
     p, x, starts, (want, rep, plain, margin), eng = case(N, P, dtype)
     print(f"N {N} {dtype} P {P}: nearest tap to the threshold {margin:.1e}")

@@ -51,6 +51,10 @@ def case(name):
             x = np.round(128 + 40 * x).astype(np.uint8)
         elif name == "i16":
             x = np.round(20000 * x).astype(np.int16)
+        elif name in ("f32", "f32_nan"):                        # the DT_F32 kernels, and det_clean_kernel<float> behind a NaN
+            x = x.astype(np.float32)
+            if name == "f32_nan":
+                x[LEAD + FRAME + LC + 2000] = np.nan
         elif name == "zeros":
             x, want = stream(lead=45000, gaps=[0, 3 * LC, 0])
         elif name == "nan":
@@ -66,7 +70,8 @@ _engines = {}
 
 
 def eng_for(x):
-    dt = {np.dtype("float64"): torch.float64, np.dtype("uint8"): torch.uint8, np.dtype("int16"): torch.int16}[x.dtype]
+    dt = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32, np.dtype("uint8"): torch.uint8,
+          np.dtype("int16"): torch.int16}[x.dtype]
     if dt not in _engines:
         _engines[dt] = engine_for(P_, in_dtype=dt)
     return _engines[dt]
@@ -82,7 +87,7 @@ def agree(got, q, V, bound, least=3 * FRAME):
     return err
 
 
-@pytest.mark.parametrize("name", ["clean", "awgn", "u8", "i16", "zeros", "nan"])
+@pytest.mark.parametrize("name", ["clean", "awgn", "u8", "i16", "zeros", "nan", "f32", "f32_nan"])
 def test_rho_and_detections_match_the_restatement(name):
     x, want, q, V = case(name)
     eng = eng_for(x)
@@ -102,7 +107,7 @@ def test_rho_and_detections_match_the_restatement(name):
         g = np.arange(LC - 1, len(r))
         silent = g[csum[g + 1] - csum[g - LC + 1] == 0]
         assert len(silent) > 45000 - LC + 2 * LC and np.all(got[silent] == 0.0) and np.all(q[silent] == 0.0)
-    if name == "nan":
+    if name in ("nan", "f32_nan"):
         assert np.isnan(got).sum() == LC
 
 
@@ -257,7 +262,8 @@ class Geo:
         return self.cases[name]
 
     def eng_for(self, x):
-        dt = {np.dtype("float64"): torch.float64, np.dtype("uint8"): torch.uint8, np.dtype("int16"): torch.int16}[x.dtype]
+        dt = {np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32, np.dtype("uint8"): torch.uint8,
+          np.dtype("int16"): torch.int16}[x.dtype]
         if dt not in self.engines:
             self.engines[dt] = engine_for(self.p, in_dtype=dt)
         return self.engines[dt]

@@ -78,14 +78,16 @@ def table_of(kind):
         return pts, bits[:, ::-1].copy()
     if kind == "ring8":
         return T.TABLES["ring8"]
-    return {"qpsk": orc.qpsk_table, "qam16": lambda: orc.square_qam_table(4), "qam64": lambda: orc.square_qam_table(6)}[kind]()
+    return {"qpsk": orc.qpsk_table, "qam4_binary": lambda: orc.square_qam_table(2), "qam16": lambda: orc.square_qam_table(4), "qam64": lambda: orc.square_qam_table(6)}[kind]()
 
 
 @pytest.mark.parametrize("kind,carriers", [("qpsk", None), ("qam16", None), ("qam64", None), ("qam16_reversed_labels", None),
-                                           ("ring8", None), ("qam16", "shuffled")])
+                                           ("ring8", None), ("qam16", "shuffled"), ("qam4_binary", None)])
 def test_kernel_matches_restatement(kind, carriers):
-    """B = 1 .. 4 in both modes: the three straight-line grid kernels, a grid with reversed labels and a table that is no
-    grid (the table-generic path), and 16-QAM on a scattered carrier map (the csi weights go through the carriers' bins)."""
+    """B = 1 .. 4 in both modes: the three straight-line grid kernels (HI = 1: the binary-indexed 4-point grid, not the
+    reference's QPSK, whose first label bit belongs to the Q axis and which takes the table-generic path), a grid with
+    reversed labels and a table that is no grid (the table-generic path), and 16-QAM on a scattered carrier map (the csi
+    weights go through the carriers' bins)."""
     pts, bits = table_of(kind)
     p = small_params(pts, bits, carriers=None if carriers is None else T.MAPS[carriers](511))
     eng = engine_of(p)

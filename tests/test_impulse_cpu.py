@@ -87,6 +87,91 @@ def test_interleaver_and_symbol_weights_only_work_as_a_pair(rate, sigma, sigma_b
         assert inter_cs == 0
 
 
+# ---- the cases of tests/test_impulse_gpu.py::test_carrier_counts and ::test_every_arm_of_the_estimate -----------------
+# launch_noise_cs turns C into NCG = 4, 8, 12 or 16 (the least of them >= ncg = (ceil(C / 64) + 1) // 2) and the table class
+# into HI = 0 .. 3: sixteen kernels.  COUNTS sits on every boundary of that rule, on odd column counts and on one column.
+COUNTS = [1, 64, 65, 129, 512, 513, 1024, 1025, 1536, 1537, 2047, 2048]
+# HI = 0, 0, 1, 2, 3.  The reference's QPSK carries its FIRST label bit on the Q axis, so it is no binary-indexed grid in the
+# sense of sep_is_binary (csrc/gf3rx_demap.h) and takes HI = 0 with the per-axis branch of the "any table" emitter; ring8
+# takes HI = 0 with the literal scan; the binary-indexed 4-point grid (oracle.square_qam_table(2)) is what selects HI = 1.
+ARM_TABLES = ["ring8", "qpsk_ref", "qam4", "qam16", "qam64"]
+ARM_COUNTS = [65, 513, 1025, 1537]                                     # NCG = 4, 8, 12, 16
+D_SMALL, F_SMALL = 3, 2
+
+
+def arm_table(name):
+    from tests import tables as T
+    return orc.square_qam_table({"qam4": 2, "qam16": 4}[name]) if name in ("qam4", "qam16") else T.TABLES[name]
+
+
+def ncg_arm(C):
+    """The NCG template argument launch_noise_cs picks (None: refused)."""
+    ncg = (-(-C // 64) + 1) // 2
+    return next((a for a in (4, 8, 12, 16) if ncg <= a), None)
+
+
+def grid_bits(points, bits):
+    """grid_bits of csrc/gf3rx_demap.h restated: h for a 2^h x 2^h grid (h <= 3) whose first h label bits are the binary
+    index of the I level and whose last h bits that of the Q level, levels numbered in order of appearance; else 0."""
+    points, bits = np.asarray(points, dtype=complex), np.asarray(bits)
+    M, mu = bits.shape
+    li, lq = list(dict.fromkeys(points.real)), list(dict.fromkeys(points.imag))
+    h = mu // 2
+    if mu % 2 or h > 3 or len(li) != 1 << h or len(lq) != 1 << h or M != 1 << mu or len(set(points.tolist())) != M:
+        return 0
+    lab = (bits * (1 << np.arange(mu - 1, -1, -1))).sum(axis=1)
+    want = [(li.index(z.real) << h) | lq.index(z.imag) for z in points]
+    return h if lab.tolist() == want else 0
+
+
+def count_case(table, C, scattered=False):
+    """-> (parameter block, eq [F D, C]): points of the table plus noise whose level differs from carrier to carrier, with
+    one symbol in five three times louder.  N = 4096 while the carriers fit, the top C bins or C bins drawn at random."""
+    from tests import tables as T
+    pts, bits = arm_table(table)
+    N = 4096 if C <= 2047 else 8192
+    K = N // 2 - 1
+    bins = np.random.default_rng(C).permutation(K)[:C] + 1 if scattered else np.arange(K - C, K) + 1
+    p = T.params_for((pts, bits), N, bins, P=1, D=D_SMALL, CP=0)
+    rng = np.random.default_rng(1000 * len(pts) + C)
+    idx = rng.integers(0, len(pts), size=(F_SMALL * D_SMALL, C))
+    dmin = np.abs(pts[:, None] - pts[None, :])[np.triu_indices(len(pts), 1)].min()
+    sig = dmin * (0.05 + 0.15 * rng.random(C)) * (1.0 + 2.0 * (rng.random((F_SMALL * D_SMALL, 1)) < 0.2))
+    return p, pts[idx] + (rng.normal(size=idx.shape) + 1j * rng.normal(size=idx.shape)) * sig
+
+
+def arm_cases():
+    """(table, C, scattered): every (HI, NCG) pair, a scattered map at least once per NCG and per table."""
+    return [(t, C, i % 4 == j) for i, t in enumerate(ARM_TABLES) for j, C in enumerate(ARM_COUNTS)]
+
+
+def test_the_arm_cases_select_all_sixteen_kernels():
+    assert [grid_bits(*arm_table(t)) for t in ARM_TABLES] == [0, 0, 1, 2, 3]
+    assert [ncg_arm(C) for C in ARM_COUNTS] == [4, 8, 12, 16]
+    arms = {(grid_bits(*arm_table(t)), ncg_arm(C)) for t, C, _ in arm_cases()}
+    assert len(arms) == 16 and {ncg_arm(C) for t, C, s in arm_cases() if s} == {4, 8, 12, 16}
+    # COUNTS: both sides of every boundary of the rule, the last accepted count, the first refused one
+    assert [ncg_arm(C) for C in COUNTS] == [4, 4, 4, 4, 4, 8, 8, 12, 12, 16, 16, 16] and ncg_arm(2049) is None
+    assert {-(-C // 64) % 2 for C in COUNTS} == {0, 1}                 # odd column counts: the second half is one column short
+
+
+@pytest.mark.parametrize("C", COUNTS)
+def test_count_cases_are_neither_flat_nor_erased(C):
+    """What the GPU test's comparison rests on, by the restatement alone: every variance is finite and positive (no packet
+    takes the flat rule, no weight is an erasure or the floor's), and every LLR of the reference is finite."""
+    tables = ["qpsk_ref"] + ([t for t, c, _ in arm_cases() if c == C] if C in ARM_COUNTS else [])
+    for table in dict.fromkeys(tables):
+        for scattered in {False} | {s for t, c, s in arm_cases() if (t, c) == (table, C)}:
+            p, eq = count_case(table, C, scattered)
+            assert eq.shape == (F_SMALL * D_SMALL, C) and p.C == C and p.D == D_SMALL
+            v_c, v_s = IR.noise_estimate2(eq, p.const_points, p.D)
+            assert np.isfinite(v_c).all() and np.isfinite(v_s).all() and v_c.min() > 0 and v_s.min() > 0
+            # (one carrier: v_c v_s / vbar = v_s, so the floor could bind only below 1e-6 of the packet's mean)
+            x = v_c[:, None, :] * v_s[:, :, None] / v_c.mean(axis=1)[:, None, None]
+            assert (x > 1e-6 * v_c.mean(axis=1)[:, None, None]).all()
+            assert np.isfinite(IR.soft_demap_nw2(eq, v_c, v_s, p.const_points, p.const_bits)).all()
+
+
 def test_nan_symbol_erases_that_symbol_only_and_a_noiseless_packet_gets_weight_one():
     rng = np.random.default_rng(4)
     Dn, Cn = 6, 40

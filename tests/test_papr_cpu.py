@@ -21,6 +21,49 @@ def scattered():
     return np.concatenate([np.arange(25, 376, 3), np.arange(400, 460)])
 
 
+# Geometries that select the kernel instantiations and label widths the first six cases of tests/test_papr_gpu.py leave
+# out: papr_kernel<1024> (N = 2048), papr_kernel<4096> (N = 8192, the arm with more than 64 KiB of dynamic LDS), and labels
+# of 1, 3, 5, 7 and 8 bits through the kernel's own three-byte window (every width but 1 and 8 straddles bytes).
+WIDTH_TABLES = ["bpsk", "psk8", "cross32", "ring8_mu7", "grid16_mu8"]
+MORE_GEOMETRIES = ["n2048_contig", "n2048_scattered", "n8192_contig"] + WIDTH_TABLES
+
+
+def more_params(name):
+    """-> (parameters, packets) of one of MORE_GEOMETRIES."""
+    from tests import tables as T
+    if name == "n2048_contig":
+        return T.params_for("qpsk_ref", 2048, np.arange(25, 700), P=1, D=3, CP=120), 3
+    if name == "n2048_scattered":                                        # every third carrier and a block above them
+        return T.params_for("qpsk_ref", 2048, np.concatenate([np.arange(25, 700, 3), np.arange(800, 900)]), P=1, D=3, CP=120), 3
+    if name == "n8192_contig":
+        return T.params_for("qpsk_ref", 8192, np.arange(100, 3000), P=1, D=2, CP=480), 2
+    return T.params_for(name, 1024, np.arange(25, 376), P=1, D=3, CP=56), 3
+
+
+def payload_bits(name, p, F):
+    """The seed rule of tests/test_papr_gpu.py::case.  A table with fewer points than labels draws among the labels it
+    carries (the oracle's mapper and tx_kernel differ, on purpose, on a label that no point carries)."""
+    rng = np.random.default_rng(len(name) + 100)
+    if len(p.const_points) < 1 << p.mu:
+        return p.const_bits[rng.integers(0, len(p.const_points), size=F * p.D * p.C)].reshape(-1)
+    return rng.integers(0, 2, size=F * p.D * p.C * p.mu)
+
+
+@pytest.mark.parametrize("name", MORE_GEOMETRIES)
+def test_more_geometries_leave_no_ties(name):
+    """The condition under which tests/test_papr_gpu.py compares the best index as an integer: at most 1 % of the symbols
+    have their two smallest iterate peaks within 1e-9 of each other, at I = 16 and I = 3, by the restatement alone."""
+    p, F = more_params(name)
+    bits = payload_bits(name, p, F)
+    for iterations in (16, 3):
+        tones, rep, peaks = PR.tone_reserve(bits, p, 6.0, 6.0, iterations)
+        share = float(np.mean([PR.near_tie(q) for q in peaks]))
+        print(f"{name} I={iterations}: N {p.N} C {p.C} mu {p.mu}: share of ties {share}, mean peak {rep[..., 0].mean():.4f} -> "
+              f"{rep[..., 1].mean():.4f}, best index mean {rep[..., 2].mean():.1f}")
+        assert tones.shape == (F, p.D, p.K - p.C) and share <= 0.01
+        assert (rep[..., 2] > 0).any()                                   # (the iteration runs: some symbol is clipped)
+
+
 @pytest.mark.parametrize("name", ["contig", "scattered"])
 def test_restatement_properties(name):
     p = small_params() if name == "contig" else small_params(carriers=scattered())

@@ -7,7 +7,10 @@ once per iteration (the map from one iterate to the next is continuous in its in
 transform away from its tones, and a deviation d on one tone moves a sample by at most 2 d / N, so
 (I + 1) x 1e-12 x peak + 2 Ku / N x the tones' atol.  The best index is compared as an integer: the restatement's two
 smallest iterate peaks must not lie within 1e-9 (relative) of each other on more than 1 % of the symbols; the seeds below
-leave none.  Measured on the MI355X: tones 8.5e-16 .. 2.6e-14, peaks and rms within 3e-4 of their bound."""
+leave none.  Measured on the MI355X: tones 8.5e-16 .. 2.6e-14, peaks and rms within 3e-4 of their bound; on
+the cases of MORE_GEOMETRIES (N = 2048 and 8192, labels of 1, 3, 5, 7 and 8 bits; the same bounds, N = 8192 inside the
+1e-12 that test_rfft_batch grants a transform up to that size): tones 7.7e-16 .. 6.6e-15, peaks and rms within 5e-5 of their
+bound."""
 import contextlib
 import io
 
@@ -17,7 +20,7 @@ import torch
 
 from oracle import gf3_oracle as orc
 from tests import papr_ref as PR
-from tests.test_papr_cpu import scattered, small_params
+from tests.test_papr_cpu import MORE_GEOMETRIES, more_params, payload_bits, scattered, small_params
 from tests.util import engine_for, load, modeA2_params
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +29,8 @@ F_SMALL = 3
 
 
 def _params(name):
+    if name in MORE_GEOMETRIES:
+        return more_params(name)
     if name == "contig":
         return small_params(), F_SMALL
     if name == "scattered":
@@ -48,7 +53,7 @@ def case(name, iterations=16):
     key = (name, iterations)
     if key not in CASES:
         p, F = _params(name)
-        bits = np.random.default_rng(len(name) + 100).integers(0, 2, size=F * p.D * p.C * p.mu)
+        bits = payload_bits(name, p, F)
         ref = PR.tone_reserve(bits, p, 6.0, 6.0, iterations)
         eng = CASES[(name, 16)][4] if (name, 16) in CASES else engine_for(p, max_window=256)
         CASES[key] = (p, F, orc.pack_bits(bits, p.D * p.C * p.mu), ref, eng)
@@ -59,7 +64,8 @@ def same_bytes(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
-NAMES = ["contig", "scattered", "one_tone", "a2_qpsk", "a2_qam16", "c3_qpsk"]
+# (MORE_GEOMETRIES: papr_kernel<1024> at N = 2048, papr_kernel<4096> at N = 8192, labels of 1, 3, 5, 7 and 8 bits)
+NAMES = ["contig", "scattered", "one_tone", "a2_qpsk", "a2_qam16", "c3_qpsk"] + MORE_GEOMETRIES
 
 
 # ---- 1. against the restatement, 4. the peak report, 5. determinism -----------------------------------------------------
@@ -99,7 +105,7 @@ def test_kernel_against_the_restatement(name, iterations):
 
 
 # ---- 2. the receiver is unaffected, 3. the untouched parts -------------------------------------------------------------
-@pytest.mark.parametrize("name", ["contig", "scattered", "a2_qam16", "c3_qpsk"])
+@pytest.mark.parametrize("name", ["contig", "scattered", "a2_qam16", "c3_qpsk", "n2048_contig", "n2048_scattered", "n8192_contig"])
 def test_receiver_unaffected_and_untouched_parts(name):
     p, F, packed, _, eng = case(name)
     rs = np.random.RandomState(len(name))

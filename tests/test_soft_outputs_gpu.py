@@ -10,7 +10,10 @@ twice, in two processes, and every item came out the same in both: all of them a
 Contexts: tests.tables.params_for(table, 1024, carriers, P=2, D=9) -- D = 9 is no multiple of the 8 symbol phases -- for
 C = 70 (descending bins: one partial 64-wide column, one partial 256-tile) and C = 300 (ascending: a strided second pass of
 the 256-thread loops, five columns for the two halves of noise_estimate_cs), on one table per arm of the table dispatch:
-qpsk_ref (HI 1), square 16-QAM (HI 2), qam64 (HI 3), psk8 (literal scan), rect8 (separable, not square).
+qpsk_ref (separable, its first label bit on the Q axis: the per-axis scan, HI 0), square 16-QAM (HI 2), qam64 (HI 3), psk8
+(literal scan), rect8 (separable, not square); and on the two widest labels of tests/tables.py, ring8_mu7 (mu = 7, literal
+scan) and grid16_mu8 (mu = 8, separable), whose digests were recorded on the commit that added them (its kernels are the
+parent's).
 Packets: F = 3 and, where F enters the launch geometry, the smallest F at which the symbols-per-workgroup rule
 (nchunk = ceil(8 n_cu / per) clamped to [1, D], Dc = ceil(D / nchunk)) gives a Dc >= 2 that does not divide D: computed
 from the engine's n_cu, asserted in the test.
@@ -36,10 +39,11 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "soft_outputs.json")
 N, P, D = 1024, 2, 9
 SNR_DB = 15.0
-CONTEXTS = [(t, C) for t in ("qpsk_ref", "qam16", "qam64", "psk8", "rect8") for C in (70, 300)]
+CONTEXTS = [(t, C) for t in ("qpsk_ref", "qam16", "qam64", "psk8", "rect8", "ring8_mu7", "grid16_mu8") for C in (70, 300)]
 SQUARE = ("qpsk_ref", "qam16", "qam64")
 FUSED = {"qpsk_ref-contig-1024-P2-D3-float64": 1, "qam64-contig-1024-P2-D3-float64": 3,
-         "psk8-all_reversed-1024-P1-D5-float64": 0, "rect8-comb2-1024-P2-D3-float64": 0}
+         "psk8-all_reversed-1024-P1-D5-float64": 0, "rect8-comb2-1024-P2-D3-float64": 0,
+         "ring8_mu7-all_reversed-1024-P1-D3-float64": 0, "grid16_mu8-shuffled-1024-P2-D3-float64": 0}
 LEFT_OUT = []                                   # "case/item" that the parent's two recordings disagreed on: not in the golden file
 CASES = [f"{t}-C{C}" for t, C in CONTEXTS] + ["fused-" + k for k in FUSED] + ["fused-qam16", "fused-direct-stores"]
 

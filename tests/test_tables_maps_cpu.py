@@ -16,6 +16,28 @@ def test_table_takes_the_branch_its_comment_names(name):
     assert T.classify(pts, bits) == T.EXPECTED_CLASS[name]
 
 
+@pytest.mark.parametrize("name", T.SOFT_TABLES)
+def test_soft_tables_have_no_empty_set(name):
+    """Every label bit takes both values over the table's points: the max-log formula has no empty set."""
+    bits = T.TABLES[name][1]
+    assert (bits.min(axis=0) == 0).all() and (bits.max(axis=0) == 1).all()
+
+
+def test_the_widest_labels_are_in_the_zoo():
+    """mu = 7 and mu = 8 (the widest gf3_ctx_create accepts) on tables of at most 64 points, in the soft tests too; the
+    oracle's mapper and packer take them."""
+    from oracle import gf3_oracle as orc
+    assert {T.TABLES[n][1].shape[1] for n in T.SOFT_TABLES} >= {1, 2, 3, 4, 5, 6, 7, 8}
+    for name, mu in (("grid16_mu8", 8), ("ring8_mu7", 7)):
+        p = T.params_for(name, 1024, T.comb3(511), P=1, D=3)
+        assert p.mu == mu and name in T.SOFT_TABLES
+        payload = T.existing_labels_payload(np.random.RandomState(mu), p, p.D * p.C)
+        X = orc.map_bits(payload.reshape(-1, p.C, p.mu), p)
+        assert X.shape == (p.D, p.C) and np.isin(X, p.const_points).all()
+        packed = orc.pack_bits(payload, p.D * p.C * p.mu)
+        assert np.array_equal(np.unpackbits(packed.reshape(-1))[: payload.size], payload)
+
+
 @pytest.mark.parametrize("K", [511, 1023, 2047, 4095])
 def test_maps_are_what_they_claim(K):
     for name, fn in T.MAPS.items():
@@ -49,6 +71,11 @@ def test_cases_cover_the_product_as_required():
     assert any(D == 1 for _, _, D, *_ in geo) and any(P == 1 for _, _, _, P, *_ in geo)
     assert {"float32", "int16"} <= {st for *_, st, nc in geo if nc}
     assert {32 % mu for mu in (T.TABLES[c[0]][1].shape[1] for c in T.CASES)} >= {0, 2}      # labels that straddle words (mu = 3, 5)
+    for t, mu in (("ring8_mu7", 7), ("grid16_mu8", 8)):            # the widest labels: an odd C mu (mu = 7), one carrier alone
+        rows = [c for c in T.CASES if c[0] == t]
+        assert T.TABLES[t][1].shape[1] == mu and any(c[1] == "single_top" and (c[4] * mu) % 32 for c in rows), t
+        assert any(c[1] == "single_top" and (c[4] * mu) % 8 for c in rows) == (mu == 7), t
+        assert any((len(T.MAPS[c[1]](c[2] // 2 - 1)) * mu) % 2 for c in rows) == (mu == 7), t
 
 
 @pytest.mark.parametrize("i", range(len(T.CASES)), ids=T.CASE_IDS)

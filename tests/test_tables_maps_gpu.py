@@ -114,11 +114,27 @@ def test_demap_near_ties_on_other_tables(name):
 def test_tx_frames_on_every_map(table, mp, N):
     """gf3_tx_frames against the oracle's transmitter (one grid, one scan table; mu = 4 and 5), then
     TX -> sync -> RX on the GPU returns the payload."""
+    _tx_round_trip(table, mp, N)
+
+
+@pytest.mark.parametrize("table,mp,N", [("grid16_mu8", "shuffled", 1024), ("grid16_mu8", "comb3", 8192), ("grid16_mu8", "single_top", 2048),
+                                        ("ring8_mu7", "two_bands", 2048), ("ring8_mu7", "all_reversed", 1024),
+                                        ("ring8_mu7", "single_top", 4096)])
+def test_tx_frames_with_the_widest_labels(table, mp, N):
+    """The same with mu = 8 and mu = 7: tx_kernel's 256- and 128-entry idx_of_label, labels of whole bytes and labels that
+    straddle two of them (C mu odd on all_reversed; D C mu = 21 on single_top)."""
+    _tx_round_trip(table, mp, N)
+
+
+def _tx_round_trip(table, mp, N):
     K = N // 2 - 1
     p = T.params_for(table, N, T.MAPS[mp](K), P=2, D=3)
     rs = np.random.RandomState(N + len(mp))
     F = 3
-    payload = rs.randint(0, 2, F * p.D * p.C * p.mu)
+    if len(p.const_points) < 1 << p.mu:                                 # (labels that no point carries: the test below)
+        payload = T.existing_labels_payload(rs, p, F * p.D * p.C)
+    else:
+        payload = rs.randint(0, 2, F * p.D * p.C * p.mu)
     fill = rs.choice(T.QPSK_FILL, size=K - p.C)
     eng = engine_for(p, max_window=256)
     packed = _packed(payload, p)
@@ -166,9 +182,9 @@ def test_tx_frames_with_a_label_no_point_carries():
 # ---- d. soft decisions ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", T.SOFT_TABLES)
 def test_soft_demap_on_every_table(name):
-    """gf3_soft_demap against the oracle's max-log formula (soft_demap_sep_kernel for mu = 1 ... 6 on the separable
-    tables, the table kernel on the others, mu = 5 included); signs are the hard decisions wherever the LLR is above the
-    absolute tolerance."""
+    """gf3_soft_demap against the oracle's max-log formula (soft_demap_sep_kernel for mu = 1, 2, 3, 4 and 8 on the separable
+    tables -- 5, 6 and 7 in the test below --, the straight-line kernel on qam64, the table kernel on the others, mu = 5 and 7
+    included); signs are the hard decisions wherever the LLR is above the absolute tolerance."""
     pts, bits = T.TABLES[name]
     p = T.params_for(name, 1024, T.contig(511), P=1, D=1, CP=0)
     eng = engine_for(p)
@@ -180,6 +196,43 @@ def test_soft_demap_on_every_table(name):
     llr = _np(eng.soft_demap(sym, nv))
     ref = orc.soft_demap_maxlog(sym, nv, p)
     assert llr.shape == ref.shape == (n, p.mu)
+    np.testing.assert_allclose(llr, ref.astype(np.float32), rtol=2e-6, atol=1e-6)
+    hard = _np(eng.demap_hard(sym)[0])
+    assert np.array_equal(hard, orc.demap_hard(sym, p)[0])
+    sure = np.abs(llr) > 1e-6
+    assert sure.mean() > 0.99 and np.array_equal((llr < 0)[sure], hard.astype(bool)[sure])
+    eng.close()
+
+
+def _separable_table(mu):
+    """A separable grid that is no binary-indexed one (Gray axis labels), mu = 5 (8 x 4), 6 (8 x 8) or 7 (4 x 4, the Q axis
+    labelled with five bits of which every one takes both values)."""
+    gray8 = [0, 1, 3, 2, 6, 7, 5, 4]
+    lv8, lv4 = np.arange(-7.0, 8.0, 2.0) / 7.0, np.arange(-3.0, 4.0, 2.0) / 3.0
+    if mu == 5:
+        return T._grid(lv8, lv4, gray8, T.GRAY4, 2)
+    if mu == 6:
+        return T._grid(lv8, lv8, gray8, gray8, 3)
+    return T._grid(lv4, lv4, T.GRAY4, [0b00000, 0b01011, 0b11101, 0b10110], 5)
+
+
+@pytest.mark.parametrize("mu", [5, 6, 7])
+def test_soft_demap_separable_tables_of_the_remaining_widths(mu):
+    """soft_demap_sep_kernel<MU> is picked by mu = 1 .. 8; the zoo's separable tables that are no binary-indexed grid have
+    mu = 1 (bpsk), 2 (pam4x1, the reference's QPSK), 3 (rect8), 4 (qam16_scaled_axes, qam16_unequal) and 8 (grid16_mu8).  The
+    same comparison as test_soft_demap_on_every_table on one table for each of mu = 5, 6, 7."""
+    pts, bits = _separable_table(mu)
+    assert bits.shape == (len(pts), mu) and T.classify(pts, bits) == "uniform"
+    assert (bits.min(axis=0) == 0).all() and (bits.max(axis=0) == 1).all()
+    p = T.params_for((pts, bits), 1024, T.contig(511), P=1, D=1, CP=0)
+    eng = engine_for(p)
+    rs = np.random.RandomState(mu)
+    n = 4999
+    dmin = np.abs(pts[:, None] - pts[None, :])[np.triu_indices(len(pts), 1)].min()
+    sym = pts[rs.randint(0, len(pts), n)] + 0.3 * dmin * (rs.randn(n) + 1j * rs.randn(n))
+    llr = _np(eng.soft_demap(sym, 0.05))
+    ref = orc.soft_demap_maxlog(sym, 0.05, p)
+    assert llr.shape == ref.shape == (n, mu)
     np.testing.assert_allclose(llr, ref.astype(np.float32), rtol=2e-6, atol=1e-6)
     hard = _np(eng.demap_hard(sym)[0])
     assert np.array_equal(hard, orc.demap_hard(sym, p)[0])
@@ -244,13 +297,14 @@ def test_known_channel_zero_forcing_on_scattered_maps(table, mp, N):
 
 # ---- f. unpack / whitening --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("table,mp,D", [("bpsk", "all_reversed", 3), ("psk8", "comb3", 5), ("cross32", "all_reversed", 3),
-                                        ("rect8", "single_top", 23)])
+                                        ("rect8", "single_top", 23), ("ring8_mu7", "all_reversed", 3),
+                                        ("ring8_mu7", "single_top", 13), ("grid16_mu8", "all_reversed", 3)])
 def test_unpack_with_whitening_for_labels_that_do_not_divide_a_word(table, mp, D):
-    """gf3_unpack_bits with the XOR mask, mu in {1, 3, 5} and odd C (padded rows, mask period C mu odd) against
-    oracle.xor_decode."""
+    """gf3_unpack_bits with the XOR mask, mu in {1, 3, 5, 7} and odd C (padded rows, mask period C mu odd) against
+    oracle.xor_decode; mu = 8 (the widest label; it does divide a word) on the same odd C."""
     K = 511
     p = T.params_for(table, 1024, T.MAPS[mp](K), P=2, D=D)
-    assert p.mu in (1, 3, 5) and p.C % 2 == 1
+    assert p.mu in (1, 3, 5, 7, 8) and p.C % 2 == 1
     eng = engine_for(p)
     F = 5
     rs = np.random.RandomState(p.C + p.mu)

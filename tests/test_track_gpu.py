@@ -160,6 +160,26 @@ def test_tables(kind):
     compare(kind, engine_of(bins, table), eq, table[0], bins, 7)
 
 
+GRID_TABLES = {"qam4_binary": (2, 0.1, 0.3), "qam16": (4, 0.03, 0.1), "qam64": (6, 0.015, 0.03)}
+
+
+def grid_case(kind, C, N):
+    """-> (table, bins, eq): F = 2, D = 3, the top C bins, the noise and the ramps of test_tables."""
+    mu, sigma, step = GRID_TABLES[kind]
+    table = orc.square_qam_table(mu)
+    bins = np.arange(N // 2 - 1 - C, N // 2 - 1) + 1
+    return table, bins, synth(table[0], bins, 2, 3, sigma, (step, -step / 2), seed=C + mu)
+
+
+@pytest.mark.parametrize("C,N", [(513, 4096), (1025, 4096), (1537, 4096), (2049, 8192)])
+@pytest.mark.parametrize("kind", list(GRID_TABLES))
+def test_grid_tables_at_every_carriers_per_thread_step(kind, C, N):
+    """track_phase_kernel<HI, CPT> for HI = 1, 2, 3 at CPT = 2, 3, 4 and 8: test_tables runs the grid kernels at one carrier
+    per thread only, test_carrier_counts walks the steps with the reference's QPSK (HI = 0)."""
+    table, bins, eq = grid_case(kind, C, N)
+    compare(f"{kind}_{C}", engine_of(bins, table, D=3, N=N), eq, table[0], bins, 3)
+
+
 # ---- coasting -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C", [65, 1025])
 def test_coasting_symbols_and_left_out_carriers(C):
