@@ -23,7 +23,7 @@ from .coding import QCLDPC_ENCODINGS, QCLDPC_LIFTING, CodedChain, decode_report 
 from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
-from .pipeline import check_clock, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
+from .pipeline import check_clock, check_rate, convert_rate, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -58,6 +58,7 @@ class CamG:
     """Parameter block: same constructor and attributes as OFDM.py:17-114."""
 
     last_tx_report = None                       # set by every transmit() (see papr_reduction below)
+    last_input_rate = None                      # set by receive calls once one has run under input_rate (see input_rate below)
     sync_report = None                          # set by every receive call (see sync_rule below)
 
     def __init__(self, mode, encoding="None", no_pilots=20, packet_length=180):
@@ -243,6 +244,27 @@ class CamG:
         # that does not end is what live.LiveReceiver takes.
         self.sync_rule = "global"
         self.detect_threshold = 0.3
+        # both sides, every encoding: the sound card's own sampling rate.  Everything here is built on fs = 48000; a phone or
+        # laptop records at 44.1 kHz, a USB interface at 88.2 or 96 kHz, and such a recording holds no chirp the sync could
+        # find (44.1 kHz is 88 435 ppm away; clock_correction works per packet, after the sync, up to 2000 ppm).
+        # input_rate = the recording's rate in Hz, a finite number in [24000, 192000]: receive() converts the recording to fs
+        # on the GPU right after the upload, ahead of the sync (Engine.resample_stream), in float32 for u8, i16
+        # and f32 recordings and float64 for f64 ones; everything after that -- every encoding and option, sync_rule
+        # "local", the plots -- is as for a 48 kHz recording, clock_correction takes the residual ppm, and every sample
+        # index reported stays in fs numbering.  receive_diversity() also takes a sequence with one rate per recording.
+        # rate_taps = 64 or 32 taps of the windowed sinc at the narrower of the two rates: 64 is clean up to 0.85 of the
+        # narrower Nyquist frequency, 32 up to 0.74 -- at 44.1 kHz that is 16.3 kHz, below the *2 modes' top carrier at
+        # 17.6 kHz, which is why 64 is the default.  A receive call leaves the rate (or the rates [B]) applied in
+        # `last_input_rate`, None where nothing was converted (the attribute stays on the class, like `last_tx_report`, until
+        # a call under input_rate first sets it); a rate equal to fs is the same as None.
+        # output_rate = the playing sound card's rate, same range: transmit() returns the signal at that rate (the 48 kHz
+        # stream through the same conversion); `last_tx_report` describes the 48 kHz rows and gains output_rate and
+        # output_samples.  ValueError for another type, a value outside the range, rate_taps other than 32 or 64, and an
+        # input_rate whose Nyquist frequency the top data carrier reaches; NotImplementedError on the piece-wise host path.
+        # live.LiveReceiver converts the blocks it is fed.  None: everything as without it, bit for bit.
+        self.input_rate = None
+        self.output_rate = None
+        self.rate_taps = 64
         self.papr_reduction = False
         self.papr_target_db = 6.0
         self.papr_iterations = 16
@@ -478,6 +500,7 @@ class transmitter(CamG):
         number = isinstance(gain, (int, float, np.integer, np.floating)) and not isinstance(gain, (bool, np.bool_))
         if not number or not np.isfinite(float(gain)) or float(gain) <= 0.0:
             raise ValueError(f"body_gain must be a finite number > 0, not {gain!r}")
+        check_rate(self.output_rate, self.rate_taps, self.fs, "output_rate")
         if not self.papr_reduction:
             return float(gain), None
         papr = Engine.check_papr(self.papr_target_db, self.papr_tone_limit_db, self.papr_iterations)
@@ -539,7 +562,7 @@ class transmitter(CamG):
             rows = np.concatenate(rows) if rows else np.zeros((0, eng.cfg.frame_len))
             found = torch.cat(found).cpu().numpy() if found else np.zeros((0, self.packet_length, 4))      # the one small read-back
         self.last_tx_report = self._tx_report(rows, found, gain) if self.no_packets else None
-        signal = np.hstack([rows.reshape(-1), self.sync_chirp()])       # final chirp (OFDM.py:259)
+        signal = self._at_output_rate(np.hstack([rows.reshape(-1), self.sync_chirp()]))       # final chirp (OFDM.py:259)
         print("Number of packets to transmit:      " + str(self.no_packets))
         if graph_output:
             self._plot_frame(signal)
@@ -567,9 +590,22 @@ class transmitter(CamG):
         if gain != 1.0:
             rows[:, self.chirp_length:] *= gain
         self.last_tx_report = self._tx_report(rows) if self.no_packets else None
+        signal = self._at_output_rate(signal)
         print("Number of packets to transmit:      " + str(self.no_packets))
         if graph_output:
             self._plot_frame(signal)
+        return signal
+
+    def _at_output_rate(self, signal):
+        """The stream transmit() made at fs -> what it returns: the same array without `output_rate`, else the stream at that
+        rate (Engine.resample_stream on the float64 engine, r = fs / output_rate), and the report of a transmission with
+        packets gains output_rate and output_samples."""
+        rate = check_rate(self.output_rate, self.rate_taps, self.fs, "output_rate")
+        if rate is not None:
+            signal = self._engine().resample_stream(torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float64)),
+                                                    float(self.fs) / rate[0], half_taps=rate[1]).cpu().numpy()
+        if self.output_rate is not None and self.last_tx_report is not None:
+            self.last_tx_report.update(output_rate=float(self.output_rate), output_samples=len(signal))
         return signal
 
 
@@ -722,6 +758,9 @@ class receiver(transmitter):
             rs = [located[0]]
             dtype = torch.empty(0, dtype=located[0].dtype).numpy().dtype
         plan = self._plan([len(r) for r in rs], graph_output, diversity)
+        rates = plan.rates if located is None else None         # (a located stream has been converted already)
+        if rates:                                               # the conversion's output type: f32 for u8, i16 and f32 recordings
+            dtype = np.dtype("float64") if dtype == np.float64 else np.dtype("float32")
         eng = self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
         # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
         # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
@@ -730,7 +769,8 @@ class receiver(transmitter):
         if plan.piecewise:
             return self._receive_chunked(eng, rs[0], plan.chunk)
         # 1. sync, every recording on its own
-        xs = [eng._samples(r) for r in rs]
+        # (under input_rate: converted to fs first, every recording by its own rate)
+        xs = [eng._samples(r) if rate is None else convert_rate(eng, r, rate, self.fs) for r, rate in zip(rs, rates or [None] * len(rs))]
         sync_rho = None
         if located is not None:
             peaks, sync_rho = [located[1]], [located[2]]
@@ -824,6 +864,9 @@ class receiver(transmitter):
         else (the table and the open point that follows from it: DESIGN §12, "The receive pipeline")."""
         self._last_slope = got["slope"]
         self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
+        if plan.rates is not None or "last_input_rate" in vars(self):      # (value or None, from the first call under input_rate on)
+            applied = None if plan.rates is None else [float(self.fs) if v is None else v[0] for v in plan.rates]
+            self.last_input_rate = applied if applied is None else (np.array(applied) if diversity else applied[0])
         for name in _VALUE_OR_NONE[diversity]:
             setattr(self, name, got.get(name))
         if plan.clock and not diversity:                        # (one recording: the value, not an array [B])

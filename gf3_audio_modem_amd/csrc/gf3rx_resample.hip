@@ -1,5 +1,7 @@
 // libgf3rx -- sampling-clock correction: packet bodies resampled with a windowed-sinc interpolator, between sync (and
-// blanking) and demodulation (gf3_resample_frames, gf3_resample_coefficients).  See DESIGN.md §12.
+// blanking) and demodulation (gf3_resample_frames, gf3_resample_coefficients); and, on the same table and arithmetic, the
+// conversion of a whole stream from another sampling rate in front of the sync (gf3_resample_stream, further down).  See
+// DESIGN.md §12.
 //
 // Clock model.  Receiver sample j of a body that starts at s holds the transmitted waveform at time j (1 + eps): eps > 0
 // means the receiver took fewer samples than were sent; ppm = 1e6 eps.
@@ -192,6 +194,110 @@ hipError_t launch_resample(const ResampleArgs& a, int T, int64_t grid, hipStream
     return launch(resample_kernel<DT, 32>, grid, RS_THREADS, 0, st, a);
 }
 
+// ---- whole-stream rate conversion (gf3_resample_stream; the rule is stated in include/gf3rx.h) ---------------------------
+// One workgroup per tile of RS_TILE outputs j = j0 + tile RS_TILE ...; the tile's input window -- floor(j r) of its first
+// output to that of its last and the taps around them -- is staged once in LDS, widened to fp64, zeros where it leaves the
+// buffer.  A wave takes 64 consecutive outputs.  r <= 1 goes through read_point / interpolate, the frames kernel's own code;
+// r > 1 widens the kernel to Tw = ceil(T r) taps to either side, and every tap of every lane has its own two table rows.
+// Rows are read from the table in memory on both paths: a ratio such as 147/160 walks through its 160 phases in no order
+// that a tile could cache as a range, and the table (264 / 528 KB) stays in L2.
+constexpr double RS_MIN_RATIO = 0.25, RS_MAX_RATIO = 4.0;
+constexpr int RS_MAX_TW = 128;                              // ceil(32 x 4)
+// window of a tile: floor((j0 + RS_TILE - 1) r) - floor(j0 r) <= 511 x 4 + 1 = 2045 input steps, plus 2 Tw <= 256 taps
+constexpr int RS_SWIN = 2304;
+static_assert((RS_TILE - 1) * RS_MAX_RATIO + 1.0 + 2.0 * RS_MAX_TW <= RS_SWIN, "a tile's input window fits the LDS buffer");
+static_assert(32 * RS_MAX_RATIO <= RS_MAX_TW, "Tw = ceil(T r) stays within RS_MAX_TW");
+
+struct StreamArgs {
+    const void* in; void* out; const double* h;
+    int64_t n_in, in_origin, j0, n_out;
+    double r;
+};
+
+// t_j = (double)j * r rounded once -> floor(t_j) as a double, mu = t_j - floor(t_j)  (read_point's first two lines)
+GF3_DEV double read_time(int64_t j, double r, double& mu) {
+#pragma clang fp contract(off)
+    const double tj = (double)j * r;
+    const double fl = floor(tj);
+    mu = tj - fl;
+    return fl;
+}
+
+// coefficient of the tap at distance d from floor(t_j) on the down path: the table read at u = (d - mu) rho = n - f,
+// column n + T - 1, phase f; 0 where the column lies outside the table.  Every product is rounded once.
+template <int T>
+GF3_DEV double down_tap(const double* h, int d, double mu, double rho) {
+#pragma clang fp contract(off)
+    const double v = ((double)d - mu) * rho;
+    const double n = ceil(v);
+    const double q = (n - v) * RS_L;
+    const int p = min((int)q, RS_L - 1);
+    const double al = q - (double)p;
+    const int col = (int)n + T - 1;
+    const bool inside = col >= 0 && col < 2 * T;
+    const double* h0 = h + (size_t)p * (2 * T) + (inside ? col : 0);
+    const double c0 = h0[0], c1 = h0[2 * T];
+    const double c = rho * fma(al, c1 - c0, c0);
+    return inside ? c : 0.0;
+}
+
+template <int DI, int DO, int T>
+__global__ __launch_bounds__(RS_THREADS) void resample_stream_kernel(StreamArgs a) {
+    typedef typename RawT<DI>::E EI;
+    typedef typename RawT<DO>::E EO;
+    __shared__ double win[RS_SWIN];
+    const int t = threadIdx.x;
+    const int64_t ja = a.j0 + (int64_t)blockIdx.x * RS_TILE, jb = min(ja + (int64_t)RS_TILE, a.j0 + a.n_out);
+    const double r = a.r;
+    const bool down = r > 1.0;
+    const int Tw = down ? min((int)ceil((double)T * r), RS_MAX_TW) : T;
+    double unused;
+    const int64_t i_first = (int64_t)read_time(ja, r, unused), i_last = (int64_t)read_time(jb - 1, r, unused);
+    const int W = (int)min(i_last - i_first + 2 * (int64_t)Tw, (int64_t)RS_SWIN);     // (never more: the static_assert above)
+    const int64_t g0 = i_first - Tw + 1 - a.in_origin;     // win[w] = in[g0 + w]
+    const EI* in = (const EI*)a.in;
+    for (int w = t; w < W; w += RS_THREADS) {
+        const int64_t g = g0 + w;
+        win[w] = (g >= 0 && g < a.n_in) ? (double)in[g] : 0.0;
+    }
+    __syncthreads();
+    EO* out = (EO*)a.out;
+    for (int64_t j = ja + t; j < jb; j += RS_THREADS) {
+        double v;
+        if (!down) {
+            int p;
+            double al;
+            const double fl = read_point(j, r, p, al);
+            const double* w = win + max(min((int)((int64_t)fl - i_first), RS_SWIN - 2 * T), 0);
+            v = interpolate<T, 2 * T>(a.h + (size_t)p * (2 * T), al, w);
+        } else {
+            double mu;
+            const double fl = read_time(j, r, mu);
+            const double* w = win + max(min((int)((int64_t)fl - i_first), RS_SWIN - 2 * Tw), 0);
+            const double rho = 1.0 / r;
+            v = 0.0;
+            for (int k = 0; k < 2 * Tw; ++k) v = fma(down_tap<T>(a.h, k - Tw + 1, mu, rho), w[k], v);
+        }
+        out[j - a.j0] = to_storage<DO>(v);
+    }
+}
+
+template <int DI, int DO>
+hipError_t launch_stream(const StreamArgs& a, int T, int64_t grid, hipStream_t st) {
+    if (T == 16) return launch(resample_stream_kernel<DI, DO, 16>, grid, RS_THREADS, 0, st, a);
+    return launch(resample_stream_kernel<DI, DO, 32>, grid, RS_THREADS, 0, st, a);
+}
+
+template <int DO>
+hipError_t launch_stream_from(int in_dtype, const StreamArgs& a, int T, int64_t grid, hipStream_t st) {
+    switch (in_dtype) {
+        case DT_F64: return launch_stream<DT_F64, DO>(a, T, grid, st);
+        case DT_F32: return launch_stream<DT_F32, DO>(a, T, grid, st);
+        case DT_I16: return launch_stream<DT_I16, DO>(a, T, grid, st);
+        default:     return launch_stream<DT_U8, DO>(a, T, grid, st);
+    }
+}
+
 }  // namespace
 
 extern "C" int gf3_resample_coefficients(int32_t half_taps, double* h_out) {
@@ -219,5 +325,28 @@ extern "C" int gf3_resample_frames(gf3_ctx* c, const void* d_in, int64_t n_in, c
     ResampleArgs a{d_in, d_out, n_in, d_off, d_eps, h, d_status, len, (int)tiles};
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_DT(c->cfg.in_dtype, HIPCHK(c, launch_resample<DTC>(a, half_taps, F * tiles, st)));
+    return GF3_OK;
+}
+
+extern "C" int gf3_resample_stream(gf3_ctx* c, const void* d_in, int32_t in_dtype, int64_t n_in, int64_t in_origin, double r,
+                                   int32_t half_taps, int64_t j0, int64_t n_out, void* d_out, void* stream) {
+    DeviceGuard dg(c);
+    constexpr int64_t EXACT = (int64_t)1 << 51;             // (double)j and j r <= 4 j stay exact integers / below 2^53
+    if (!c || n_in < 0 || n_out < 0 || in_origin < 0 || j0 < 0) return fail(c, GF3_EINVAL, "gf3_resample_stream: bad argument (a negative count or index)");
+    if (in_dtype < DT_F64 || in_dtype > DT_U8) return fail(c, GF3_EINVAL, "gf3_resample_stream: in_dtype must be one of GF3_F64 .. GF3_U8, not %d", in_dtype);
+    if (d_out && d_out == d_in) return fail(c, GF3_EINVAL, "gf3_resample_stream: d_out must be a second buffer, not d_in");
+    if (half_taps != 16 && half_taps != 32) return fail(c, GF3_EINVAL, "gf3_resample_stream: half_taps must be 16 or 32, not %d", half_taps);
+    if (!(r >= RS_MIN_RATIO && r <= RS_MAX_RATIO)) return fail(c, GF3_EINVAL, "gf3_resample_stream: r must be a finite ratio in [0.25, 4], not %g", r);
+    const int64_t tiles = n_out / RS_TILE + (n_out % RS_TILE ? 1 : 0);
+    if (tiles > 0x7fffffff)
+        return fail(c, GF3_EINVAL, "gf3_resample_stream: at most 2^31 - 1 tiles of %d outputs per call (n_out = %lld)", RS_TILE, (long long)n_out);
+    if (n_in > EXACT || in_origin > EXACT || j0 > EXACT - n_out) return fail(c, GF3_EINVAL, "gf3_resample_stream: indices beyond 2^51");
+    if (n_out == 0) return GF3_OK;                          // (no outputs: no address is needed)
+    if (!d_out || (!d_in && n_in > 0)) return fail(c, GF3_EINVAL, "gf3_resample_stream: null pointer");
+    const double* h = device_table(c, half_taps);
+    if (!h) return fail(c, GF3_EHIP, "gf3_resample_stream: the coefficient table could not be made on the device");
+    StreamArgs a{d_in, d_out, h, n_in, in_origin, j0, n_out, r};
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_DT(c->cfg.in_dtype, HIPCHK(c, launch_stream_from<DTC>(in_dtype, a, half_taps, tiles, st)));
     return GF3_OK;
 }

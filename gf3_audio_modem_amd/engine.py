@@ -989,6 +989,69 @@ class Engine:
                                                  _ptr(status), self._stream()))
         return rows, torch.arange(F, dtype=torch.int64, device=self.device) * n, status
 
+    @staticmethod
+    def check_ratio(r, half_taps, who="resample_stream"):
+        """ValueError unless r is a finite number in [0.25, 4] and half_taps 16 or 32 (what gf3_resample_stream refuses)
+        -> (r as a float, half_taps as an int)."""
+        if isinstance(half_taps, (bool, np.bool_)) or half_taps not in (16, 32):
+            raise ValueError(f"{who}: half_taps must be 16 or 32, not {half_taps!r}")
+        number = isinstance(r, (int, float, np.integer, np.floating)) and not isinstance(r, (bool, np.bool_))
+        if not number or not 0.25 <= float(r) <= 4.0:       # (NaN fails both comparisons)
+            raise ValueError(f"{who}: r must be a finite number of input samples per output sample in [0.25, 4], not {r!r}")
+        return float(r), int(half_taps)
+
+    @staticmethod
+    def stream_outputs(n_seen, r, half_taps, final=False):
+        """How many outputs j = 0, 1, ... of resample_stream are final once n_seen input samples have arrived: those with
+        floor((double)j r) + Tw <= n_seen - 1, Tw = ceil(half_taps r) (half_taps where r <= 1).  final=True: the stream has
+        ended at n_seen samples -> the whole-recording count, every j with (double)j r <= n_seen - 1.  Integer and double
+        arithmetic on the host; no GPU call."""
+        r, half_taps = Engine.check_ratio(r, half_taps, "stream_outputs")
+        n_seen = int(n_seen)
+        if n_seen < 0:
+            raise ValueError(f"stream_outputs: n_seen must be >= 0, not {n_seen}")
+        reach = 0 if final else (int(math.ceil(half_taps * r)) if r > 1.0 else half_taps)
+        last = n_seen - 1 - reach                               # the largest floor(t_j) (final: the largest t_j) that counts
+        if last < 0:
+            return 0
+
+        def counts(j):                                          # (monotonic in j: the product is rounded monotonically)
+            t = float(j) * r
+            return t <= last if final else math.floor(t) <= last
+        j = int(last / r)
+        while counts(j + 1):
+            j += 1
+        while j >= 0 and not counts(j):
+            j -= 1
+        return j + 1
+
+    def resample_stream(self, x, r, half_taps=32, in_origin=0, j0=0, n_out=None, out=None):
+        """Whole-stream rate conversion (gf3_resample_stream): x, a device tensor (or array) of any of the four storage
+        types, holds samples in_origin .. in_origin + len(x) - 1 of a stream taken at r = input_rate / output_rate input
+        samples per output sample (0.25 <= r <= 4); outputs j0 .. j0 + n_out - 1 are read at the times j r through a
+        Kaiser-windowed sinc of 2 half_taps taps -- widened by r, and low-passing to the output's Nyquist frequency, where
+        r > 1 -- with samples outside x read as 0.  Indices are the stream's own, so a stream converted block by block
+        (stream_outputs tells how far) gives the bytes of the stream converted whole.  n_out: default the whole-recording
+        count of in_origin + len(x) samples, less j0.  out: optional contiguous tensor of n_out samples in the engine's
+        storage type, not x itself.  -> n_out samples in the ENGINE's storage type, whatever x's is.  ValueError for what
+        the library refuses.  Two calls give identical bytes."""
+        r, half_taps = self.check_ratio(r, half_taps)
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if not isinstance(x, torch.Tensor) or x.dtype not in _DT_OF:
+            raise ValueError("resample_stream: x must be a tensor or array of float64, float32, int16 or uint8 samples")
+        x = x.to(self.device).contiguous().reshape(-1)
+        in_origin, j0 = int(in_origin), int(j0)
+        if n_out is None:
+            n_out = max(self.stream_outputs(in_origin + x.numel(), r, half_taps, final=True) - j0, 0) if in_origin >= 0 else 0
+        n_out = int(n_out)
+        if n_out < 0:
+            raise ValueError(f"resample_stream: n_out must be >= 0, not {n_out}")
+        y = self._out(out, (n_out,), self.cfg.in_dtype, "n_out").reshape(-1)
+        self._check(self.lib.gf3_resample_stream(self._h, _ptr(x) if x.numel() else None, _DT_OF[x.dtype], x.numel(), in_origin, r,
+                                                 half_taps, j0, n_out, _ptr(y) if n_out else None, self._stream()))
+        return y
+
     def clock_offset(self, slope):
         """The sampling-clock offset eps a fitted phase slope stands for (demod_frames(want=("slope",))): the slope is the
         phase per carrier index accrued over the (P + D) S samples between the pilot blocks' centres, so

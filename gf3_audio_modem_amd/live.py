@@ -11,9 +11,15 @@ rule (Engine.detect_chunk / detect_decide) does not, so a stream can be fed bloc
 
 `Segmenter` is the state machine between the two (detections in, closed transmissions out); it works on integers and makes
 no GPU call.  Whatever a listener must survive -- a lone chirp, a transmission that never ends, a packet cut off by the end
-of the stream, a transmission that fails to decode -- becomes an entry of `live.events`, never an exception."""
+of the stream, a transmission that fails to decode -- becomes an entry of `live.events`, never an exception.
+
+With `rx.input_rate` set the blocks are taken at that rate: every block is converted to fs as far as its outputs are final
+(Engine.resample_stream on the stream's own indices, with the input samples the next outputs still read carried over), so
+what the detector and the decoder see is byte for byte the whole stream converted at once, whatever the block sizes; every
+index reported stays in fs numbering, and `Transmission.start_input_sample` is the index in the stream as it was fed."""
 import contextlib
 import io
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -67,6 +73,7 @@ class Transmission:
     decode_report: object                                       # rx.last_decode_report of its decode
     Hs0: np.ndarray
     He0: np.ndarray
+    start_input_sample: int = None                              # start_sample in the numbering of the stream as it was fed
 
 
 class LiveReceiver:
@@ -85,6 +92,9 @@ class LiveReceiver:
         with self._local():
             plan = plan_receive(rx, rx._chain(), [self.max_samples], False, False)
         self.tau = plan.detect
+        self.rate = plan.rates[0] if plan.rates else None       # (input rate, half_taps) of the fed stream, or None
+        self.r = 1.0 if self.rate is None else self.rate[0] / float(rx.fs)
+        self.n_fed = self.raw_base = self.n_converted = 0       # input samples fed; stream index of raw[0]; outputs made so far
         self.eng = None
         self.n_seen = self.n_done = self.base = 0               # samples fed; lags through detect_chunk; stream index of buf[0]
         self.decided = -END                                     # final_below of the last decision
@@ -100,7 +110,12 @@ class LiveReceiver:
 
     def _start(self, block):
         dtype = block.dtype if isinstance(block, np.ndarray) else torch.empty(0, dtype=block.dtype).numpy().dtype
-        self.eng = eng = self.rx._engine(dtype if dtype in (np.float64, np.float32, np.int16, np.uint8) else np.dtype("float64"))
+        dtype = dtype if dtype in (np.float64, np.float32, np.int16, np.uint8) else np.dtype("float64")
+        self.raw_dtype = dtype
+        if self.rate is not None:                               # the conversion's output type, as in rx.receive()
+            dtype = np.dtype("float64") if dtype == np.float64 else np.dtype("float32")
+        self.eng = eng = self.rx._engine(dtype)
+        self.raw = torch.empty((0,), dtype=torch.from_numpy(np.empty(0, self.raw_dtype)).dtype, device=eng.device)
         self.buf = torch.empty((0,), dtype=eng.cfg.in_dtype, device=eng.device)
         self.vrun = torch.zeros((1,), dtype=torch.float64, device=eng.device)
         self.idx = torch.empty((0,), dtype=torch.int64, device=eng.device)
@@ -110,7 +125,30 @@ class LiveReceiver:
         """Take the next samples of the stream -> the transmissions that ended inside them (a list, often empty)."""
         if self.eng is None:
             self._start(block)
-        x = self.eng._samples(block).reshape(-1)
+        if self.rate is not None:
+            return self._feed(self._convert(block, final=False))
+        return self._feed(self.eng._samples(block).reshape(-1))
+
+    def _convert(self, block, final):
+        """The next input samples (None: none) -> the samples at fs that they make final (final: the stream has ended -- all
+        that are left, the taps behind the end reading zeros)."""
+        if block is not None:
+            block = torch.as_tensor(block).reshape(-1)
+            self.raw = torch.cat([self.raw, block.to(self.raw.dtype).to(self.eng.device)])
+            self.n_fed += block.numel()
+        r, half_taps = self.r, self.rate[1]
+        upto = self.eng.stream_outputs(self.n_fed, r, half_taps, final=final)
+        y = self.eng.resample_stream(self.raw, r, half_taps, in_origin=self.raw_base, j0=self.n_converted,
+                                     n_out=max(upto - self.n_converted, 0))
+        self.n_converted = max(upto, self.n_converted)
+        reach = int(math.ceil(half_taps * r)) if r > 1.0 else half_taps
+        keep = max(int(math.floor(float(self.n_converted) * r)) - reach + 1, self.raw_base)     # the first sample the next output reads
+        if keep > self.raw_base:
+            self.raw, self.raw_base = self.raw[keep - self.raw_base:].clone(), keep
+        return y
+
+    def _feed(self, x):
+        """feed() on samples at fs in the engine's storage."""
         if x.numel() == 0:
             return []
         self.buf = torch.cat([self.buf, x])
@@ -143,6 +181,10 @@ class LiveReceiver:
         still open with more than max_gap samples behind its last chirp is reported as a cut-off packet."""
         if self.eng is None:
             return []
+        out = self._feed(self._convert(None, final=True)) if self.rate is not None else []
+        return out + self._flush()
+
+    def _flush(self):
         was_open = bool(self.seg.open) or bool(self.idx.numel())
         out = self._decide(END, at_end=was_open)
         self.idx, self.rho = self.idx[:0], self.rho[:0]
@@ -185,5 +227,6 @@ class LiveReceiver:
                 self.events.append({"kind": "decode_failed", "start_sample": starts[0], "packets": len(starts),
                                     "error": f"{type(e).__name__}: {e}"})
                 continue
-            out.append(Transmission(bits, starts[0], len(starts), rho, self.rx.last_decode_report, Hs0, He0))
+            out.append(Transmission(bits, starts[0], len(starts), rho, self.rx.last_decode_report, Hs0, He0,
+                                    int(math.floor(starts[0] * self.r))))
         return out

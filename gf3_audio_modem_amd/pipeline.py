@@ -10,6 +10,7 @@ from .engine import Engine
 
 PIECEWISE_ABOVE = 1 << 27                                   # samples: a longer recording is taken from host memory piece by piece
 PIECEWISE_CHUNK = 1 << 25                                   # samples per piece where `host_chunk_samples` names none
+RATE_RANGE = (24000.0, 192000.0)                           # sampling rates `input_rate` / `output_rate` take, in Hz
 CLOCK_MAX_PPM = 2000.0                                      # |eps| <= 2e-3: beyond it gf3_resample_frames copies the body
 _HOST = "the piece-wise host path of long recordings (or host_chunk_samples)"
 _LOCAL = "sync_rule 'local': {host} decides by the reference's global rule; feed the stream to a LiveReceiver"
@@ -57,6 +58,45 @@ def check_clock(clock_correction, clock_taps):
     return ppm, int(clock_taps) // 2
 
 
+def check_rate(rate, rate_taps, fs, name="input_rate"):
+    """What `input_rate` / `output_rate` and `rate_taps` refuse before any GPU work -> None (off, or the rate is fs itself), or
+    (the rate in Hz as a float, half_taps).  ValueError for a value that is not a finite number in [24000, 192000] and for a
+    tap count other than 32 or 64."""
+    if rate is None:
+        return None
+    if isinstance(rate_taps, (bool, np.bool_)) or rate_taps not in (32, 64):
+        raise ValueError(f"rate_taps must be 32 or 64, not {rate_taps!r}")
+    number = isinstance(rate, (int, float, np.integer, np.floating)) and not isinstance(rate, (bool, np.bool_))
+    if not number or not RATE_RANGE[0] <= float(rate) <= RATE_RANGE[1]:     # (NaN fails both comparisons)
+        raise ValueError(f"{name} must be None or a finite number of samples per second in [{RATE_RANGE[0]:.0f}, {RATE_RANGE[1]:.0f}], "
+                         f"not {rate!r}")
+    return None if float(rate) == float(fs) else (float(rate), int(rate_taps) // 2)
+
+
+def check_input_rates(rx, count, diversity):
+    """`input_rate` of a receive call on `count` recordings -> None (no recording is converted), or a tuple with check_rate's
+    answer for every recording.  receive_diversity() also takes a sequence with one rate per recording.  ValueError for
+    what check_rate refuses, a sequence of another length (or any sequence under receive()), and a rate whose Nyquist
+    frequency the top data carrier reaches: nothing could decode it."""
+    rate = rx.input_rate
+    if rate is None:
+        return None
+    if isinstance(rate, (list, tuple, np.ndarray)):
+        if not diversity:
+            raise ValueError(f"input_rate must be None or one number for receive(), not {rate!r}")
+        if len(rate) != count:
+            raise ValueError(f"input_rate holds {len(rate)} rates for {count} recordings")
+        rates = [check_rate(v, rx.rate_taps, rx.fs) for v in rate]
+    else:
+        rates = [check_rate(rate, rx.rate_taps, rx.fs)] * count
+    top = float(np.max(rx.data_carriers)) * float(rx.fs) / rx.ofdm_symbol_size
+    for v in rates:
+        if v is not None and top >= v[0] / 2.0:
+            raise ValueError(f"input_rate {v[0]:g}: the top data carrier lies at {top:.0f} Hz, at or above half that rate; "
+                             "nothing could decode it")
+    return tuple(rates) if any(v is not None for v in rates) else None
+
+
 def check_sync_rule(sync_rule, detect_threshold):
     """What `sync_rule` / `detect_threshold` refuse before any GPU work -> None under "global" (the reference's rule), the
     threshold as a float under "local" (Engine.detect_stream).  ValueError for another rule and for a threshold that is not a
@@ -79,29 +119,33 @@ class ReceivePlan(NamedTuple):
     piecewise: bool                         # the recording is taken from host memory piece by piece (Engine.receive_host)
     chunk: int                              # samples per piece
     detect: object = None                   # the threshold of the self-normalised detection (sync_rule "local"), or None
+    rates: object = None                    # check_input_rates' answer: per recording None or (input rate, half_taps), or None
 
 
 def plan_receive(rx, chain, lengths, plots, diversity):
     """The plan of receive() (diversity False) or receive_diversity() on recordings of `lengths` samples, from the
     receiver's attributes as they are now and its CodedChain.  Every refusal of a receive call is raised here, in this order:
     the coded chain's own (CodedChain.check_receive / check_diversity: ValueError), the values of the blanking and the
-    clock correction and of the sync rule (ValueError), then what has no path (NotImplementedError)."""
+    clock correction, of the sync rule and of the input rate (ValueError), then what has no path (NotImplementedError)."""
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = not plots and bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
     if diversity:
         rate, fused, blanking = chain.check_diversity(), False, None
         clock = check_clock(rx.clock_correction, rx.clock_taps)
         detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
+        rates = check_input_rates(rx, len(lengths), True)
         no_path = ((rx.impulse_blanking, "receive_diversity: impulse_blanking is not combined; blank each recording's samples "
                                          "with Engine.blank_impulses first"),
                    (plots, "receive_diversity: no plots; receive() one recording for them"),
                    (piecewise, "receive_diversity: {host} combines nothing; receive shorter recordings"),
-                   (detect and piecewise, _LOCAL))
+                   (detect and piecewise, _LOCAL),
+                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"))
     else:
         rate, fused = chain.check_receive()
         blanking = Engine.check_blanking(rx.blanking_threshold, rx.blanking_guard) if rx.impulse_blanking else None
         clock = check_clock(rx.clock_correction, rx.clock_taps)
         detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
+        rates = check_input_rates(rx, len(lengths), False)
         loaded = chain.loading is not None
         no_path = ((chain.denoise and piecewise, "channel_denoising: {host} has no denoising pass; receive shorter recordings"),
                    (loaded and plots, "bit_loading: the plots draw one constellation; receive with graph_output = False"),
@@ -110,13 +154,20 @@ def plan_receive(rx, chain, lengths, plots, diversity):
                    (clock and piecewise, "clock_correction: {host} has no resampling pass; receive shorter recordings"),
                    (rate is not None and piecewise, "encoding {encoding!r}: {host} has no soft-decision decoding; "
                                                     "receive shorter recordings"),
-                   (detect and piecewise, _LOCAL))
+                   (detect and piecewise, _LOCAL),
+                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"))
     for on, why in no_path:
         if on:
             raise NotImplementedError(why.format(host=_HOST, encoding=chain.encoding))
     denoise = None if chain.denoise is None else float(chain.denoise[0])       # (validated by the chain's checks above)
     return ReceivePlan(chain, rate, fused and not plots, blanking, clock, denoise, bool(plots), piecewise,
-                       int(chunk or PIECEWISE_CHUNK), detect)
+                       int(chunk or PIECEWISE_CHUNK), detect, rates)
+
+
+def convert_rate(eng, r, rate, fs):
+    """One recording (a host array of any storage type) taken at `rate` = check_rate's answer -> the engine's samples at fs:
+    uploaded as it is and converted whole (Engine.resample_stream with r = rate / fs)."""
+    return eng.resample_stream(torch.from_numpy(r), rate[0] / float(fs), half_taps=rate[1])
 
 
 def correct_clock(eng, x, starts, clock):

@@ -807,6 +807,44 @@ int gf3_resample_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int6
                         const double *d_eps_f64, int32_t half_taps, void *d_out, int32_t *d_status_i32, void *stream);
 
 /*
+ * Whole-stream rate conversion, in front of the sync (not in the reference).  Opt-in.  Every kernel here assumes samples
+ * taken at cfg.fs; a recording at 44.1, 88.2 or 96 kHz is 88 435 ppm and more away, far beyond what the per-packet
+ * correction above can take.  gf3_resample_stream converts a stream by any ratio, in either direction, and can be cut
+ * into blocks.
+ *   r = input_rate / output_rate: input samples per output sample, a double in [0.25, 4].  T = half_taps = 16 or 32,
+ *   h the table of gf3_resample_coefficients, [L + 1, 2T], L = 1024.  All in fp64, every product rounded once.
+ *   Output j (a GLOBAL index, int64, j >= 0) reads at
+ *       t_j = (double)j * r,   i_j = floor(t_j),   mu = t_j - i_j.
+ *   r <= 1 (the input is the slower side): gf3_resample_frames' rule, by the same code:
+ *       q = mu L,  p = min((int)q, L - 1),  a = q - p,  c_k = fma(a, h[p+1][k] - h[p][k], h[p][k])
+ *       out[j] = sum_{k = 0 .. 2T-1} c_k x[i_j + k - T + 1]        (ascending k, one fused multiply-add per tap)
+ *     r = 1 copies finite input exactly.
+ *   r > 1 (the input is the faster side): the low-pass moves down to the OUTPUT's Nyquist frequency:
+ *       rho = 1.0 / r,  Tw = (int)ceil(T r);  taps k = 0 .. 2 Tw - 1,  d = k - Tw + 1
+ *       v = ((double)d - mu) rho,  n = ceil(v),  f = n - v,  q = f L,  p = min((int)q, L - 1),  a = q - p,  col = n + T - 1
+ *       c_k = rho fma(a, h[p+1][col] - h[p][col], h[p][col]),   c_k = 0 where col lies outside [0, 2T)
+ *       out[j] = sum_k c_k x[i_j + d]                               (ascending k, one fused multiply-add per tap)
+ *   The input buffer d_in holds x[in_origin .. in_origin + n_in) in the stream's numbering, in the storage type in_dtype
+ *   (a gf3_dtype; it need not be the context's); every sample outside it reads as 0.  The call writes outputs
+ *   j = j0 .. j0 + n_out - 1 to d_out[0 .. n_out) in the CONTEXT's storage type (fp64 as is, f32 by a cast, i16 / u8 by
+ *   rint, half to even, clamped): an 8- or 16-bit recording becomes float32 without a second context.
+ *   Because j and the input index are global, a stream converted in blocks gives the bytes of the stream converted whole,
+ *   as long as each block's buffer holds every sample its outputs' taps reach: i_j - Tw + 1 .. i_j + Tw (T for Tw where
+ *   r <= 1).  A whole recording of n_in samples yields as many outputs as there are j >= 0 with (double)j r <= n_in - 1;
+ *   outputs j with i_j + Tw <= n_seen - 1 are final once n_seen input samples have arrived.
+ *   Band: as gf3_resample_frames, relative to the NARROWER of the two Nyquist frequencies: T = 16 within -100 dB up to
+ *   0.74 of it, T = 32 up to 0.85; at r > 1 what lies above (2 - 0.74 | 0.85) of the output's Nyquist is rejected by
+ *   more than 105 dB.  sum_k |c_k| < 2.8.
+ *   GF3_EINVAL (the text names the function) for a null d_out, or a null d_in with n_in > 0, when n_out > 0;
+ *   d_out == d_in; half_taps other than 16 or 32; in_dtype that is no gf3_dtype; r that is not finite or lies outside
+ *   [0.25, 4]; a negative n_in, n_out, in_origin or j0; more than 2^31 - 1 tiles of 512 outputs; indices beyond 2^51.
+ *   n_out == 0 is a no-op and needs no addresses.  No refusal writes anything.  One launch, no atomics (two runs give
+ *   identical bytes), asynchronous on `stream`; the table is the context's, made on first use as for gf3_resample_frames.
+ */
+int gf3_resample_stream(gf3_ctx *ctx, const void *d_in, int32_t in_dtype, int64_t n_in, int64_t in_origin, double r,
+                        int32_t half_taps, int64_t j0, int64_t n_out, void *d_out, void *stream);
+
+/*
  * Quasi-cyclic LDPC codes (not in the reference, whose pyldpc code is marked broken there).  Lifting size Z = 64, 128
  * or 256; the shift table h_shifts [mb*nb] (row major, int16) holds -1 for a zero block and s in [0, Z) for the
  * circulant whose row z has its one in column (z + s) mod Z.  Block columns 0 .. nb-mb-1 carry the message (systematic
