@@ -27,6 +27,13 @@
  *     the small workspaces gf3_sync_frames keeps in the context, one per
  *     (stream, host thread), under a mutex of the context's own.
  *   - complex128 arrays are interleaved (re, im) doubles, as NumPy stores them.
+ *   - every typed array is aligned as its element type is.  Every workspace
+ *     (`d_work`, `d_list`) must be 16-BYTE ALIGNED: the library carves int32 /
+ *     int64 counts, doubles and complex128 arrays out of it at offsets that keep
+ *     each type's alignment and reads the counts as aligned words.  It cannot check
+ *     the size of a device pointer and does not check this either: a workspace
+ *     off that alignment gives counts and offsets read from the wrong bytes,
+ *     and indices computed from them are not bounded.
  */
 #ifndef GF3RX_H
 #define GF3RX_H
@@ -133,7 +140,10 @@ int gf3_rfft_batch(gf3_ctx *ctx, const void *d_in, int64_t n_in,
  *   d_slope        optional [F]      float64   : polyfit slope p (OFDM.py:462)
  *   d_Hest         optional [F, D, K] complex128: channel model (OFDM.py:471-475)
  * A frame whose samples fall outside [0, n_in) decodes to zero bits and sets
- * bit 0 of *d_status (optional int32 on the device).
+ * bit 0 of *d_status (optional int32 on the device); its rows of d_eq, d_Hs,
+ * d_He, d_slope and d_Hest are NOT written (they keep what the caller put
+ * there), in every form of the call below (_ex in both forms, _px, _dn, _llr).
+ * The kernels only ever set bits in *d_status: the caller zeroes it.
  */
 int gf3_demod_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in,
                      const int64_t *d_frame_offsets, int64_t F,

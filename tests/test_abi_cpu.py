@@ -23,6 +23,62 @@ def test_library_exports_every_declared_symbol():
     assert lib.gf3_version() == b"0.1.0"
 
 
+def _c_kind(decl):
+    """One C parameter or return type, without its name, as 'pointer', 'int32', 'int64', 'double' or 'void'."""
+    if "*" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    kinds = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "double": "double", "void": "void"}
+    assert words and words[0] in kinds, f"a type this test does not know: {decl!r}"
+    return kinds[words[0]]
+
+
+def _ctypes_kind(t):
+    import ctypes as C
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    # c_int is c_int32 under another name on every platform this builds for; c_long would not be
+    return {C.c_int: "int32", C.c_int32: "int32", C.c_int64: "int64", C.c_double: "double"}[t]
+
+
+def header_prototypes(text):
+    """{name: (return kind, [parameter kinds])} of every gf3_* function the header declares."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = " ".join(text.split())                                    # continuation lines joined
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)(gf3_[a-z_]+)\s*\(([^()]*)\)\s*;", text):
+        params = [p.strip() for p in params.split(",")]
+        kinds = [] if params == ["void"] else [_c_kind(p) for p in params]
+        assert "void" not in kinds, name
+        ret = ret.replace("extern", " ").replace('"C"', " ").strip()
+        protos[name] = ("pointer" if "*" in ret else _c_kind(ret), kinds)
+    return protos
+
+
+def test_ctypes_signatures_match_the_header():
+    """Return type and every parameter, in order and in number, of every prototype: a pointer stays a pointer, an int32 an
+    int32, an int64 an int64, a double a double.  (ctypes would pass a mismatch on without a word: a double sent as an
+    int64 lands in the wrong register class, an int64 sent as int32 loses its upper half.)"""
+    from gf3_audio_modem_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "gf3rx.h")).read()
+    protos = header_prototypes(hdr)
+    assert set(protos) == set(_lib._SIGS), sorted(set(protos) ^ set(_lib._SIGS))
+    # the parser itself, on prototypes whose answer is written out here
+    assert protos["gf3_version"] == ("pointer", [])
+    assert protos["gf3_ctx_destroy"] == ("void", ["pointer"])
+    assert protos["gf3_sync_stream_workspace_bytes"] == ("int64", ["pointer", "int64"])
+    assert protos["gf3_resample_stream"] == ("int32", ["pointer", "pointer", "int32", "int64", "int64", "double", "int32", "int64",
+                                                      "int64", "pointer", "pointer"])
+    assert protos["gf3_combine_branches"][1][:5] == ["pointer", "int32", "pointer", "int32", "pointer"]
+    for name, (res, args) in _lib._SIGS.items():
+        mine = (_ctypes_kind(res), [_ctypes_kind(a) for a in args])
+        assert mine == protos[name], f"{name}: ctypes says {mine}, the header says {protos[name]}"
+
+
 def test_config_struct_matches_header_order():
     from gf3_audio_modem_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "gf3rx.h")).read()
