@@ -24,6 +24,7 @@ from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
 from .pipeline import check_clock, check_rate, convert_rate, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
+from .pipeline import check_mimo_pilots, plan_mimo
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -60,6 +61,7 @@ class CamG:
     last_tx_report = None                       # set by every transmit() (see papr_reduction below)
     last_input_rate = None                      # set by receive calls once one has run under input_rate (see input_rate below)
     sync_report = None                          # set by every receive call (see sync_rule below)
+    last_mimo_separation = None                 # set by every receive_mimo() (see mimo_advance below)
 
     def __init__(self, mode, encoding="None", no_pilots=20, packet_length=180):
         self.encoding = encoding
@@ -265,6 +267,20 @@ class CamG:
         self.input_rate = None
         self.output_rate = None
         self.rate_taps = 64
+        # both sides, every encoding: 2 x 2 spatial multiplexing.  transmitter.transmit_mimo sends two packets at
+        # once, one per loudspeaker, and returns the stereo signal [2, n]; receiver.receive_mimo separates them from 2 to 4
+        # recordings per carrier, by joint maximum-likelihood detection (Engine.mimo_detect): twice the rate in the same band
+        # and air time.  Speaker 0 sends every chirp, so each recording is synchronised on speaker 0; speaker 1's sound may
+        # arrive earlier than that.  receive_mimo therefore moves every packet start back by mimo_advance samples, so that an
+        # early speaker 1 stays inside the transform window (the channel estimates absorb the shift): 48 samples are 1 ms,
+        # a 34 cm path difference between the speakers.  The advance is taken from the cyclic prefix: advance + the longest
+        # echo must fit cp_length.  no_pilots must be even and >= 2 (speaker 1 negates every other pilot symbol; that is how
+        # the receiver tells the speakers apart).  receive_mimo leaves 1 - |G01|^2 / (G00 G11) per packet pair and carrier
+        # [pairs, C] in `last_mimo_separation`: 1 where the two speakers' channels are orthogonal over the microphones, 0
+        # where they are parallel and nothing separates the streams -- move the speakers apart.  Between two sound cards use
+        # clock_correction: a clock offset leaks one speaker's pilots into the other's estimate.  ValueError for an odd or
+        # zero no_pilots and an advance that is not an integer in [0, cp_length].
+        self.mimo_advance = 48
         self.papr_reduction = False
         self.papr_target_db = 6.0
         self.papr_iterations = 16
@@ -356,21 +372,22 @@ def _as_samples(r):
     return np.ascontiguousarray(r)
 
 
-def _as_recordings(signals):
-    """receive_diversity's input -> B = 1 .. GF3_MAX_BRANCHES one-dimensional recordings, as `_as_samples` gives them."""
+def _as_recordings(signals, who="receive_diversity", least=1):
+    """receive_diversity's (receive_mimo's: least = 2) input -> B = least .. GF3_MAX_BRANCHES one-dimensional recordings, as
+    `_as_samples` gives them."""
     if isinstance(signals, torch.Tensor):
         signals = signals.detach().cpu().numpy()
     if isinstance(signals, np.ndarray) and signals.ndim != 2:
-        raise ValueError(f"receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n], not an array of shape {signals.shape}")
+        raise ValueError(f"{who}: signals must be a sequence of recordings or a 2-D array [B, n], not an array of shape {signals.shape}")
     try:
         B = len(signals)
     except TypeError:
-        raise ValueError("receive_diversity: signals must be a sequence of recordings or a 2-D array [B, n]")
-    if not 1 <= B <= GF3_MAX_BRANCHES:
-        raise ValueError(f"receive_diversity: 1 to {GF3_MAX_BRANCHES} recordings, not {B}")
+        raise ValueError(f"{who}: signals must be a sequence of recordings or a 2-D array [B, n]")
+    if not least <= B <= GF3_MAX_BRANCHES:
+        raise ValueError(f"{who}: {least} to {GF3_MAX_BRANCHES} recordings, not {B}")
     rs = [_as_samples(r) for r in signals]
     if any(r.ndim != 1 for r in rs):
-        raise ValueError("receive_diversity: every recording must be one-dimensional")
+        raise ValueError(f"{who}: every recording must be one-dimensional")
     return rs
 
 
@@ -393,18 +410,23 @@ class transmitter(CamG):
     reproduces the reference's stream; `transmit` runs map + IFFT + CP + framing in the HIP kernel."""
 
     def encode(self, bits):
+        return self._encode(bits, 1)
+
+    def _encode(self, bits, packets):
+        """encode() with the fill brought to a multiple of `packets` packets (1: encode itself; 2: transmit_mimo's pairs)."""
         if self.encoding == "LDPC":
             raise NotImplementedError("LDPC encoding is out of scope (pyldpc; marked broken in the reference, OFDM.py:21)")
         bits = np.asarray(bits)
         chain = self._chain()
         rate = chain.rate()
         if rate is not None:                                           # QC-LDPC (not in the reference): the codewords
-            bits = chain.encode(bits, rate)                            # fill packets like uncoded bits (the fill below)
+            bits = chain.encode(bits, rate, even=True) if packets == 2 else chain.encode(bits, rate)   # fill packets like
+                                                                       # uncoded bits (the fill below)
         if self.encoding == "XOR":                                     # whitening, OFDM.py:163-166
             bits = bits ^ self._xor_mask(bits.shape).astype(bits.dtype)
         # fill the last packet with coin flips (OFDM.py:168-173, 178-185): ONE draw from the legacy global RNG, of
         # exactly the missing length, so a seeded run consumes the generator as the reference does
-        missing = -len(bits) % chain.per_packet
+        missing = -len(bits) % (packets * chain.per_packet)
         bits = np.concatenate([bits, np.random.binomial(n=1, p=0.5, size=(missing,))])
         if self.interleave:                                            # whole packets, the fill included
             sent = self._engine().interleave(torch.from_numpy(bits.astype(np.uint8)))
@@ -573,6 +595,52 @@ class transmitter(CamG):
         time = np.linspace(0, len(signal) / self.fs, len(signal))
         plt.plot(time, 5 * signal, label="Signal")
         plt.title("OFDM Frame"); plt.xlabel("time"); plt.legend(); plt.savefig("OFDM Frame"); plt.show()
+
+    # ---- 2 x 2 spatial multiplexing (not in the reference) ------------------------------------------------------------
+    def transmit_mimo(self, bits):
+        """transmit() for two loudspeakers: packet 2q of the encoded stream goes to speaker 0, packet 2q + 1 to speaker 1,
+        sample-aligned -> float64 [2, n], row s for speaker s.  The bits are encoded as transmit() encodes them; the fill
+        is ONE draw that brings the packets to an even number.  Speaker 0 sends every chirp, the final one included, and
+        speaker 1 is silent for those samples: a receiver synchronises each recording on speaker 0, as ever.  In both
+        pilot blocks of speaker 1 the pilot symbols of odd index (counted from the block's first) are negated; that cover
+        is how receive_mimo tells the two channels apart, so no_pilots must be even and >= 2.  One random_qpsk() draw
+        fills the unused carriers of both speakers.  body_gain and output_rate apply to both rows; `last_tx_report`
+        describes all packets.  ValueError: an odd or zero no_pilots, interleave; NotImplementedError: papr_reduction,
+        bit_loading."""
+        check_mimo_pilots(self.no_pilots)
+        if self.interleave:
+            raise ValueError("transmit_mimo: interleave is not supported with two streams; switch it off")
+        if self.bit_loading is not None:
+            raise NotImplementedError("transmit_mimo with bit_loading: the loaded mapper runs on the host, one stream at a time")
+        if self.papr_reduction:
+            raise NotImplementedError("transmit_mimo with papr_reduction: the reserved tones of two speakers add up in the air")
+        gain, _ = self._check_tx()
+        print("-" * 42 + "\nTRANSMIT\n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        bits_encoded = np.asarray(self._encode(np.asarray(bits), 2), dtype=np.uint8)
+        eng = self._engine()
+        nbp = self.packet_length * self.data_bits_per_symbol
+        self.no_packets = len(bits_encoded) // nbp
+        rand_qpsk = self.random_qpsk()                                  # ONE draw, on both speakers
+        filler = np.zeros(self.K, dtype=complex)
+        filler[self.unused_carriers - 1] = rand_qpsk
+        print("Number of bits to transmit:         " + str(len(bits)))
+        print("Number of OFDM symbols to transmit: " + str(self.no_packets * self.packet_length))
+        packed = np.packbits(bits_encoded.reshape(self.no_packets, nbp), axis=1)
+        rows = eng.tx_frames(packed, filler, out_dtype=torch.float64, body_gain=gain).cpu().numpy()   # [packets, chirp + (2P+D)(N+CP)]
+        self.last_tx_report = self._tx_report(rows, None, gain) if self.no_packets else None
+        Lc, P, D = self.chirp_length, self.no_pilots, self.packet_length
+        first, second = rows[0::2], rows[1::2].copy()
+        second[:, :Lc] = 0.0                                            # speaker 1: silent under the chirps,
+        body = second[:, Lc:].reshape(second.shape[0], 2 * P + D, -1)   # (a view)
+        body[:, 1:P:2] *= -1.0                                          # the cover on the start block
+        body[:, P + D + 1::2] *= -1.0                                   # and on the end block
+        chirp = self.sync_chirp()
+        streams = [np.hstack([first.reshape(-1), chirp]), np.hstack([second.reshape(-1), np.zeros(Lc)])]
+        signal = np.stack([self._at_output_rate(s) for s in streams])
+        print("Number of packets to transmit:      " + str(self.no_packets))
+        return signal
 
     def _transmit_loaded(self, bits, bits_encoded, graph_output, gain=1.0):
         """transmit() under `bit_loading`, on the host (gf3_tx_frames maps one table): the loaded mapper, then the
@@ -744,32 +812,23 @@ class receiver(transmitter):
         """What this call will do with recordings of `lengths` samples, or its refusal (pipeline.plan_receive); no GPU work."""
         return plan_receive(self, self._chain(), lengths, graph_output, diversity)
 
-    def _receive(self, signals, graph_output, diversity, located=None):
-        """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage.
-        located (live.LiveReceiver): (samples on the engine's device, their detections under the local rule, the detections'
-        coefficients) -- step 1 is then skipped: the stream it was cut from has been through it already."""
-        print("-" * 42 + "\nReceive \n" + "-" * 42)
-        print("OFDM Paramters:")
-        print(self)
+    def _receive_engine(self, plan, rs, located=None):
+        """The engine of a receive call on recordings `rs`: by their common sample type, or by the rate conversion's output
+        type (f32 for u8, i16 and f32 recordings) where the plan converts them."""
         if located is None:
-            rs = _as_recordings(signals) if diversity else [_as_samples(signals)]
             dtype = np.result_type(*[r.dtype for r in rs])
         else:
-            rs = [located[0]]
             dtype = torch.empty(0, dtype=located[0].dtype).numpy().dtype
-        plan = self._plan([len(r) for r in rs], graph_output, diversity)
-        rates = plan.rates if located is None else None         # (a located stream has been converted already)
-        if rates:                                               # the conversion's output type: f32 for u8, i16 and f32 recordings
+        if plan.rates and located is None:                      # (a located stream has been converted already)
             dtype = np.dtype("float64") if dtype == np.float64 else np.dtype("float32")
-        eng = self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
-        # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
-        # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
-        # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
-        # stay on the one-shot path.
-        if plan.piecewise:
-            return self._receive_chunked(eng, rs[0], plan.chunk)
-        # 1. sync, every recording on its own
-        # (under input_rate: converted to fs first, every recording by its own rate)
+        return self._engine(dtype if dtype in _NP2T else np.dtype("float64"))
+
+    def _synchronise(self, eng, plan, rs, located=None, who="receive_diversity"):
+        """Step 1 of every receive call: every recording uploaded (under input_rate: converted to fs first, by its own rate)
+        and synchronised on its own, by the plan's rule -> (samples on the device, the packets' first-pilot samples, the
+        detections' coefficients under the local rule or None).  Sets `no_packets`; ValueError where the recordings hold
+        different numbers of packets, or none."""
+        rates = plan.rates if located is None else None         # (a located stream has been converted already)
         xs = [eng._samples(r) if rate is None else convert_rate(eng, r, rate, self.fs) for r, rate in zip(rs, rates or [None] * len(rs))]
         sync_rho = None
         if located is not None:
@@ -781,10 +840,125 @@ class receiver(transmitter):
         starts = [(p + 2)[:-1] for p in peaks]                  # OFDM.py:393-395
         counts = [int(st.numel()) for st in starts]
         if len(set(counts)) != 1:
-            raise ValueError(f"receive_diversity: the recordings hold different numbers of packets: {counts}")
+            raise ValueError(f"{who}: the recordings hold different numbers of packets: {counts}")
         self.no_packets = counts[0]
         if self.no_packets == 0:
             raise ValueError("need at least one array to concatenate")
+        return xs, starts, sync_rho
+
+    # ---- 2 x 2 spatial multiplexing (not in the reference) ------------------------------------------------------------
+    def receive_mimo(self, signals, graph_output=False):
+        """receive() for what transmit_mimo sent: B = 2 .. 4 recordings of the two loudspeakers (the channels of a stereo
+        recording, more microphones), a sequence of one-dimensional recordings or a 2-D array [B, n].  Every recording is
+        synchronised on its own -- on speaker 0, which alone sends the chirps -- under `sync_rule`, after `input_rate`'s
+        conversion, and corrected by `clock_correction` on its own.  Every packet start is then moved back by
+        `mimo_advance` samples.  Per recording the demodulator gives the slope and the ragged flag, Engine.mimo_pilots the
+        two columns of the channel from the covered pilots, Engine.rfft_batch the data symbols' spectra; Engine.mimo_detect
+        separates the two streams by joint maximum likelihood over the 4 x 4 pairs of points, packets at a time so that
+        the spectra stay under 256 MB.  "QCLDPC-*": the LLRs go through decode's chain (LDPC -> CRC -> outer code) and
+        `last_decode_report`; "None" / "XOR": bits = (LLR < 0), then un-whitened.  -> (bits, Hs, He of recording 0's first
+        packet from speaker 0), as receive_diversity().  `no_packets` counts the packet PAIRS found.  Leaves
+        `last_branch_starts` int64 [B, pairs] (before the advance), `last_mimo_separation` float64 [pairs, C], `last_clock_ppm`
+        [B] and `sync_report` as receive_diversity() does.  ValueError: an odd or zero no_pilots, B outside 2 .. 4,
+        recordings with different packet counts, llr_weighting other than "csi", fused_llr, phase_tracking,
+        decoder_feedback, interleave, bit_loading, a mimo_advance that is not an integer in [0, cp_length].
+        NotImplementedError: impulse_blanking, channel_denoising, graph_output, the piece-wise host path of long
+        recordings (or host_chunk_samples)."""
+        print("-" * 42 + "\nReceive \n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        rs = _as_recordings(signals, "receive_mimo", least=2)
+        plan = plan_mimo(self, self._chain(), [len(r) for r in rs], graph_output)
+        eng = self._receive_engine(plan, rs)
+        cfg = eng.cfg
+        # 1. sync, every recording on its own
+        xs, starts, sync_rho = self._synchronise(eng, plan, rs, who="receive_mimo")
+        F, B = self.no_packets, len(rs)
+        # 2. every packet start moved back; per recording: the clock correction, the slope and the ragged flag, the two
+        # columns of the channel
+        slopes, Hs, ragged, stages, first = [], [], [], [], None
+        moved = []
+        for i, (x, st) in enumerate(zip(xs, starts)):
+            st = st - plan.advance
+            stage = {}
+            if plan.clock:
+                x, st, clock_status, stage = correct_clock(eng, x, st, plan.clock)
+                ragged.append(clock_status)
+                xs[i] = x
+            o = eng.demod_frames(x, st, want=("Hs", "He", "slope", "status"))
+            H, status = eng.mimo_pilots(x, st)
+            first = o if first is None else first
+            slopes.append(o["slope"])
+            Hs.append(H)
+            ragged += [o["status"], status]
+            stages.append(stage)
+            moved.append(st)
+        # 3. the data symbols' spectra and the joint detection, packets at a time
+        llr = eng._new((F, 2, cfg.D, cfg.C, cfg.mu), torch.float32)
+        step = max(1, (256 << 20) // (16 * B * cfg.D * (cfg.N // 2 + 1)))
+        within = (cfg.P + torch.arange(cfg.D, dtype=torch.int64, device=eng.device)) * cfg.S + cfg.CP
+        for lo in range(0, F, step):
+            hi = min(lo + step, F)
+            Ys = [eng.rfft_batch(x, (st[lo:hi, None] + within).reshape(-1)) for x, st in zip(xs, moved)]
+            eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi])
+        # 4. decode: the coded chain, or the hard decisions
+        llr = llr.reshape(-1)
+        rows = {}
+        if plan.rate is not None:
+            bits_t, iters, status, bad = plan.chain.decode(plan.chain.code(plan.rate, eng.device), llr)
+            rows.update(_report_rows(iters, status, bad))
+        else:
+            bits_t = (llr < 0).to(torch.int64)
+            if self.encoding == "XOR":
+                bits_t = bits_t ^ torch.from_numpy(self._xor_mask(bits_t.numel())).to(eng.device)
+        # 5. how far apart the speakers stand, from the start-block estimates: 1 - |G01|^2 / (G00 G11) per carrier
+        col = torch.as_tensor(np.asarray(self.data_carriers) - 1, device=eng.device)
+        h = torch.stack([H[:, 0] for H in Hs])[..., col]        # [B, F, 2, C]
+        g00, g11 = (h[:, :, 0].abs() ** 2).sum(dim=0), (h[:, :, 1].abs() ** 2).sum(dim=0)
+        g01 = (h[:, :, 0].conj() * h[:, :, 1]).sum(dim=0)
+        rows["last_mimo_separation"] = 1.0 - g01.abs() ** 2 / (g00 * g11)
+        # 6. everything else the host needs, in ONE small copy behind the kernels
+        rows.update(Hs0=first["Hs"][0], He0=first["He"][0], slope=first["slope"], last_branch_starts=torch.stack(starts))
+        rows.update({name: torch.stack([stage[name] for stage in stages]) for name in stages[0]})
+        if sync_rho is not None:
+            rows["sync_rho"] = torch.stack(list(sync_rho))
+        got = fetch({**rows, "ragged": torch.cat([r.reshape(-1) for r in ragged])})
+        if got["ragged"].any():                                 # (a packet that runs past the recording, or starts before it)
+            raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
+        print("Number of received OFDM symbols:    " + str(2 * F * self.packet_length))
+        bits = bits_t.cpu().numpy().astype(np.int64)
+        self._last_slope = got["slope"]
+        self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
+        if plan.rates is not None or "last_input_rate" in vars(self):
+            self.last_input_rate = None if plan.rates is None else np.array([float(self.fs) if v is None else v[0] for v in plan.rates])
+        for name in ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets"):
+            setattr(self, name, got.get(name))
+        if plan.rate is not None:
+            self.last_decode_report = decode_report(got["iters"], got["status"], plan.chain.outer(), got.get("crc_bad"))
+        print("Number of received bits:            " + str(len(bits)))
+        return bits, got["Hs0"], got["He0"]
+
+    def _receive(self, signals, graph_output, diversity, located=None):
+        """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage.
+        located (live.LiveReceiver): (samples on the engine's device, their detections under the local rule, the detections'
+        coefficients) -- step 1 is then skipped: the stream it was cut from has been through it already."""
+        print("-" * 42 + "\nReceive \n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        if located is None:
+            rs = _as_recordings(signals) if diversity else [_as_samples(signals)]
+        else:
+            rs = [located[0]]
+        plan = self._plan([len(r) for r in rs], graph_output, diversity)
+        eng = self._receive_engine(plan, rs, located)
+        # Long recordings (or when `host_chunk_samples` is set on the receiver) are taken from host memory piece by piece
+        # -- Engine.receive_host: pinned double-buffered upload under the kernels, the global-max rule of OFDM.py:359
+        # kept exact across the pieces -- instead of being uploaded whole; the plots need every packet's symbols and
+        # stay on the one-shot path.
+        if plan.piecewise:
+            return self._receive_chunked(eng, rs[0], plan.chunk)
+        # 1. sync, every recording on its own
+        xs, starts, sync_rho = self._synchronise(eng, plan, rs, located)
         # 2. demodulate, every recording on its own: under impulse_blanking a copy of the samples with the clicks inside the
         # packets' bodies blanked, under clock_correction the packets' bodies at the corrected rate, packed (every recording
         # has its own clock)

@@ -11,6 +11,7 @@ GF3_OK, GF3_EINVAL, GF3_EHIP, GF3_ENOMEM, GF3_ERANGE, GF3_ENODETECT = 0, -1, -2,
 DT_F64, DT_F32, DT_I16, DT_U8 = 0, 1, 2, 3
 GF3_MAX_BRANCHES = 4                    # gf3_combine_branches: branches at most
 GF3_COMBINE_CSI, GF3_COMBINE_NOISE = 0, 1
+GF3_MIMO_STREAMS = 2                    # gf3_mimo_detect: streams sent at once
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -145,6 +146,8 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p]),
     "gf3_combine_branches": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gf3_mimo_pilots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gf3_mimo_detect": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gf3_track_phase": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gf3_feedback_equalise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

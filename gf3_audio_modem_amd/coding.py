@@ -157,9 +157,11 @@ class CodedChain:
         return (int(n),) + Engine.check_feedback_window(hs, hb, self.feedback_min_known)
 
     # ---- transmit side ---------------------------------------------------------------------------------------------------
-    def encode(self, bits, rate):
+    def encode(self, bits, rate, even=False):
         """Message bits -> coded bits (int64, host): zero padding to whole codewords, encoded on the GPU.  Outer code: the
-        smallest packet count whose groups hold the message, zero padding to whole groups, then the parity codewords.
+        smallest packet count whose groups hold the message (the smallest even one under `even`: transmit_mimo sends
+        packets in pairs, and the receiver lays the groups out over the packets it finds), zero padding to whole groups,
+        then the parity codewords.
         `codeword_crc`: a codeword carries k = code.k - 32 of these bits and the CRC of them, parity codewords included."""
         code = self.code(rate)
         gr = self.outer()
@@ -170,7 +172,8 @@ class CodedChain:
         else:
             G, R = gr
             rs = OuterRS(G, R, k)
-            NG = self.outer_layout(packets_for(len(bits), self.per_packet, code.n, k, G, R))[1]
+            F = packets_for(len(bits), self.per_packet, code.n, k, G, R)
+            NG = self.outer_layout(F + (F % 2 if even else 0))[1]
             data = torch.zeros(NG * G * k, dtype=torch.uint8)
             data[: len(bits)] = torch.from_numpy(bits)
             data = data.to(rs.device).reshape(NG, G, k)
@@ -245,6 +248,22 @@ class CodedChain:
             if getattr(self, name):
                 raise ValueError(f"receive_diversity: {name} works on one recording; switch it off")
         return rate
+
+    def check_mimo(self):
+        """What receive_mimo() refuses before any GPU work -> rate.  The joint detector demaps by the context's one table
+        and weights by the channel estimates themselves; the steps that work on one stream's equalised symbols have
+        nothing to work on."""
+        if self.loading is not None:
+            raise ValueError("receive_mimo: bit_loading is not detected jointly (the detector scans the context's one table)")
+        if self.llr_weighting != "csi":
+            raise ValueError(f"receive_mimo: llr_weighting must be 'csi', not {self.llr_weighting!r}: the joint metric carries "
+                             "the channel estimates as its weights")
+        for name in ("fused_llr", "phase_tracking", "decoder_feedback"):
+            if getattr(self, name):
+                raise ValueError(f"receive_mimo: {name} works on one stream's equalised symbols; switch it off")
+        if self.interleave:
+            raise ValueError("receive_mimo: interleave is not supported with two streams; switch it off")
+        return self.check_receive()[0]
 
     def combine(self, eng, outs, points, want="llr"):
         """Receive diversity: the per-branch demodulator outputs (B dicts with 'eq', 'Hs', 'He') -> (maximal-ratio combined

@@ -849,6 +849,59 @@ class Engine:
                                                   _ptr(o.get("eq")), _ptr(o.get("w")), _ptr(o.get("llr")), self._stream()))
         return o
 
+    def mimo_pilots(self, x, frame_offsets):
+        """The two-column pilot estimate of 2 x 2 spatial multiplexing (gf3_mimo_pilots): speaker 1 negates its pilot symbols
+        of odd index, so at one microphone cover t = mean_p (-1)^(t p) Y_p / X is its channel from speaker t.
+        -> (H complex128 [F, 2 sides, 2 covers, K], status int32 [F]): side 0 is the start block, 1 the end block; cover 0 is
+        demod_frames' Hs / He.  status 1 marks a packet whose body leaves the samples at either end; its rows are NaN.
+        Needs an even P >= 2 (ValueError).  Fixed summation order: two calls give identical bytes."""
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F = off.numel()
+        H = self._new((F, 2, _lib.GF3_MIMO_STREAMS, self.cfg.K), torch.complex128)
+        status = self._new((F,), torch.int32)
+        self._check(self.lib.gf3_mimo_pilots(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(H), _ptr(status), self._stream()))
+        return H, status
+
+    def mimo_detect(self, Ys, Hs, slopes, out=None):
+        """Joint max-log ML detection of the two streams of 2 x 2 spatial multiplexing (gf3_mimo_detect) from B = len(Ys)
+        <= 4 recordings: Ys[b] the data symbols' spectra [F*D, N/2+1] as rfft_batch writes them, Hs[b] mimo_pilots' H
+        [F, 2, 2, K], slopes[b] demod_frames' slope [F] of recording b.  Per cell the reference's channel model gives the
+        B x 2 channel entries; the metric sum_b |y_b - h_b0 x0 - h_b1 x1|^2 is minimised over the 4 x 4 pairs of points.
+        A branch whose spectrum value or estimates are not finite at a cell drops out there; where all do, the LLRs are +0.
+        -> float32 [F, 2 streams, D, C, mu]: flattened, the coded order of packets 2f, 2f + 1; LLR > 0 <=> bit 0.  out:
+        optional contiguous float32 tensor of that many elements.  Needs a table of 4 points with mu = 2 (ValueError)."""
+        cfg = self.cfg
+        Ys, Hs, slopes = list(Ys), list(Hs), list(slopes)
+        B = len(Ys)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"mimo_detect: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        if len(Hs) != B or len(slopes) != B:
+            raise ValueError(f"mimo_detect: Hs holds {len(Hs)} branches and slopes {len(slopes)}, Ys {B}")
+        if cfg.mu != 2 or len(self._re) != 4:
+            raise ValueError(f"mimo_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
+                             f"points with mu = {cfg.mu}")
+        Ys = [self._dev(y) for y in Ys]
+        Hs = [self._dev(h) for h in Hs]
+        slopes = [self._dev(s, torch.float64) for s in slopes]
+        NB = cfg.N // 2 + 1
+        if Ys[0].numel() % (cfg.D * NB):
+            raise ValueError("mimo_detect: Ys must be [F*D, N/2+1] for whole packets")
+        F = Ys[0].numel() // (cfg.D * NB)
+        if any(y.numel() != F * cfg.D * NB for y in Ys):
+            raise ValueError("mimo_detect: every branch needs Y [F*D, N/2+1] of the same F")
+        if any(h.numel() != F * 4 * cfg.K for h in Hs):
+            raise ValueError("mimo_detect: every H must be [F, 2, 2, K] for Y [F*D, N/2+1]")
+        if any(s.numel() != F for s in slopes):
+            raise ValueError("mimo_detect: every slope must be [F] for Y [F*D, N/2+1]")
+        shape = (F, _lib.GF3_MIMO_STREAMS, cfg.D, cfg.C, cfg.mu)
+        llr = self._out(out, shape, torch.float32, "F*2*D*C*mu", name="mimo_detect: out")
+
+        def table(xs):
+            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
+        self._check(self.lib.gf3_mimo_detect(self._h, B, table(Ys), table(Hs), table(slopes), F, _ptr(llr), self._stream()))
+        return llr
+
     def noise_estimate2(self, eq):
         """Per-carrier AND per-symbol noise variance of each packet from one pass over eq [F*D, C]
         (gf3_noise_estimate_cs): var_c [F, C] is noise_estimate's output bit for bit, var_s [F, D] the mean over the

@@ -120,6 +120,45 @@ class ReceivePlan(NamedTuple):
     chunk: int                              # samples per piece
     detect: object = None                   # the threshold of the self-normalised detection (sync_rule "local"), or None
     rates: object = None                    # check_input_rates' answer: per recording None or (input rate, half_taps), or None
+    advance: int = 0                        # receive_mimo: samples every packet start is moved back by (`mimo_advance`)
+
+
+def check_mimo_pilots(no_pilots):
+    """The pilot cover of 2 x 2 spatial multiplexing needs an even number of pilot symbols, at least 2 (ValueError)."""
+    if isinstance(no_pilots, (bool, np.bool_)) or not isinstance(no_pilots, (int, np.integer)) or no_pilots < 2 or no_pilots % 2:
+        raise ValueError(f"spatial multiplexing covers the pilots in pairs: no_pilots must be even and >= 2, not {no_pilots!r}")
+    return int(no_pilots)
+
+
+def check_advance(advance, cp_length):
+    """`mimo_advance` -> the samples as an int; ValueError unless it is an integer in [0, cp_length]."""
+    if isinstance(advance, (bool, np.bool_)) or not isinstance(advance, (int, np.integer)) or not 0 <= advance <= cp_length:
+        raise ValueError(f"mimo_advance must be an integer number of samples in [0, cp_length = {cp_length}], not {advance!r}")
+    return int(advance)
+
+
+def plan_mimo(rx, chain, lengths, plots):
+    """The plan of receive_mimo() on recordings of `lengths` samples, in plan_receive's manner and order: the pilot cover's
+    and the coded chain's own refusals (CodedChain.check_mimo), the values of the advance, the clock correction, the sync
+    rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work."""
+    check_mimo_pilots(rx.no_pilots)
+    rate = chain.check_mimo()
+    advance = check_advance(rx.mimo_advance, rx.cp_length)
+    clock = check_clock(rx.clock_correction, rx.clock_taps)
+    detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
+    rates = check_input_rates(rx, len(lengths), True)
+    chunk = getattr(rx, "host_chunk_samples", None)
+    piecewise = bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
+    no_path = ((rx.impulse_blanking, "receive_mimo: impulse_blanking is not applied; blank each recording's samples with "
+                                     "Engine.blank_impulses first"),
+               (rx.channel_denoising, "receive_mimo: channel_denoising cleans one column of the channel; the two covers have "
+                                      "no denoiser"),
+               (plots, "receive_mimo: no plots; receive() one stream for them"),
+               (piecewise, "receive_mimo: {host} separates nothing; receive shorter recordings"))
+    for on, why in no_path:
+        if on:
+            raise NotImplementedError(why.format(host=_HOST))
+    return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance)
 
 
 def plan_receive(rx, chain, lengths, plots, diversity):

@@ -688,6 +688,47 @@ int gf3_combine_branches(gf3_ctx *ctx, int32_t B, const void *const *d_eq_c128, 
                          int64_t F, void *d_eq_out_c128, double *d_wsum_f64, float *d_llr_f32, void *stream);
 
 /*
+ * 2 x 2 spatial multiplexing (not in the reference): two packets sent at once, one per loudspeaker, sample-aligned, and
+ * separated per carrier from B >= 1 recordings (B >= 2 to separate two streams that both carry data).  Speaker 0 sends
+ * every chirp and its pilots as they are; speaker 1 is silent during the chirps and negates its pilot symbols of odd index
+ * p (counted from each block's first symbol).  At microphone b the pilots then read Y_p[k] = (H_b0[k] + (-1)^p H_b1[k]) X[k],
+ * so for an even P the two covers
+ *     cover t:  mean_p (-1)^(t p) Y_p[k] / X[k],  t = 0, 1
+ * are the two columns H_b0, H_b1 of the channel; cover 0 is what gf3_demod_frames returns as Hs / He.
+ *   - gf3_mimo_pilots: d_H_out_c128 [F][2 sides][2 covers][K] complex128 (side 0: the start block, 1: the end block) from the
+ *     samples d_in [n_in] of the context's type and the packets' first-pilot offsets.  Per (packet, side) the signed
+ *     time-domain sums sum_p (-1)^(t p) x_p[n] of the P pilot symbols without their prefix (p ascending), one real transform
+ *     each, times 1 / (P known_k).  d_status_i32 [F]: 1 for a packet whose body [offset, offset + (2P + D)(N + CP)) leaves
+ *     [0, n_in) at either end, else 0; such a packet's rows are NaN in both parts, never left unwritten.
+ *     GF3_EINVAL for a context whose P is odd or < 2, a null pointer with F > 0, F < 0, n_in < 0, more than 2^30 - 1
+ *     packets.  F == 0 is a no-op.
+ *   - gf3_mimo_detect: joint max-log ML detection of the two streams' symbols over the 4 x 4 pairs of constellation points.
+ *     Inputs are HOST arrays of B device pointers (read during the call only), 1 <= B <= GF3_MAX_BRANCHES:
+ *       d_Y_c128[b]     [F*D, N/2+1]  the data symbols' spectra as gf3_rfft_batch writes them; data carrier c is read at
+ *                                     bin data_bins[c]
+ *       d_H_c128[b]     [F, 2, 2, K]  gf3_mimo_pilots' output for recording b
+ *       d_slope_f64[b]  [F]           gf3_demod_frames' slope for recording b (one pair of clocks: it serves both columns)
+ *     Per cell (f, l, c), with n = data_bins[c] - 1, f_l = (l + P/2) / (D + P), and for each of the B x 2 entries the
+ *     reference's channel model from its start and end estimates Hs, He:
+ *       h_bt = (|Hs| + (|He| - |Hs|) f_l) (Hs / |Hs|) exp(i slope_b n f_l)        (Hs / |Hs| = 1 where |Hs| = 0)
+ *       G00 = sum_b |h_b0|^2,  G11 = sum_b |h_b1|^2,  G01 = sum_b conj(h_b0) h_b1,  m_t = sum_b conj(h_bt) y_b   (b ascending)
+ *       metric(x0, x1) = G00 |x0|^2 + G11 |x1|^2 + 2 Re(conj(x0) G01 x1) - 2 Re(conj(x0) m0) - 2 Re(conj(x1) m1)
+ *       LLR of a bit of stream s = min over the pairs with that bit 1 - min over the pairs with that bit 0      (> 0: bit 0)
+ *     which is sum_b |y_b - h_b0 x0 - h_b1 x1|^2 less the term without x.  A branch whose y_b, whose slope or any of whose
+ *     four estimates at the cell is not finite is left out of every sum; where every branch is, the four LLRs are +0.
+ *     d_llr_f32 [F][GF3_MIMO_STREAMS][D][C][mu] float32: flattened, the coded order of packets 2f and 2f + 1.
+ *     GF3_EINVAL for a null context, a context whose table is not mu = 2 with 4 points, B out of range, a null pointer,
+ *     F < 0, more than 65535 packets.  F == 0 is a no-op.
+ *   Both: one launch, no allocation, no host synchronisation, asynchronous on `stream`; every sum in a fixed order, no
+ *   atomics: two calls give identical bytes.  The text of a refusal names the function.
+ */
+#define GF3_MIMO_STREAMS 2
+int gf3_mimo_pilots(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                    void *d_H_out_c128, int32_t *d_status_i32, void *stream);
+int gf3_mimo_detect(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const void *const *d_H_c128,
+                    const double *const *d_slope_f64, int64_t F, float *d_llr_f32, void *stream);
+
+/*
  * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
  * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
  * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
