@@ -24,7 +24,7 @@ from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
 from .pipeline import check_clock, check_rate, convert_rate, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
-from .pipeline import check_mimo_pilots, plan_mimo
+from .pipeline import check_mimo_pilots, check_stbc_length, plan_mimo, plan_stbc
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -62,6 +62,7 @@ class CamG:
     last_input_rate = None                      # set by receive calls once one has run under input_rate (see input_rate below)
     sync_report = None                          # set by every receive call (see sync_rule below)
     last_mimo_separation = None                 # set by every receive_mimo() (see mimo_advance below)
+    last_stbc_slope = None                      # set by every receive_stbc(): the joint phase slope per packet, float64 [F]
 
     def __init__(self, mode, encoding="None", no_pilots=20, packet_length=180):
         self.encoding = encoding
@@ -642,6 +643,65 @@ class transmitter(CamG):
         print("Number of packets to transmit:      " + str(self.no_packets))
         return signal
 
+    # ---- transmit diversity: two speakers, one microphone (not in the reference) -----------------------------------------
+    def transmit_stbc(self, bits):
+        """transmit() for two loudspeakers and ONE stream, for a listener with one microphone: the Alamouti space-time block
+        code over pairs of data symbols -> float64 [2, n], row s for speaker s.  The bits are encoded as transmit() encodes
+        them.  Chirps, pilots and cover are transmit_mimo's: speaker 0 sends every chirp, speaker 1 is silent under them and
+        negates its pilot symbols of odd index, so no_pilots must be even and >= 2; one random_qpsk() draw fills the unused
+        carriers of both speakers.  With X_l the spectrum of data symbol l of a packet, filler included, speaker 0 sends
+        X_2j then -conj(X_(2j+1)) and speaker 1 X_(2j+1) then conj(X_2j); the symbols are real, so conj(X) is the N-sample
+        body reversed in time, x[(-n) mod N], under a prefix rebuilt from it -- host work on Engine.tx_frames' rows.
+        packet_length must be even.  Through two paths H0, H1 one microphone then sees |H0|^2 + |H1|^2 per carrier
+        (receive_stbc).  body_gain and output_rate apply to both rows; `last_tx_report` describes the packets as speaker 0
+        sends them.  ValueError: an odd or zero no_pilots, an odd packet_length, interleave; NotImplementedError:
+        papr_reduction, bit_loading."""
+        check_mimo_pilots(self.no_pilots)
+        check_stbc_length(self.packet_length)
+        if self.interleave:
+            raise ValueError("transmit_stbc: interleave is not supported with the space-time code; switch it off")
+        if self.bit_loading is not None:
+            raise NotImplementedError("transmit_stbc with bit_loading: the loaded mapper runs on the host, one stream at a time")
+        if self.papr_reduction:
+            raise NotImplementedError("transmit_stbc with papr_reduction: the reserved tones of two speakers add up in the air")
+        gain, _ = self._check_tx()
+        print("-" * 42 + "\nTRANSMIT\n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        bits_encoded = np.asarray(self._encode(np.asarray(bits), 1), dtype=np.uint8)
+        eng = self._engine()
+        nbp = self.packet_length * self.data_bits_per_symbol
+        self.no_packets = len(bits_encoded) // nbp
+        rand_qpsk = self.random_qpsk()                                  # ONE draw, on both speakers
+        filler = np.zeros(self.K, dtype=complex)
+        filler[self.unused_carriers - 1] = rand_qpsk
+        print("Number of bits to transmit:         " + str(len(bits)))
+        print("Number of OFDM symbols to transmit: " + str(self.no_packets * self.packet_length))
+        packed = np.packbits(bits_encoded.reshape(self.no_packets, nbp), axis=1)
+        rows = eng.tx_frames(packed, filler, out_dtype=torch.float64, body_gain=gain).cpu().numpy()   # [packets, chirp + (2P+D)(N+CP)]
+        Lc, P, D, CP = self.chirp_length, self.no_pilots, self.packet_length, self.cp_length
+        first, second = rows.copy(), rows.copy()
+        second[:, :Lc] = 0.0                                            # speaker 1: silent under the chirps,
+        b0 = first[:, Lc:].reshape(rows.shape[0], 2 * P + D, -1)        # (views)
+        b1 = second[:, Lc:].reshape(rows.shape[0], 2 * P + D, -1)
+        b1[:, 1:P:2] *= -1.0                                            # the cover on the start block
+        b1[:, P + D + 1::2] *= -1.0                                     # and on the end block
+
+        def reversed_in_time(sym):                                      # conj of a real symbol's spectrum: x[(-n) mod N]
+            rev = np.roll(sym[..., CP:][..., ::-1], 1, axis=-1)
+            return np.concatenate([rev[..., rev.shape[-1] - CP:], rev], axis=-1)
+        data = rows[:, Lc:].reshape(rows.shape[0], 2 * P + D, -1)[:, P:P + D]
+        even, odd = data[:, 0::2], data[:, 1::2]
+        b0[:, P + 1:P + D:2] = -reversed_in_time(odd)
+        b1[:, P:P + D:2] = odd
+        b1[:, P + 1:P + D:2] = reversed_in_time(even)
+        self.last_tx_report = self._tx_report(first, None, gain) if self.no_packets else None
+        chirp = self.sync_chirp()
+        streams = [np.hstack([first.reshape(-1), chirp]), np.hstack([second.reshape(-1), np.zeros(Lc)])]
+        signal = np.stack([self._at_output_rate(s) for s in streams])
+        print("Number of packets to transmit:      " + str(self.no_packets))
+        return signal
+
     def _transmit_loaded(self, bits, bits_encoded, graph_output, gain=1.0):
         """transmit() under `bit_loading`, on the host (gf3_tx_frames maps one table): the loaded mapper, then the
         reference's own steps -- build_OFDM_symbol (which draws the unused-carrier filler), ifft, add_cp, send_to_stream;
@@ -873,9 +933,32 @@ class receiver(transmitter):
         cfg = eng.cfg
         # 1. sync, every recording on its own
         xs, starts, sync_rho = self._synchronise(eng, plan, rs, who="receive_mimo")
-        F, B = self.no_packets, len(rs)
+        F = self.no_packets
         # 2. every packet start moved back; per recording: the clock correction, the slope and the ragged flag, the two
         # columns of the channel
+        slopes, Hs, ragged, stages, first, moved = self._covered_estimates(eng, plan, xs, starts)
+        # 3. the data symbols' spectra and the joint detection, packets at a time
+        llr = eng._new((F, 2, cfg.D, cfg.C, cfg.mu), torch.float32)
+        for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
+            eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi])
+        # 4. decode: the coded chain, or the hard decisions
+        bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
+        # 5. how far apart the speakers stand, from the start-block estimates: 1 - |G01|^2 / (G00 G11) per carrier
+        col = torch.as_tensor(np.asarray(self.data_carriers) - 1, device=eng.device)
+        h = torch.stack([H[:, 0] for H in Hs])[..., col]        # [B, F, 2, C]
+        g00, g11 = (h[:, :, 0].abs() ** 2).sum(dim=0), (h[:, :, 1].abs() ** 2).sum(dim=0)
+        g01 = (h[:, :, 0].conj() * h[:, :, 1]).sum(dim=0)
+        rows["last_mimo_separation"] = 1.0 - g01.abs() ** 2 / (g00 * g11)
+        # 6. everything else the host needs, in ONE small copy behind the kernels
+        return self._publish_covered(plan, rows, first, starts, stages, sync_rho, ragged, bits_t, 2 * F * self.packet_length,
+                             ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets"))
+
+    # ---- the steps receive_mimo and receive_stbc share ------------------------------------------------------------------
+    def _covered_estimates(self, eng, plan, xs, starts):
+        """Step 2 of both: every packet start moved back by the plan's advance; per recording the clock correction (xs[i] is
+        replaced by the corrected samples), the demodulator for the slope, the ragged flag and the returned Hs / He, and
+        Engine.mimo_pilots for the two columns of the channel -> (slopes, Hs, ragged flags, clock stages, recording 0's
+        demodulator outputs, the moved starts)."""
         slopes, Hs, ragged, stages, first = [], [], [], [], None
         moved = []
         for i, (x, st) in enumerate(zip(xs, starts)):
@@ -893,16 +976,20 @@ class receiver(transmitter):
             ragged += [o["status"], status]
             stages.append(stage)
             moved.append(st)
-        # 3. the data symbols' spectra and the joint detection, packets at a time
-        llr = eng._new((F, 2, cfg.D, cfg.C, cfg.mu), torch.float32)
-        step = max(1, (256 << 20) // (16 * B * cfg.D * (cfg.N // 2 + 1)))
+        return slopes, Hs, ragged, stages, first, moved
+
+    def _data_spectra(self, eng, xs, moved, F):
+        """Step 3 of both: (lo, hi, the B recordings' data-symbol spectra of packets lo .. hi - 1), packets at a time so that
+        the spectra stay under 256 MB."""
+        cfg = eng.cfg
+        step = max(1, (256 << 20) // (16 * len(xs) * cfg.D * (cfg.N // 2 + 1)))
         within = (cfg.P + torch.arange(cfg.D, dtype=torch.int64, device=eng.device)) * cfg.S + cfg.CP
         for lo in range(0, F, step):
             hi = min(lo + step, F)
-            Ys = [eng.rfft_batch(x, (st[lo:hi, None] + within).reshape(-1)) for x, st in zip(xs, moved)]
-            eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi])
-        # 4. decode: the coded chain, or the hard decisions
-        llr = llr.reshape(-1)
+            yield lo, hi, [eng.rfft_batch(x, (st[lo:hi, None] + within).reshape(-1)) for x, st in zip(xs, moved)]
+
+    def _decode_llrs(self, eng, plan, llr):
+        """Step 4 of both: the coded chain, or the hard decisions with the un-whitening -> (bits on the device, report rows)"""
         rows = {}
         if plan.rate is not None:
             bits_t, iters, status, bad = plan.chain.decode(plan.chain.code(plan.rate, eng.device), llr)
@@ -911,13 +998,11 @@ class receiver(transmitter):
             bits_t = (llr < 0).to(torch.int64)
             if self.encoding == "XOR":
                 bits_t = bits_t ^ torch.from_numpy(self._xor_mask(bits_t.numel())).to(eng.device)
-        # 5. how far apart the speakers stand, from the start-block estimates: 1 - |G01|^2 / (G00 G11) per carrier
-        col = torch.as_tensor(np.asarray(self.data_carriers) - 1, device=eng.device)
-        h = torch.stack([H[:, 0] for H in Hs])[..., col]        # [B, F, 2, C]
-        g00, g11 = (h[:, :, 0].abs() ** 2).sum(dim=0), (h[:, :, 1].abs() ** 2).sum(dim=0)
-        g01 = (h[:, :, 0].conj() * h[:, :, 1]).sum(dim=0)
-        rows["last_mimo_separation"] = 1.0 - g01.abs() ** 2 / (g00 * g11)
-        # 6. everything else the host needs, in ONE small copy behind the kernels
+        return bits_t, rows
+
+    def _publish_covered(self, plan, rows, first, starts, stages, sync_rho, ragged, bits_t, symbols, names):
+        """The last step of both: everything the host needs in ONE small copy behind the kernels, the ragged refusal, the
+        attributes `names` (the fetched value or None) -> (bits, Hs, He of recording 0's first packet from speaker 0)."""
         rows.update(Hs0=first["Hs"][0], He0=first["He"][0], slope=first["slope"], last_branch_starts=torch.stack(starts))
         rows.update({name: torch.stack([stage[name] for stage in stages]) for name in stages[0]})
         if sync_rho is not None:
@@ -925,18 +1010,52 @@ class receiver(transmitter):
         got = fetch({**rows, "ragged": torch.cat([r.reshape(-1) for r in ragged])})
         if got["ragged"].any():                                 # (a packet that runs past the recording, or starts before it)
             raise ValueError("all the input array dimensions except for the concatenation axis must match exactly")
-        print("Number of received OFDM symbols:    " + str(2 * F * self.packet_length))
+        print("Number of received OFDM symbols:    " + str(symbols))
         bits = bits_t.cpu().numpy().astype(np.int64)
         self._last_slope = got["slope"]
         self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
         if plan.rates is not None or "last_input_rate" in vars(self):
             self.last_input_rate = None if plan.rates is None else np.array([float(self.fs) if v is None else v[0] for v in plan.rates])
-        for name in ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets"):
+        for name in names:
             setattr(self, name, got.get(name))
         if plan.rate is not None:
             self.last_decode_report = decode_report(got["iters"], got["status"], plan.chain.outer(), got.get("crc_bad"))
         print("Number of received bits:            " + str(len(bits)))
         return bits, got["Hs0"], got["He0"]
+
+    # ---- transmit diversity: two speakers, one microphone (not in the reference) -----------------------------------------
+    def receive_stbc(self, signals, graph_output=False):
+        """receive() for what transmit_stbc sent: B = 1 .. 4 recordings of the two loudspeakers -- ONE microphone is the
+        point --, a sequence of one-dimensional recordings or a 2-D array [B, n].  The steps are receive_mimo's: every
+        recording synchronised on its own (on speaker 0, which alone sends the chirps) under `sync_rule`, after
+        `input_rate`'s conversion, corrected by `clock_correction` on its own; every packet start moved back by
+        `mimo_advance` samples; Engine.mimo_pilots for the two columns of the channel; Engine.rfft_batch for the data
+        symbols' spectra, packets at a time under 256 MB.  Then ONE phase slope per packet from all paths together
+        (Engine.stbc_slope: the demodulator is still called for the ragged flag and the returned Hs / He, its slope --
+        fitted on one path, which breaks at that path's nulls -- is not used) and the joint maximum-likelihood detection of
+        every Alamouti pair (Engine.stbc_detect).  "QCLDPC-*": the LLRs go through decode's chain and `last_decode_report`;
+        "None" / "XOR": bits = (LLR < 0), then un-whitened.  -> (bits, Hs, He of recording 0's first packet from speaker 0).
+        `no_packets` counts the packets found.  Leaves `last_branch_starts` int64 [B, F] (before the advance),
+        `last_stbc_slope` float64 [F], `last_clock_ppm` [B] and `sync_report` as receive_mimo() does.  ValueError: what
+        receive_mimo refuses, an odd packet_length, B outside 1 .. 4.  NotImplementedError: as receive_mimo."""
+        print("-" * 42 + "\nReceive \n" + "-" * 42)
+        print("OFDM Paramters:")
+        print(self)
+        rs = _as_recordings(signals, "receive_stbc")
+        plan = plan_stbc(self, self._chain(), [len(r) for r in rs], graph_output)
+        eng = self._receive_engine(plan, rs)
+        cfg = eng.cfg
+        xs, starts, sync_rho = self._synchronise(eng, plan, rs, who="receive_stbc")
+        F = self.no_packets
+        _, Hs, ragged, stages, first, moved = self._covered_estimates(eng, plan, xs, starts)
+        slope = eng.stbc_slope(Hs)
+        llr = eng._new((F, cfg.D, cfg.C, cfg.mu), torch.float32)
+        for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
+            eng.stbc_detect(Ys, [H[lo:hi] for H in Hs], slope[lo:hi], out=llr[lo:hi])
+        bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
+        rows["last_stbc_slope"] = slope
+        return self._publish_covered(plan, rows, first, starts, stages, sync_rho, ragged, bits_t, F * self.packet_length,
+                             ("last_branch_starts", "last_stbc_slope", "last_clock_ppm", "last_clock_ppm_packets"))
 
     def _receive(self, signals, graph_output, diversity, located=None):
         """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage.

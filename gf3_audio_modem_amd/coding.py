@@ -249,20 +249,20 @@ class CodedChain:
                 raise ValueError(f"receive_diversity: {name} works on one recording; switch it off")
         return rate
 
-    def check_mimo(self):
-        """What receive_mimo() refuses before any GPU work -> rate.  The joint detector demaps by the context's one table
-        and weights by the channel estimates themselves; the steps that work on one stream's equalised symbols have
-        nothing to work on."""
+    def check_mimo(self, who="receive_mimo", what="two streams"):
+        """What receive_mimo() (and, as `who`, receive_stbc(), which sends `what` = "the space-time code") refuses before any
+        GPU work -> rate.  The joint detector demaps by the context's one table and weights by the channel estimates
+        themselves; the steps that work on one stream's equalised symbols have nothing to work on."""
         if self.loading is not None:
-            raise ValueError("receive_mimo: bit_loading is not detected jointly (the detector scans the context's one table)")
+            raise ValueError(f"{who}: bit_loading is not detected jointly (the detector scans the context's one table)")
         if self.llr_weighting != "csi":
-            raise ValueError(f"receive_mimo: llr_weighting must be 'csi', not {self.llr_weighting!r}: the joint metric carries "
+            raise ValueError(f"{who}: llr_weighting must be 'csi', not {self.llr_weighting!r}: the joint metric carries "
                              "the channel estimates as its weights")
         for name in ("fused_llr", "phase_tracking", "decoder_feedback"):
             if getattr(self, name):
-                raise ValueError(f"receive_mimo: {name} works on one stream's equalised symbols; switch it off")
+                raise ValueError(f"{who}: {name} works on one stream's equalised symbols; switch it off")
         if self.interleave:
-            raise ValueError("receive_mimo: interleave is not supported with two streams; switch it off")
+            raise ValueError(f"{who}: interleave is not supported with {what}; switch it off")
         return self.check_receive()[0]
 
     def combine(self, eng, outs, points, want="llr"):

@@ -23,6 +23,8 @@
 //   gf3rx_combine.hip        combine_kernel + gf3_combine_branches (receive diversity: maximal-ratio combining of B branches' symbols)
 //   gf3rx_mimo.hip           mimo_pilots_kernel, mimo_detect_kernel + gf3_mimo_pilots, gf3_mimo_detect (2 x 2 spatial multiplexing: both
 //                            columns of the channel from the covered pilots; joint max-log ML detection of the two streams)
+//   gf3rx_stbc.hip           stbc_slope_kernel, stbc_detect_kernel + gf3_stbc_slope, gf3_stbc_detect (transmit diversity: the Alamouti code over
+//                            pairs of data symbols; one phase slope from all paths, joint max-log ML detection of a pair)
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)
 //   gf3rx_feedback.hip       feedback_kernel + gf3_feedback_equalise (residual channel from re-encoded codewords, divided out)
 //   gf3rx_blank.hip          blank_stats_kernel, blank_level_kernel, blank_write_kernel + gf3_blank_impulses (impulse blanking of the samples)

@@ -902,6 +902,83 @@ class Engine:
         self._check(self.lib.gf3_mimo_detect(self._h, B, table(Ys), table(Hs), table(slopes), F, _ptr(llr), self._stream()))
         return llr
 
+    def _stbc_geometry(self, who):
+        """What both calls of transmit diversity refuse of a context: the pilot cover and the pairing of the data symbols."""
+        cfg = self.cfg
+        if cfg.P < 2 or cfg.P % 2:
+            raise ValueError(f"{who}: the two covers need an even number of pilot symbols, P >= 2, not {cfg.P}")
+        if cfg.D % 2:
+            raise ValueError(f"{who}: the code pairs the data symbols: an even D, not {cfg.D}")
+
+    def _stbc_estimates(self, Hs, who, F=None):
+        """Hs -> (B tensors on the device, B, F): 1 to GF3_MAX_BRANCHES arrays [F, 2, 2, K] of one F."""
+        Hs = list(Hs)
+        B = len(Hs)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"{who}: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        Hs = [self._dev(h) for h in Hs]
+        per = 4 * self.cfg.K
+        if F is None:
+            if Hs[0].numel() % per:
+                raise ValueError(f"{who}: every H must be [F, 2, 2, K]")
+            F = Hs[0].numel() // per
+        if any(h.numel() != F * per for h in Hs):
+            raise ValueError(f"{who}: every H must be [F, 2, 2, K] of the same F")
+        return Hs, B, F
+
+    def stbc_slope(self, Hs):
+        """The joint phase slope of transmit diversity (gf3_stbc_slope) from B = len(Hs) <= 4 recordings' mimo_pilots output
+        [F, 2, 2, K]: per packet d[k] = sum_b sum_t conj(H_b[f, 0, t, k]) H_b[f, 1, t, k], y = unwrap(angle d), the
+        first-degree least-squares coefficient of y over the context's [fit_lo, fit_hi) -- what demod_frames' slope means,
+        fitted once on all paths together, so it breaks only where every path has a null.  -> float64 [F]; NaN for a packet
+        with a non-finite d in the fit range.  Needs an even P >= 2 and an even D (ValueError).  Fixed summation order: two
+        calls give identical bytes."""
+        self._stbc_geometry("stbc_slope")
+        Hs, B, F = self._stbc_estimates(Hs, "stbc_slope")
+        slope = self._new((F,), torch.float64)
+        table = (C.c_void_p * B)(*[h.data_ptr() for h in Hs])
+        self._check(self.lib.gf3_stbc_slope(self._h, B, table, F, _ptr(slope), self._stream()))
+        return slope
+
+    def stbc_detect(self, Ys, Hs, slope, out=None):
+        """Joint max-log ML detection of the Alamouti pairs of transmit diversity (gf3_stbc_detect) from B = len(Ys) <= 4
+        recordings: Ys[b] the data symbols' spectra [F*D, N/2+1] as rfft_batch writes them, Hs[b] mimo_pilots' H
+        [F, 2, 2, K], slope ONE array [F] for every branch (stbc_slope).  Symbols 2j and 2j + 1 of a packet carry x0, x1 as
+        (x0, x1) then (-conj(x1), conj(x0)) on the two speakers; per carrier the statistics of both slots and all branches go
+        into mimo_detect's metric over the 4 x 4 pairs of points.  A branch whose spectrum value at either slot or whose
+        estimates are not finite drops out of the pair; where all do (or the slope is not finite), the LLRs are +0.
+        -> float32 [F, D, C, mu]: flattened, the coded order of one stream; LLR > 0 <=> bit 0.  out: optional contiguous
+        float32 tensor of that many elements.  Needs a table of 4 points with mu = 2, an even P >= 2, an even D (ValueError)."""
+        cfg = self.cfg
+        Ys = list(Ys)
+        B = len(Ys)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"stbc_detect: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        Hs = list(Hs)
+        if len(Hs) != B:
+            raise ValueError(f"stbc_detect: Hs holds {len(Hs)} branches, Ys {B}")
+        if cfg.mu != 2 or len(self._re) != 4:
+            raise ValueError(f"stbc_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
+                             f"points with mu = {cfg.mu}")
+        self._stbc_geometry("stbc_detect")
+        Ys = [self._dev(y) for y in Ys]
+        NB = cfg.N // 2 + 1
+        if Ys[0].numel() % (cfg.D * NB):
+            raise ValueError("stbc_detect: Ys must be [F*D, N/2+1] for whole packets")
+        F = Ys[0].numel() // (cfg.D * NB)
+        if any(y.numel() != F * cfg.D * NB for y in Ys):
+            raise ValueError("stbc_detect: every branch needs Y [F*D, N/2+1] of the same F")
+        Hs, _, _ = self._stbc_estimates(Hs, "stbc_detect", F)
+        slope = self._dev(slope, torch.float64)
+        if slope.numel() != F:
+            raise ValueError("stbc_detect: the slope must be ONE array [F] for Y [F*D, N/2+1]")
+        llr = self._out(out, (F, cfg.D, cfg.C, cfg.mu), torch.float32, "F*D*C*mu", name="stbc_detect: out")
+
+        def table(xs):
+            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
+        self._check(self.lib.gf3_stbc_detect(self._h, B, table(Ys), table(Hs), _ptr(slope), F, _ptr(llr), self._stream()))
+        return llr
+
     def noise_estimate2(self, eq):
         """Per-carrier AND per-symbol noise variance of each packet from one pass over eq [F*D, C]
         (gf3_noise_estimate_cs): var_c [F, C] is noise_estimate's output bit for bit, var_s [F, D] the mean over the

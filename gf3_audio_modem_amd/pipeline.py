@@ -137,28 +137,43 @@ def check_advance(advance, cp_length):
     return int(advance)
 
 
-def plan_mimo(rx, chain, lengths, plots):
+def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams", verb="separates"):
     """The plan of receive_mimo() on recordings of `lengths` samples, in plan_receive's manner and order: the pilot cover's
     and the coded chain's own refusals (CodedChain.check_mimo), the values of the advance, the clock correction, the sync
-    rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work."""
+    rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work.  (plan_stbc names
+    itself in `who`.)"""
     check_mimo_pilots(rx.no_pilots)
-    rate = chain.check_mimo()
+    rate = chain.check_mimo(who, what)
     advance = check_advance(rx.mimo_advance, rx.cp_length)
     clock = check_clock(rx.clock_correction, rx.clock_taps)
     detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
     rates = check_input_rates(rx, len(lengths), True)
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
-    no_path = ((rx.impulse_blanking, "receive_mimo: impulse_blanking is not applied; blank each recording's samples with "
+    no_path = ((rx.impulse_blanking, f"{who}: impulse_blanking is not applied; blank each recording's samples with "
                                      "Engine.blank_impulses first"),
-               (rx.channel_denoising, "receive_mimo: channel_denoising cleans one column of the channel; the two covers have "
+               (rx.channel_denoising, f"{who}: channel_denoising cleans one column of the channel; the two covers have "
                                       "no denoiser"),
-               (plots, "receive_mimo: no plots; receive() one stream for them"),
-               (piecewise, "receive_mimo: {host} separates nothing; receive shorter recordings"))
+               (plots, f"{who}: no plots; receive() one stream for them"),
+               (piecewise, f"{who}: {{host}} {verb} nothing; receive shorter recordings"))
     for on, why in no_path:
         if on:
             raise NotImplementedError(why.format(host=_HOST))
     return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance)
+
+
+def check_stbc_length(packet_length):
+    """The Alamouti code pairs the data symbols: an even packet_length (ValueError)."""
+    if packet_length % 2:
+        raise ValueError(f"the space-time code pairs the data symbols: packet_length must be even, not {packet_length!r}")
+    return int(packet_length)
+
+
+def plan_stbc(rx, chain, lengths, plots):
+    """The plan of receive_stbc(): plan_mimo's checks under its own name, and the pairing of the data symbols."""
+    plan = plan_mimo(rx, chain, lengths, plots, "receive_stbc", "the space-time code", "decodes")
+    check_stbc_length(rx.packet_length)
+    return plan
 
 
 def plan_receive(rx, chain, lengths, plots, diversity):

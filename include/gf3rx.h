@@ -729,6 +729,47 @@ int gf3_mimo_detect(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const 
                     const double *const *d_slope_f64, int64_t F, float *d_llr_f32, void *stream);
 
 /*
+ * Transmit diversity (not in the reference): two loudspeakers, B >= 1 recordings -- one microphone is the point -- and the
+ * Alamouti space-time block code over pairs of data symbols.  ONE stream is sent.  Chirps, pilots and cover are those of
+ * spatial multiplexing above (P even and >= 2), so gf3_mimo_pilots gives both columns H_b0, H_b1 of every recording.  D is
+ * even; with X_l the spectrum of data symbol l, for j = 0 .. D/2 - 1
+ *     slot a = 2j:       speaker 0 sends  X_a,          speaker 1  X_b'
+ *     slot b' = 2j + 1:  speaker 0 sends  -conj(X_b'),  speaker 1  conj(X_a)
+ * (the symbols are real: conj(X) is the N-sample body reversed in time, x[(-n) mod N], under a prefix rebuilt from it).  Per
+ * carrier, with x0, x1 the points of symbols a and b':  y_a = h0(a) x0 + h1(a) x1,  conj(y_b') = conj(h1(b')) x0 - conj(h0(b')) x1,
+ * and a single microphone sees |H0|^2 + |H1|^2 where one speaker gives |H0|^2 and the same signal on both |H0 + H1|^2.
+ *   - gf3_stbc_slope: the phase the channel gains per carrier between the two pilot blocks -- what gf3_demod_frames' slope
+ *     means -- fitted ONCE per packet on all paths together.  d_H_c128 is a HOST array of B device pointers (read during
+ *     the call only), 1 <= B <= GF3_MAX_BRANCHES, each gf3_mimo_pilots' output [F, 2, 2, K].  Per packet f
+ *       d[k] = sum_b sum_t conj(H_b[f, 0, t, k]) H_b[f, 1, t, k]                 (b, then t, ascending)
+ *       y = unwrap(angle d) along k;  slope = the first-degree least-squares coefficient of y over [fit_lo, fit_hi)
+ *     with the demodulator's own angle, unwrap correction and cumulative-correction fit.  The clock drift it measures is
+ *     common to every path, and d has a null only where every path has one, where the angle series of ONE path breaks at
+ *     that path's nulls.  d_slope_f64 [F]; NaN for a packet with a d[k] of the fit range that is not finite.  One workgroup
+ *     per packet.  GF3_EINVAL for a null context, an odd P or P < 2, an odd D, B out of range, a null pointer, F < 0, more
+ *     than 2^30 - 1 packets.  F == 0 is a no-op.
+ *   - gf3_stbc_detect: joint max-log ML detection of every pair over the 4 x 4 pairs of constellation points.  d_Y_c128 and
+ *     d_H_c128 are HOST arrays of B device pointers as gf3_mimo_detect takes them; d_slope_f64 [F] is ONE device array, the
+ *     slope of every branch.  Per branch b the B x 2 channel entries h_t(l) at both slots are the reference's channel model
+ *     as gf3_mimo_detect states it, and per (f, j, c)
+ *       G00 = sum_b |h0(a)|^2 + |h1(b')|^2        G11 = sum_b |h1(a)|^2 + |h0(b')|^2
+ *       G01 = sum_b conj(h0(a)) h1(a) - h1(b') conj(h0(b'))
+ *       m0 = sum_b conj(h0(a)) y_a + h1(b') conj(y_b')        m1 = sum_b conj(h1(a)) y_a - h0(b') conj(y_b')     (b ascending)
+ *     go into gf3_mimo_detect's metric and LLR rule; the LLRs of x0 go to symbol 2j, those of x1 to symbol 2j + 1.  G01 is
+ *     what the channel's change between the two slots leaves (0 on a static channel); with it the detector is the exact
+ *     max-log ML of the pair.  A branch whose y at either slot, whose four estimates at the carrier, or the slope is not
+ *     finite is left out of every sum; where every branch is, both symbols' LLRs are +0.
+ *     d_llr_f32 [F][D][C][mu] float32: flattened, the coded order of one stream.
+ *     GF3_EINVAL for a null context, a context whose table is not mu = 2 with 4 points, an odd P or P < 2, an odd D, B out
+ *     of range, a null pointer, F < 0, more than 65535 packets.  F == 0 is a no-op.
+ *   Both: one launch, no allocation, no host synchronisation, asynchronous on `stream`; every sum in a fixed order, no
+ *   atomics: two calls give identical bytes.  The text of a refusal names the function.
+ */
+int gf3_stbc_slope(gf3_ctx *ctx, int32_t B, const void *const *d_H_c128, int64_t F, double *d_slope_f64, void *stream);
+int gf3_stbc_detect(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const void *const *d_H_c128,
+                    const double *d_slope_f64, int64_t F, float *d_llr_f32, void *stream);
+
+/*
  * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
  * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
  * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
