@@ -282,6 +282,21 @@ class CamG:
         # clock_correction: a clock offset leaks one speaker's pilots into the other's estimate.  ValueError for an odd or
         # zero no_pilots and an advance that is not an integer in [0, cp_length].
         self.mimo_advance = 48
+        # receive_mimo and receive_stbc, every encoding: joint_weighting chooses what weighs the recordings and carriers
+        # against each other in the joint metric sum_b w_b |y_b - h_b0 x0 - h_b1 x1|^2.  "csi": w = 1, maximum likelihood
+        # when every microphone hears the same white noise.  "noise": w_b = 1 / the noise variance of recording b at the
+        # carrier, for a fan in one microphone's low band or a phone's hiss at the top.  The variance is
+        # measured on the pilots, not on decisions: the two covers take two of a block's no_pilots observations per
+        # carrier, the squared residual of the rest is the noise (Engine.mimo_pilot_noise; the mean of the two blocks,
+        # floored at 1e-6 of the packet's mean over all recordings, Engine.joint_noise_weights).  It costs the pilot symbols'
+        # transforms once more and equals "csi" to within the estimate's own scatter in white noise; with no_pilots = 4 that
+        # scatter is large (two degrees of freedom per block), so prefer more pilots with it.  Under "noise" the receive
+        # call leaves `last_branch_snr_db` [B, F, 2 speakers, C] = 10 log10(Es |Hs_bt|^2 / floored variance) and `last_snr_db`:
+        # receive_stbc [F, C] = 10 log10(Es sum_b w_b (|Hs_b0|^2 + |Hs_b1|^2)), receive_mimo [pairs, 2 streams, C] =
+        # 10 log10(Es (G_ss - |G01|^2 / G_tt)) from the weighted sums, the zero-forcing SNR of stream s, a lower bound on what
+        # the joint detector sees; both are None under "csi".  `llr_weighting` is not read by these two calls beyond their
+        # refusal of anything but "csi".  ValueError for another value, and for "noise" with no_pilots < 4.
+        self.joint_weighting = "csi"
         self.papr_reduction = False
         self.papr_target_db = 6.0
         self.papr_iterations = 16
@@ -919,7 +934,10 @@ class receiver(transmitter):
         `last_decode_report`; "None" / "XOR": bits = (LLR < 0), then un-whitened.  -> (bits, Hs, He of recording 0's first
         packet from speaker 0), as receive_diversity().  `no_packets` counts the packet PAIRS found.  Leaves
         `last_branch_starts` int64 [B, pairs] (before the advance), `last_mimo_separation` float64 [pairs, C], `last_clock_ppm`
-        [B] and `sync_report` as receive_diversity() does.  ValueError: an odd or zero no_pilots, B outside 2 .. 4,
+        [B] and `sync_report` as receive_diversity() does.  joint_weighting = "noise": Engine.mimo_pilot_noise per recording
+        and one Engine.joint_noise_weights give the detector its weights, and `last_snr_db` [pairs, 2, C] and
+        `last_branch_snr_db` [B, pairs, 2, C] are left (None under "csi").  ValueError: an odd or zero no_pilots, a
+        joint_weighting other than "csi" or "noise", "noise" with no_pilots < 4, B outside 2 .. 4,
         recordings with different packet counts, llr_weighting other than "csi", fused_llr, phase_tracking,
         decoder_feedback, interleave, bit_loading, a mimo_advance that is not an integer in [0, cp_length].
         NotImplementedError: impulse_blanking, channel_denoising, graph_output, the piece-wise host path of long
@@ -936,13 +954,22 @@ class receiver(transmitter):
         F = self.no_packets
         # 2. every packet start moved back; per recording: the clock correction, the slope and the ragged flag, the two
         # columns of the channel
-        slopes, Hs, ragged, stages, first, moved = self._covered_estimates(eng, plan, xs, starts)
+        slopes, Hs, ragged, stages, first, moved, noise = self._covered_estimates(eng, plan, xs, starts)
+        w, snr = self._joint_noise(eng, Hs, noise) if plan.joint_noise else (None, {})
         # 3. the data symbols' spectra and the joint detection, packets at a time
         llr = eng._new((F, 2, cfg.D, cfg.C, cfg.mu), torch.float32)
         for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
-            eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi])
+            eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi],
+                            weights=None if w is None else w[:, lo:hi])
         # 4. decode: the coded chain, or the hard decisions
         bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
+        if w is not None:
+            # the zero-forcing SNR of either stream from the weighted sums of the start-block estimates
+            h = snr.pop("h")                                    # [B, F, 2, C]
+            g = [(w * h[:, :, t].abs() ** 2).sum(dim=0) for t in range(2)]
+            g01 = (w * h[:, :, 0].conj() * h[:, :, 1]).sum(dim=0).abs() ** 2
+            snr["last_snr_db"] = 10.0 * torch.log10(snr.pop("es") * torch.stack([g[0] - g01 / g[1], g[1] - g01 / g[0]], dim=1))
+            rows.update(snr)
         # 5. how far apart the speakers stand, from the start-block estimates: 1 - |G01|^2 / (G00 G11) per carrier
         col = torch.as_tensor(np.asarray(self.data_carriers) - 1, device=eng.device)
         h = torch.stack([H[:, 0] for H in Hs])[..., col]        # [B, F, 2, C]
@@ -951,16 +978,18 @@ class receiver(transmitter):
         rows["last_mimo_separation"] = 1.0 - g01.abs() ** 2 / (g00 * g11)
         # 6. everything else the host needs, in ONE small copy behind the kernels
         return self._publish_covered(plan, rows, first, starts, stages, sync_rho, ragged, bits_t, 2 * F * self.packet_length,
-                             ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets"))
+                             ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets",
+                              "last_snr_db", "last_branch_snr_db"))
 
     # ---- the steps receive_mimo and receive_stbc share ------------------------------------------------------------------
     def _covered_estimates(self, eng, plan, xs, starts):
         """Step 2 of both: every packet start moved back by the plan's advance; per recording the clock correction (xs[i] is
         replaced by the corrected samples), the demodulator for the slope, the ragged flag and the returned Hs / He, and
         Engine.mimo_pilots for the two columns of the channel -> (slopes, Hs, ragged flags, clock stages, recording 0's
-        demodulator outputs, the moved starts)."""
+        demodulator outputs, the moved starts, under the plan's joint_noise every recording's Engine.mimo_pilot_noise
+        [F, 2, K] -- else an empty list)."""
         slopes, Hs, ragged, stages, first = [], [], [], [], None
-        moved = []
+        moved, noise = [], []
         for i, (x, st) in enumerate(zip(xs, starts)):
             st = st - plan.advance
             stage = {}
@@ -974,9 +1003,25 @@ class receiver(transmitter):
             slopes.append(o["slope"])
             Hs.append(H)
             ragged += [o["status"], status]
+            if plan.joint_noise:
+                var, noise_status = eng.mimo_pilot_noise(x, st, H)
+                noise.append(var)
+                ragged.append(noise_status)
             stages.append(stage)
             moved.append(st)
-        return slopes, Hs, ragged, stages, first, moved
+        return slopes, Hs, ragged, stages, first, moved, noise
+
+    def _joint_noise(self, eng, Hs, noise):
+        """joint_weighting = "noise": the recordings' pilot-measured variances -> (the detectors' weights [B, F, C], rows for the
+        host: `last_branch_snr_db` [B, F, 2, C] = 10 log10(Es |Hs_bt|^2 / max(v_b, 1e-6 vbar)), and for the caller's own SNR
+        "h" = the start-block estimates on the data carriers [B, F, 2, C] and "es" = the table's mean power)."""
+        w = eng.joint_noise_weights(noise)
+        col = torch.as_tensor(np.asarray(self.data_carriers) - 1, device=eng.device)
+        v = torch.stack([0.5 * (n[:, 0] + n[:, 1]) for n in noise])[..., col]           # [B, F, C]
+        floored = torch.maximum(v, 1e-6 * v.mean(dim=(0, 2))[None, :, None])
+        es = float(np.mean(np.abs(self._tables()[0]) ** 2))
+        h = torch.stack([H[:, 0] for H in Hs])[..., col]                                # [B, F, 2, C]
+        return w, {"last_branch_snr_db": 10.0 * torch.log10(es * h.abs() ** 2 / floored[:, :, None, :]), "h": h, "es": es}
 
     def _data_spectra(self, eng, xs, moved, F):
         """Step 3 of both: (lo, hi, the B recordings' data-symbol spectra of packets lo .. hi - 1), packets at a time so that
@@ -1036,7 +1081,9 @@ class receiver(transmitter):
         every Alamouti pair (Engine.stbc_detect).  "QCLDPC-*": the LLRs go through decode's chain and `last_decode_report`;
         "None" / "XOR": bits = (LLR < 0), then un-whitened.  -> (bits, Hs, He of recording 0's first packet from speaker 0).
         `no_packets` counts the packets found.  Leaves `last_branch_starts` int64 [B, F] (before the advance),
-        `last_stbc_slope` float64 [F], `last_clock_ppm` [B] and `sync_report` as receive_mimo() does.  ValueError: what
+        `last_stbc_slope` float64 [F], `last_clock_ppm` [B] and `sync_report` as receive_mimo() does; under joint_weighting =
+        "noise" the pilot-measured weights go into the detector and `last_snr_db` [F, C] and `last_branch_snr_db`
+        [B, F, 2, C] are left, as receive_mimo() does.  ValueError: what
         receive_mimo refuses, an odd packet_length, B outside 1 .. 4.  NotImplementedError: as receive_mimo."""
         print("-" * 42 + "\nReceive \n" + "-" * 42)
         print("OFDM Paramters:")
@@ -1047,15 +1094,22 @@ class receiver(transmitter):
         cfg = eng.cfg
         xs, starts, sync_rho = self._synchronise(eng, plan, rs, who="receive_stbc")
         F = self.no_packets
-        _, Hs, ragged, stages, first, moved = self._covered_estimates(eng, plan, xs, starts)
+        _, Hs, ragged, stages, first, moved, noise = self._covered_estimates(eng, plan, xs, starts)
+        w, snr = self._joint_noise(eng, Hs, noise) if plan.joint_noise else (None, {})
         slope = eng.stbc_slope(Hs)
         llr = eng._new((F, cfg.D, cfg.C, cfg.mu), torch.float32)
         for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
-            eng.stbc_detect(Ys, [H[lo:hi] for H in Hs], slope[lo:hi], out=llr[lo:hi])
+            eng.stbc_detect(Ys, [H[lo:hi] for H in Hs], slope[lo:hi], out=llr[lo:hi], weights=None if w is None else w[:, lo:hi])
         bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
         rows["last_stbc_slope"] = slope
+        if w is not None:
+            # the SNR after combining both speakers' paths of every recording under its weight
+            gain = (w * (snr.pop("h").abs() ** 2).sum(dim=2)).sum(dim=0)
+            snr["last_snr_db"] = 10.0 * torch.log10(snr.pop("es") * gain)
+            rows.update(snr)
         return self._publish_covered(plan, rows, first, starts, stages, sync_rho, ragged, bits_t, F * self.packet_length,
-                             ("last_branch_starts", "last_stbc_slope", "last_clock_ppm", "last_clock_ppm_packets"))
+                             ("last_branch_starts", "last_stbc_slope", "last_clock_ppm", "last_clock_ppm_packets",
+                              "last_snr_db", "last_branch_snr_db"))
 
     def _receive(self, signals, graph_output, diversity, located=None):
         """The pipeline behind receive() (one recording) and receive_diversity() (B of them); they differ in the decode stage.

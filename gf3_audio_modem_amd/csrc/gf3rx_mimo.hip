@@ -12,7 +12,9 @@
 //   thread = carrier (combine_kernel's shape).  Per carrier the 2 B magnitudes at both pilot blocks and the 2 B phasors
 //   stay in registers; the phasors advance by one complex multiply per symbol.  Y is read straight from the spectra at
 //   bin data_bins[c]: B x 16 bytes per cell, 16 bytes written.  Every sum runs in a fixed order, no atomics: two runs
-//   give identical bytes.
+//   give identical bytes.  NW (gf3_mimo_detect_nw): one weight per branch and carrier, read into a register ahead of the
+//   symbol loop, multiplies that branch's term of every sum; a weight that is 0 or not finite takes the branch out at that
+//   carrier.  The NW = false instantiations are the arithmetic they were.
 #include "gf3rx_demap.h"
 
 namespace {
@@ -98,9 +100,10 @@ struct MimoDetectArgs {
     const int* bins;                        // [C] 1-based FFT bin of each data carrier
     int D, C, K, NB, P, Dc, ntile;
     const double* cre; const double* cim; const int* clab;      // the 4 points and their labels
+    const double* wgt;                      // NW: [B][F][C] the branches' weights (gf3_joint_noise_weights)
 };
 
-template <int B>
+template <int B, bool NW>
 __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs a) {
     const int t = threadIdx.x;
     const int tile = blockIdx.x % a.ntile, chunk = blockIdx.x / a.ntile;
@@ -116,10 +119,16 @@ __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs 
     double ms[B][2], me[B][2];
     cplx w[B][2], step[B];
     bool okh[B];
+    double wt[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
         const double sl = a.slope[b][f];
         okh[b] = is_fin(sl);
+        wt[b] = 1.0;
+        if constexpr (NW) {
+            wt[b] = a.wgt[((int64_t)b * gridDim.y + f) * a.C + c];
+            okh[b] = okh[b] && is_fin(wt[b]) && wt[b] != 0.0;
+        }
         const cplx rot = cis_fast(sl * n * f0);
         step[b] = cis_fast(sl * n / (double)(D + P));
 #pragma unroll
@@ -153,10 +162,15 @@ __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs 
             any = any || ok;
             const cplx h0 = cscale(w[b][0], ms[b][0] + (me[b][0] - ms[b][0]) * fl);
             const cplx h1 = cscale(w[b][1], ms[b][1] + (me[b][1] - ms[b][1]) * fl);
-            const cplx g = cmul_conj(h1, h0);               // conj(h0) h1
-            const cplx a0 = cmul_conj(y[b], h0), a1 = cmul_conj(y[b], h1);
-            G00 += ok ? h0.x * h0.x + h0.y * h0.y : 0.0;
-            G11 += ok ? h1.x * h1.x + h1.y * h1.y : 0.0;
+            cplx g = cmul_conj(h1, h0);                     // conj(h0) h1
+            cplx a0 = cmul_conj(y[b], h0), a1 = cmul_conj(y[b], h1);
+            double p0 = h0.x * h0.x + h0.y * h0.y, p1 = h1.x * h1.x + h1.y * h1.y;
+            if constexpr (NW) {
+                p0 *= wt[b]; p1 *= wt[b];
+                g = cscale(g, wt[b]); a0 = cscale(a0, wt[b]); a1 = cscale(a1, wt[b]);
+            }
+            G00 += ok ? p0 : 0.0;
+            G11 += ok ? p1 : 0.0;
             G01.x += ok ? g.x : 0.0;  G01.y += ok ? g.y : 0.0;
             m0.x += ok ? a0.x : 0.0;  m0.y += ok ? a0.y : 0.0;
             m1.x += ok ? a1.x : 0.0;  m1.y += ok ? a1.y : 0.0;
@@ -223,20 +237,22 @@ extern "C" int gf3_mimo_pilots(gf3_ctx* c, const void* d_in, int64_t n_in, const
     return GF3_OK;
 }
 
-extern "C" int gf3_mimo_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* const* d_slope,
-                               int64_t F, float* d_llr, void* stream) {
+// both entries of the detector: `who` names the caller in a refusal, d_w is null for the unweighted one
+template <bool NW>
+static int mimo_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* const* d_Y, const void* const* d_H,
+                            const double* const* d_slope, const double* d_w, int64_t F, float* d_llr, void* stream) {
     DeviceGuard dg(c);
-    if (!c) return fail(c, GF3_EINVAL, "gf3_mimo_detect: null context");
+    if (!c) return fail(c, GF3_EINVAL, "%s: null context", who);
     if (c->cfg.mu != 2 || c->cfg.M != 4)
-        return fail(c, GF3_EINVAL, "gf3_mimo_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)",
+        return fail(c, GF3_EINVAL, "%s: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)", who,
                     c->cfg.M, c->cfg.mu);
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0;
+    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w);
     for (int b = 0; ok && b < B; ++b) ok = d_Y[b] && d_H[b] && d_slope[b];
     if (!ok)
-        return fail(c, GF3_EINVAL, "gf3_mimo_detect: bad argument (1 <= B <= %d branches, each with spectra, estimates and slopes; "
-                                   "an output; F >= 0)", GF3_MAX_BRANCHES);
-    if (const int rc = too_many_packets(c, F, "gf3_mimo_detect")) return rc;
+        return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra, estimates and slopes; %s"
+                                   "an output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "");
+    if (const int rc = too_many_packets(c, F, who)) return rc;
     MimoDetectArgs a{};
     for (int b = 0; b < B; ++b) { a.Y[b] = (const cplx*)d_Y[b]; a.H[b] = (const cplx*)d_H[b]; a.slope[b] = d_slope[b]; }
     a.llr = d_llr;
@@ -245,14 +261,25 @@ extern "C" int gf3_mimo_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, co
     a.ntile = (a.C + MD_THREADS - 1) / MD_THREADS;
     a.Dc = symbols_per_group(c, F * a.ntile, a.D);
     a.cre = c->d_cre; a.cim = c->d_cim; a.clab = c->d_clab;
+    a.wgt = d_w;
     const dim3 grid((unsigned)(a.ntile * ((a.D + a.Dc - 1) / a.Dc)), (unsigned)F);
     const hipStream_t st = (hipStream_t)stream;
     switch (B) {
-        case 1: hipLaunchKernelGGL((mimo_detect_kernel<1>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((mimo_detect_kernel<2>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((mimo_detect_kernel<3>), grid, dim3(MD_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((mimo_detect_kernel<4>), grid, dim3(MD_THREADS), 0, st, a); break;
+        case 1: hipLaunchKernelGGL((mimo_detect_kernel<1, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((mimo_detect_kernel<2, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((mimo_detect_kernel<3, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
+        default: hipLaunchKernelGGL((mimo_detect_kernel<4, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
     }
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
+}
+
+extern "C" int gf3_mimo_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* const* d_slope,
+                               int64_t F, float* d_llr, void* stream) {
+    return mimo_detect_call<false>(c, "gf3_mimo_detect", B, d_Y, d_H, d_slope, nullptr, F, d_llr, stream);
+}
+
+extern "C" int gf3_mimo_detect_nw(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* const* d_slope,
+                                  const double* d_w, int64_t F, float* d_llr, void* stream) {
+    return mimo_detect_call<true>(c, "gf3_mimo_detect_nw", B, d_Y, d_H, d_slope, d_w, F, d_llr, stream);
 }

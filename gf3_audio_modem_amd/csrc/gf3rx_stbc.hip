@@ -15,7 +15,8 @@
 //   symbol PAIRS of one packet; thread = carrier.  The 2 B magnitudes at both pilot blocks and the 2 B phasors stay in
 //   registers; ONE slope serves every branch, so one step advances them all, one complex multiply per entry and symbol.
 //   Per pair a thread reads B x 32 bytes of Y and writes 16.  Every sum runs in a fixed order, no atomics: two runs give
-//   identical bytes.
+//   identical bytes.  NW (gf3_stbc_detect_nw): mimo_detect_kernel's weights -- one per branch and carrier, in a register
+//   ahead of the pair loop, on that branch's term of every sum at both slots; 0 or not finite takes the branch out.
 #include "gf3rx_demap.h"
 
 namespace {
@@ -77,9 +78,10 @@ struct StbcDetectArgs {
     const int* bins;                        // [C] 1-based FFT bin of each data carrier
     int D, C, K, NB, P, Jc, ntile;
     const double* cre; const double* cim; const int* clab;      // the 4 points and their labels
+    const double* wgt;                      // NW: [B][F][C] the branches' weights (gf3_joint_noise_weights)
 };
 
-template <int B>
+template <int B, bool NW>
 __global__ __launch_bounds__(SD_THREADS) void stbc_detect_kernel(StbcDetectArgs a) {
     const int t = threadIdx.x;
     const int tile = blockIdx.x % a.ntile, chunk = blockIdx.x / a.ntile;
@@ -98,9 +100,15 @@ __global__ __launch_bounds__(SD_THREADS) void stbc_detect_kernel(StbcDetectArgs 
     double ms[B][2], me[B][2];
     cplx w[B][2];
     bool okh[B];
+    double wt[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
         okh[b] = oks;
+        wt[b] = 1.0;
+        if constexpr (NW) {
+            wt[b] = a.wgt[((int64_t)b * gridDim.y + f) * a.C + c];
+            okh[b] = okh[b] && is_fin(wt[b]) && wt[b] != 0.0;
+        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const cplx hs = a.H[b][((f * 2 + 0) * 2 + s) * a.K + (bin - 1)];
@@ -145,11 +153,19 @@ __global__ __launch_bounds__(SD_THREADS) void stbc_detect_kernel(StbcDetectArgs 
             const cplx ga = cmul_conj(h1a, h0a), gb = cmul_conj(h1b, h0b);    // conj(h0) h1 at either slot
             const cplx a0 = cmul_conj(ya[b], h0a), a1 = cmul_conj(ya[b], h1a);
             const cplx b0 = cmul_conj(h1b, yb[b]), b1 = cmul_conj(h0b, yb[b]); // h1(b') conj(y_b'), h0(b') conj(y_b')
-            G00 += ok ? (h0a.x * h0a.x + h0a.y * h0a.y) + (h1b.x * h1b.x + h1b.y * h1b.y) : 0.0;
-            G11 += ok ? (h1a.x * h1a.x + h1a.y * h1a.y) + (h0b.x * h0b.x + h0b.y * h0b.y) : 0.0;
-            G01.x += ok ? ga.x - gb.x : 0.0;  G01.y += ok ? ga.y - gb.y : 0.0;
-            m0.x += ok ? a0.x + b0.x : 0.0;   m0.y += ok ? a0.y + b0.y : 0.0;
-            m1.x += ok ? a1.x - b1.x : 0.0;   m1.y += ok ? a1.y - b1.y : 0.0;
+            double p0 = (h0a.x * h0a.x + h0a.y * h0a.y) + (h1b.x * h1b.x + h1b.y * h1b.y);
+            double p1 = (h1a.x * h1a.x + h1a.y * h1a.y) + (h0b.x * h0b.x + h0b.y * h0b.y);
+            cplx g = cmk(ga.x - gb.x, ga.y - gb.y);
+            cplx s0 = cmk(a0.x + b0.x, a0.y + b0.y), s1 = cmk(a1.x - b1.x, a1.y - b1.y);
+            if constexpr (NW) {                             // both slots of the pair carry the branch's one weight
+                p0 *= wt[b]; p1 *= wt[b];
+                g = cscale(g, wt[b]); s0 = cscale(s0, wt[b]); s1 = cscale(s1, wt[b]);
+            }
+            G00 += ok ? p0 : 0.0;
+            G11 += ok ? p1 : 0.0;
+            G01.x += ok ? g.x : 0.0;    G01.y += ok ? g.y : 0.0;
+            m0.x += ok ? s0.x : 0.0;    m0.y += ok ? s0.y : 0.0;
+            m1.x += ok ? s1.x : 0.0;    m1.y += ok ? s1.y : 0.0;
         }
         // the 16 metrics d[i][k] of (x0 = point i, x1 = point k), reduced once along each symbol of the pair, as
         // mimo_detect_kernel reduces them along each stream: best[0][i] is the minimum over x1 with x0 = point i,
@@ -232,21 +248,23 @@ extern "C" int gf3_stbc_slope(gf3_ctx* c, int32_t B, const void* const* d_H, int
     return GF3_OK;
 }
 
-extern "C" int gf3_stbc_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* d_slope,
-                               int64_t F, float* d_llr, void* stream) {
+// both entries of the detector: `who` names the caller in a refusal, d_w is null for the unweighted one
+template <bool NW>
+static int stbc_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* const* d_Y, const void* const* d_H,
+                            const double* d_slope, const double* d_w, int64_t F, float* d_llr, void* stream) {
     DeviceGuard dg(c);
-    if (!c) return fail(c, GF3_EINVAL, "gf3_stbc_detect: null context");
+    if (!c) return fail(c, GF3_EINVAL, "%s: null context", who);
     if (c->cfg.mu != 2 || c->cfg.M != 4)
-        return fail(c, GF3_EINVAL, "gf3_stbc_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)",
+        return fail(c, GF3_EINVAL, "%s: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)", who,
                     c->cfg.M, c->cfg.mu);
-    if (const int rc = stbc_geometry(c, "gf3_stbc_detect")) return rc;
+    if (const int rc = stbc_geometry(c, who)) return rc;
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0;
+    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w);
     for (int b = 0; ok && b < B; ++b) ok = d_Y[b] && d_H[b];
     if (!ok)
-        return fail(c, GF3_EINVAL, "gf3_stbc_detect: bad argument (1 <= B <= %d branches, each with spectra and estimates; one slope "
-                                   "array; an output; F >= 0)", GF3_MAX_BRANCHES);
-    if (const int rc = too_many_packets(c, F, "gf3_stbc_detect")) return rc;
+        return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra and estimates; one slope "
+                                   "array; %san output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "");
+    if (const int rc = too_many_packets(c, F, who)) return rc;
     StbcDetectArgs a{};
     for (int b = 0; b < B; ++b) { a.Y[b] = (const cplx*)d_Y[b]; a.H[b] = (const cplx*)d_H[b]; }
     a.slope = d_slope;
@@ -256,15 +274,26 @@ extern "C" int gf3_stbc_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, co
     a.ntile = (a.C + SD_THREADS - 1) / SD_THREADS;
     a.Jc = symbols_per_group(c, F * a.ntile, a.D / 2);
     a.cre = c->d_cre; a.cim = c->d_cim; a.clab = c->d_clab;
+    a.wgt = d_w;
     const int pairs = a.D / 2;
     const dim3 grid((unsigned)(a.ntile * ((pairs + a.Jc - 1) / a.Jc)), (unsigned)F);
     const hipStream_t st = (hipStream_t)stream;
     switch (B) {
-        case 1: hipLaunchKernelGGL((stbc_detect_kernel<1>), grid, dim3(SD_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((stbc_detect_kernel<2>), grid, dim3(SD_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((stbc_detect_kernel<3>), grid, dim3(SD_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((stbc_detect_kernel<4>), grid, dim3(SD_THREADS), 0, st, a); break;
+        case 1: hipLaunchKernelGGL((stbc_detect_kernel<1, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((stbc_detect_kernel<2, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((stbc_detect_kernel<3, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
+        default: hipLaunchKernelGGL((stbc_detect_kernel<4, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
     }
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
+}
+
+extern "C" int gf3_stbc_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* d_slope,
+                               int64_t F, float* d_llr, void* stream) {
+    return stbc_detect_call<false>(c, "gf3_stbc_detect", B, d_Y, d_H, d_slope, nullptr, F, d_llr, stream);
+}
+
+extern "C" int gf3_stbc_detect_nw(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* d_slope,
+                                  const double* d_w, int64_t F, float* d_llr, void* stream) {
+    return stbc_detect_call<true>(c, "gf3_stbc_detect_nw", B, d_Y, d_H, d_slope, d_w, F, d_llr, stream);
 }

@@ -863,14 +863,64 @@ class Engine:
         self._check(self.lib.gf3_mimo_pilots(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(H), _ptr(status), self._stream()))
         return H, status
 
-    def mimo_detect(self, Ys, Hs, slopes, out=None):
+    def mimo_pilot_noise(self, x, frame_offsets, H):
+        """The per-carrier noise variance of one recording of two loudspeakers, measured on the covered pilots
+        (gf3_mimo_pilot_noise): with H = mimo_pilots(x, frame_offsets)[0],
+        v[f, side, k] = 1 / (P - 2) sum_p |Y_p[k] / X[k] - H[f, side, 0, k] - (-1)^p H[f, side, 1, k]|^2 over the side's P
+        pilot symbols -- what the two covers leave of them, so nothing has to be decided.  In the unit of |H|^2: white noise
+        of deviation sigma per sample gives N sigma^2.  -> (var float64 [F, 2 sides, K], status int32 [F]); status and the NaN
+        rows of a packet that leaves the samples are mimo_pilots' rule.  Needs an even P >= 4 (ValueError: P = 2 leaves no
+        degree of freedom).  Fixed summation order: two calls give identical bytes."""
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F = off.numel()
+        H = self._dev(H)
+        if H.numel() != F * 2 * _lib.GF3_MIMO_STREAMS * self.cfg.K:
+            raise ValueError("mimo_pilot_noise: H must be mimo_pilots' [F, 2, 2, K] for the F offsets")
+        var = self._new((F, 2, self.cfg.K), torch.float64)
+        status = self._new((F,), torch.int32)
+        self._check(self.lib.gf3_mimo_pilot_noise(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(H), _ptr(var), _ptr(status),
+                                                  self._stream()))
+        return var, status
+
+    def joint_noise_weights(self, vars):
+        """The weights of the joint detectors under coloured noise (gf3_joint_noise_weights) from B = len(vars) <= 4
+        recordings' mimo_pilot_noise output [F, 2, K]: v_b[f, c] = the mean of the two sides at data carrier c's bin, then
+        combine_branches' rule under `var` -- vbar[f] the mean over all branches and data carriers, w = 1 / max(v, 1e-6
+        vbar); 1 for the whole packet where vbar is 0 or not finite; 0 where v is not finite.  -> float64 [B, F, C], what
+        mimo_detect and stbc_detect take as `weights`.  Fixed summation order: two calls give identical bytes."""
+        vars = list(vars)
+        B = len(vars)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"joint_noise_weights: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        vars = [self._dev(v, torch.float64) for v in vars]
+        per = 2 * self.cfg.K
+        if vars[0].numel() % per or any(v.numel() != vars[0].numel() for v in vars):
+            raise ValueError("joint_noise_weights: every branch needs var [F, 2, K] of the same F")
+        F = vars[0].numel() // per
+        w = self._new((B, F, self.cfg.C), torch.float64)
+        table = (C.c_void_p * B)(*[v.data_ptr() for v in vars])
+        self._check(self.lib.gf3_joint_noise_weights(self._h, B, table, F, _ptr(w), self._stream()))
+        return w
+
+    def _joint_weights(self, weights, B, F, who):
+        """`weights` of the joint detectors -> one contiguous float64 tensor [B, F, C] on the device"""
+        w = self._dev(weights, torch.float64)
+        if w.numel() != B * F * self.cfg.C:
+            raise ValueError(f"{who}: weights must be [B, F, C] for {B} branches of Y [F*D, N/2+1]")
+        return w
+
+    def mimo_detect(self, Ys, Hs, slopes, out=None, weights=None):
         """Joint max-log ML detection of the two streams of 2 x 2 spatial multiplexing (gf3_mimo_detect) from B = len(Ys)
         <= 4 recordings: Ys[b] the data symbols' spectra [F*D, N/2+1] as rfft_batch writes them, Hs[b] mimo_pilots' H
         [F, 2, 2, K], slopes[b] demod_frames' slope [F] of recording b.  Per cell the reference's channel model gives the
         B x 2 channel entries; the metric sum_b |y_b - h_b0 x0 - h_b1 x1|^2 is minimised over the 4 x 4 pairs of points.
         A branch whose spectrum value or estimates are not finite at a cell drops out there; where all do, the LLRs are +0.
         -> float32 [F, 2 streams, D, C, mu]: flattened, the coded order of packets 2f, 2f + 1; LLR > 0 <=> bit 0.  out:
-        optional contiguous float32 tensor of that many elements.  Needs a table of 4 points with mu = 2 (ValueError)."""
+        optional contiguous float32 tensor of that many elements.  weights: None, or joint_noise_weights' [B, F, C]
+        (gf3_mimo_detect_nw): branch b's term of the metric at carrier c is multiplied by w[b, f, c] -- maximum likelihood
+        for noise of variance 1 / w --, and a branch whose weight is 0 drops out there as a non-finite estimate does.
+        Needs a table of 4 points with mu = 2 (ValueError)."""
         cfg = self.cfg
         Ys, Hs, slopes = list(Ys), list(Hs), list(slopes)
         B = len(Ys)
@@ -899,7 +949,12 @@ class Engine:
 
         def table(xs):
             return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
-        self._check(self.lib.gf3_mimo_detect(self._h, B, table(Ys), table(Hs), table(slopes), F, _ptr(llr), self._stream()))
+        if weights is None:
+            self._check(self.lib.gf3_mimo_detect(self._h, B, table(Ys), table(Hs), table(slopes), F, _ptr(llr), self._stream()))
+        else:
+            w = self._joint_weights(weights, B, F, "mimo_detect")
+            self._check(self.lib.gf3_mimo_detect_nw(self._h, B, table(Ys), table(Hs), table(slopes), _ptr(w), F, _ptr(llr),
+                                                    self._stream()))
         return llr
 
     def _stbc_geometry(self, who):
@@ -940,7 +995,7 @@ class Engine:
         self._check(self.lib.gf3_stbc_slope(self._h, B, table, F, _ptr(slope), self._stream()))
         return slope
 
-    def stbc_detect(self, Ys, Hs, slope, out=None):
+    def stbc_detect(self, Ys, Hs, slope, out=None, weights=None):
         """Joint max-log ML detection of the Alamouti pairs of transmit diversity (gf3_stbc_detect) from B = len(Ys) <= 4
         recordings: Ys[b] the data symbols' spectra [F*D, N/2+1] as rfft_batch writes them, Hs[b] mimo_pilots' H
         [F, 2, 2, K], slope ONE array [F] for every branch (stbc_slope).  Symbols 2j and 2j + 1 of a packet carry x0, x1 as
@@ -948,7 +1003,9 @@ class Engine:
         into mimo_detect's metric over the 4 x 4 pairs of points.  A branch whose spectrum value at either slot or whose
         estimates are not finite drops out of the pair; where all do (or the slope is not finite), the LLRs are +0.
         -> float32 [F, D, C, mu]: flattened, the coded order of one stream; LLR > 0 <=> bit 0.  out: optional contiguous
-        float32 tensor of that many elements.  Needs a table of 4 points with mu = 2, an even P >= 2, an even D (ValueError)."""
+        float32 tensor of that many elements.  weights: None, or joint_noise_weights' [B, F, C] (gf3_stbc_detect_nw), as
+        mimo_detect takes them; both slots of a pair carry the branch's one weight.  Needs a table of 4 points with mu = 2,
+        an even P >= 2, an even D (ValueError)."""
         cfg = self.cfg
         Ys = list(Ys)
         B = len(Ys)
@@ -976,7 +1033,12 @@ class Engine:
 
         def table(xs):
             return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
-        self._check(self.lib.gf3_stbc_detect(self._h, B, table(Ys), table(Hs), _ptr(slope), F, _ptr(llr), self._stream()))
+        if weights is None:
+            self._check(self.lib.gf3_stbc_detect(self._h, B, table(Ys), table(Hs), _ptr(slope), F, _ptr(llr), self._stream()))
+        else:
+            w = self._joint_weights(weights, B, F, "stbc_detect")
+            self._check(self.lib.gf3_stbc_detect_nw(self._h, B, table(Ys), table(Hs), _ptr(slope), _ptr(w), F, _ptr(llr),
+                                                    self._stream()))
         return llr
 
     def noise_estimate2(self, eq):

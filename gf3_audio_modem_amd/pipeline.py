@@ -121,6 +121,7 @@ class ReceivePlan(NamedTuple):
     detect: object = None                   # the threshold of the self-normalised detection (sync_rule "local"), or None
     rates: object = None                    # check_input_rates' answer: per recording None or (input rate, half_taps), or None
     advance: int = 0                        # receive_mimo: samples every packet start is moved back by (`mimo_advance`)
+    joint_noise: bool = False               # receive_mimo, receive_stbc: pilot-measured weights (`joint_weighting` = "noise")
 
 
 def check_mimo_pilots(no_pilots):
@@ -137,13 +138,26 @@ def check_advance(advance, cp_length):
     return int(advance)
 
 
+def check_joint_weighting(joint_weighting, no_pilots, who):
+    """`joint_weighting` -> True under "noise" (Engine.mimo_pilot_noise, joint_noise_weights), False under "csi".  ValueError
+    for another value, and for "noise" with fewer than 4 pilot symbols: the two covers take two of them per carrier and the
+    noise is measured on the rest."""
+    if not isinstance(joint_weighting, str) or joint_weighting not in ("csi", "noise"):
+        raise ValueError(f"{who}: joint_weighting must be 'csi' or 'noise', not {joint_weighting!r}")
+    if joint_weighting == "noise" and no_pilots < 4:
+        raise ValueError(f"{who}: joint_weighting = 'noise' measures the noise on the pilot symbols the two covers leave over: "
+                         f"no_pilots must be >= 4, not {no_pilots!r}")
+    return joint_weighting == "noise"
+
+
 def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams", verb="separates"):
     """The plan of receive_mimo() on recordings of `lengths` samples, in plan_receive's manner and order: the pilot cover's
-    and the coded chain's own refusals (CodedChain.check_mimo), the values of the advance, the clock correction, the sync
-    rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work.  (plan_stbc names
-    itself in `who`.)"""
+    and the coded chain's own refusals (CodedChain.check_mimo), the values of the joint weighting, the advance, the clock
+    correction, the sync rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work.
+    (plan_stbc names itself in `who`.)"""
     check_mimo_pilots(rx.no_pilots)
     rate = chain.check_mimo(who, what)
+    joint_noise = check_joint_weighting(rx.joint_weighting, rx.no_pilots, who)
     advance = check_advance(rx.mimo_advance, rx.cp_length)
     clock = check_clock(rx.clock_correction, rx.clock_taps)
     detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
@@ -159,7 +173,8 @@ def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams",
     for on, why in no_path:
         if on:
             raise NotImplementedError(why.format(host=_HOST))
-    return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance)
+    return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance,
+                       joint_noise)
 
 
 def check_stbc_length(packet_length):

@@ -770,6 +770,46 @@ int gf3_stbc_detect(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const 
                     const double *d_slope_f64, int64_t F, float *d_llr_f32, void *stream);
 
 /*
+ * The two-speaker paths under coloured noise (not in the reference).  The joint metric sum_b |y_b - h_b0 x0 - h_b1 x1|^2
+ * weights every recording and carrier alike, which is maximum likelihood only in white noise of one level.  With a weight
+ * w_b[f, c] per recording, packet and data carrier the statistics of gf3_mimo_detect and gf3_stbc_detect become
+ *     G00 = sum_b w_b |h_b0|^2,  G11, G01, m0, m1 likewise (for the space-time code both slots of a pair under the one w_b),
+ * everything after the sums unchanged: the maximum-likelihood metric for noise of variance 1 / w_b.  The variance is
+ * measured on the covered pilots, where nothing has to be decided: two of a block's P observations per carrier give the
+ * two columns (gf3_mimo_pilots), the other P - 2 the noise.
+ *   - gf3_mimo_pilot_noise: d_var_out_f64 [F][2 sides][K] float64 from the samples and offsets as gf3_mimo_pilots takes them
+ *     and that call's output d_H_c128 [F][2][2][K]:
+ *       v[f, side, k] = 1 / (P - 2) sum_p | Y_p[k] / X[k] - H[f, side, 0, k] - (-1)^p H[f, side, 1, k] |^2
+ *     over the side's P pilot symbols without their prefix, p ascending, each transformed on its own; 1 / X as in
+ *     gf3_mimo_pilots.  The unit is that of |H|^2: white noise of deviation sigma per sample gives
+ *     N sigma^2 / |X|^2 under the library's unnormalised transform.  d_status_i32 [F] and the NaN rows of a packet whose
+ *     body leaves [0, n_in) are gf3_mimo_pilots' rule.  One workgroup per (packet, side).
+ *     GF3_EINVAL for a null context, a context whose P is odd or < 4 (P = 2 leaves no degree of freedom), a null pointer
+ *     with F > 0, F < 0, n_in < 0, more than 2^30 - 1 packets.  F == 0 is a no-op.
+ *   - gf3_joint_noise_weights: d_var_f64 is a HOST array of B device pointers (read during the call only), 1 <= B <=
+ *     GF3_MAX_BRANCHES, each gf3_mimo_pilot_noise's output [F][2][K] for one recording.  Per data carrier c
+ *       v_b[f, c] = 0.5 (var_b[f, 0, data_bins[c] - 1] + var_b[f, 1, data_bins[c] - 1])
+ *     and then gf3_combine_branches' rule under GF3_COMBINE_NOISE: vbar[f] the mean of v_b[f, c] over all branches and data
+ *     carriers (fixed order), w = 1 for the whole packet where vbar is 0 or not finite, else w = 1 / max(v, 1e-6 vbar);
+ *     w = 0 where v is not finite.  d_w_out_f64 [B][F][C] float64.  One workgroup per packet.
+ *     GF3_EINVAL for a null context, B out of range, a null pointer, F < 0, more than 2^30 - 1 packets.  F == 0 is a no-op.
+ *   - gf3_mimo_detect_nw, gf3_stbc_detect_nw: gf3_mimo_detect and gf3_stbc_detect with d_w_f64 [B][F][C], ONE device array,
+ *     gf3_joint_noise_weights' output.  A branch whose weight at a carrier is 0 or not finite is left out of every sum
+ *     there, as one with a non-finite estimate is; where every branch is, the LLRs are +0.  Arguments, outputs and refusals
+ *     are the unweighted calls', and a null d_w_f64 is refused.
+ *   All: one launch, no allocation, no host synchronisation, asynchronous on `stream`; every sum in a fixed order, no
+ *   atomics: two calls give identical bytes.  The text of a refusal names the function.
+ */
+int gf3_mimo_pilot_noise(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                         const void *d_H_c128, double *d_var_out_f64, int32_t *d_status_i32, void *stream);
+int gf3_joint_noise_weights(gf3_ctx *ctx, int32_t B, const double *const *d_var_f64, int64_t F, double *d_w_out_f64,
+                            void *stream);
+int gf3_mimo_detect_nw(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const void *const *d_H_c128,
+                       const double *const *d_slope_f64, const double *d_w_f64, int64_t F, float *d_llr_f32, void *stream);
+int gf3_stbc_detect_nw(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const void *const *d_H_c128,
+                       const double *d_slope_f64, const double *d_w_f64, int64_t F, float *d_llr_f32, void *stream);
+
+/*
  * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
  * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
  * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
