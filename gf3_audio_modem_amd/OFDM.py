@@ -297,6 +297,19 @@ class CamG:
         # the joint detector sees; both are None under "csi".  `llr_weighting` is not read by these two calls beyond their
         # refusal of anything but "csi".  ValueError for another value, and for "noise" with no_pilots < 4.
         self.joint_weighting = "csi"
+        # receive_mimo, "QCLDPC-*": mimo_cancellation = n > 0 lets receive_mimo decode up to n more times (successive
+        # interference cancellation, driven by the code).  The two packets of a pair share every cell, and their codewords
+        # are different codewords.  The codewords the first decode TRUSTS (converged and, under codeword_crc, with a matching
+        # CRC) are re-encoded, and the packet pairs that still hold a bit of an untrusted codeword are detected again with
+        # those bits known (Engine.mimo_detect_known): a pair of points that contradicts a known bit leaves the metric's
+        # minima, so where one stream is known the other sees its own column alone -- gain G11 instead of
+        # G11 (1 - |G01|^2 / (G00 G11)), which is what the carriers of low `last_mimo_separation` lack.  Only the untrusted
+        # codewords are decoded again; the loop ends when nothing is untrusted, when a pass trusts nothing new, or after n
+        # passes.  Use codeword_crc with it: a miscorrected codeword cancels the wrong signal.  `last_decode_report` then also
+        # holds "cancel_passes" and "cancel_recovered".  ValueError for a value that is not an integer >= 0, a value > 0 under
+        # another encoding, and a value > 0 on receive_stbc (its pair decouples: nothing to cancel); receive() and
+        # receive_diversity() do not read it.  0: everything as without it.
+        self.mimo_cancellation = 0
         self.papr_reduction = False
         self.papr_target_db = 6.0
         self.papr_iterations = 16
@@ -358,7 +371,8 @@ class CamG:
                           phase_tracking=bool(self.phase_tracking), decoder_feedback=self.decoder_feedback,
                           feedback_window=self.feedback_window, feedback_min_known=self.feedback_min_known,
                           loading=None if order is None else tuple(order.tolist()),
-                          denoise=(self.denoise_threshold, self.no_pilots) if self.channel_denoising else None)
+                          denoise=(self.denoise_threshold, self.no_pilots) if self.channel_denoising else None,
+                          mimo_cancellation=self.mimo_cancellation)
 
     def _qcldpc_rate(self):
         """Rate of a "QCLDPC-*" encoding, else None (ValueError: interleave, outer_code or codeword_crc on another encoding)."""
@@ -936,8 +950,12 @@ class receiver(transmitter):
         `last_branch_starts` int64 [B, pairs] (before the advance), `last_mimo_separation` float64 [pairs, C], `last_clock_ppm`
         [B] and `sync_report` as receive_diversity() does.  joint_weighting = "noise": Engine.mimo_pilot_noise per recording
         and one Engine.joint_noise_weights give the detector its weights, and `last_snr_db` [pairs, 2, C] and
-        `last_branch_snr_db` [B, pairs, 2, C] are left (None under "csi").  ValueError: an odd or zero no_pilots, a
-        joint_weighting other than "csi" or "noise", "noise" with no_pilots < 4, B outside 2 .. 4,
+        `last_branch_snr_db` [B, pairs, 2, C] are left (None under "csi").  mimo_cancellation = n > 0 ("QCLDPC-*"): up to n
+        more passes (CodedChain.decode_cancel), each of which detects the packet pairs that hold an untrusted codeword again
+        with the trusted codewords' bits known (Engine.mimo_detect_known, their data symbols transformed again) and decodes
+        the untrusted codewords alone; `last_decode_report` then holds "cancel_passes" and "cancel_recovered".
+        ValueError: a mimo_cancellation that is not an integer >= 0 or is > 0 without a "QCLDPC-*" encoding, an odd or zero
+        no_pilots, a joint_weighting other than "csi" or "noise", "noise" with no_pilots < 4, B outside 2 .. 4,
         recordings with different packet counts, llr_weighting other than "csi", fused_llr, phase_tracking,
         decoder_feedback, interleave, bit_loading, a mimo_advance that is not an integer in [0, cp_length].
         NotImplementedError: impulse_blanking, channel_denoising, graph_output, the piece-wise host path of long
@@ -961,8 +979,17 @@ class receiver(transmitter):
         for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
             eng.mimo_detect(Ys, [H[lo:hi] for H in Hs], [s[lo:hi] for s in slopes], out=llr[lo:hi],
                             weights=None if w is None else w[:, lo:hi])
-        # 4. decode: the coded chain, or the hard decisions
-        bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
+        # 4. decode: the coded chain, or the hard decisions; under mimo_cancellation the pairs that hold an untrusted
+        # codeword are detected again with the trusted codewords' bits known, from their spectra taken again
+        def detect_known(pairs, bits, known):
+            at = torch.from_numpy(pairs).to(eng.device)
+            out = eng._new((len(pairs), 2, cfg.D, cfg.C, cfg.mu), torch.float32)
+            for lo, hi, Ys in self._data_spectra(eng, xs, [st[at] for st in moved], len(pairs)):
+                sel = at[lo:hi]
+                eng.mimo_detect_known(Ys, [H[sel] for H in Hs], [s[sel] for s in slopes], bits[lo:hi].contiguous(),
+                                      known[lo:hi].contiguous(), out=out[lo:hi], weights=None if w is None else w[:, sel])
+            return out
+        bits_t, rows, cancel = self._decode_llrs(eng, plan, llr.reshape(-1), detect_known if plan.cancel else None)
         if w is not None:
             # the zero-forcing SNR of either stream from the weighted sums of the start-block estimates
             h = snr.pop("h")                                    # [B, F, 2, C]
@@ -979,7 +1006,7 @@ class receiver(transmitter):
         # 6. everything else the host needs, in ONE small copy behind the kernels
         return self._publish_covered(plan, rows, first, starts, stages, sync_rho, ragged, bits_t, 2 * F * self.packet_length,
                              ("last_branch_starts", "last_mimo_separation", "last_clock_ppm", "last_clock_ppm_packets",
-                              "last_snr_db", "last_branch_snr_db"))
+                              "last_snr_db", "last_branch_snr_db"), cancel)
 
     # ---- the steps receive_mimo and receive_stbc share ------------------------------------------------------------------
     def _covered_estimates(self, eng, plan, xs, starts):
@@ -1033,21 +1060,27 @@ class receiver(transmitter):
             hi = min(lo + step, F)
             yield lo, hi, [eng.rfft_batch(x, (st[lo:hi, None] + within).reshape(-1)) for x, st in zip(xs, moved)]
 
-    def _decode_llrs(self, eng, plan, llr):
-        """Step 4 of both: the coded chain, or the hard decisions with the un-whitening -> (bits on the device, report rows)"""
-        rows = {}
-        if plan.rate is not None:
+    def _decode_llrs(self, eng, plan, llr, detect_known=None):
+        """Step 4 of both: the coded chain, or the hard decisions with the un-whitening -> (bits on the device, report rows,
+        what the cancellation adds to the report or None).  detect_known: receive_mimo's under `mimo_cancellation`, what
+        CodedChain.decode_cancel asks for the LLRs of packet pairs given what is known."""
+        rows, cancel = {}, None
+        if detect_known is not None:
+            bits_t, iters, status, bad, cancel = plan.chain.decode_cancel(eng, plan.chain.code(plan.rate, eng.device), llr, detect_known)
+            rows.update(_report_rows(iters, status, bad))
+        elif plan.rate is not None:
             bits_t, iters, status, bad = plan.chain.decode(plan.chain.code(plan.rate, eng.device), llr)
             rows.update(_report_rows(iters, status, bad))
         else:
             bits_t = (llr < 0).to(torch.int64)
             if self.encoding == "XOR":
                 bits_t = bits_t ^ torch.from_numpy(self._xor_mask(bits_t.numel())).to(eng.device)
-        return bits_t, rows
+        return bits_t, rows, cancel
 
-    def _publish_covered(self, plan, rows, first, starts, stages, sync_rho, ragged, bits_t, symbols, names):
+    def _publish_covered(self, plan, rows, first, starts, stages, sync_rho, ragged, bits_t, symbols, names, cancel=None):
         """The last step of both: everything the host needs in ONE small copy behind the kernels, the ragged refusal, the
-        attributes `names` (the fetched value or None) -> (bits, Hs, He of recording 0's first packet from speaker 0)."""
+        attributes `names` (the fetched value or None) -> (bits, Hs, He of recording 0's first packet from speaker 0).
+        cancel: what `mimo_cancellation` adds to `last_decode_report`, or None."""
         rows.update(Hs0=first["Hs"][0], He0=first["He"][0], slope=first["slope"], last_branch_starts=torch.stack(starts))
         rows.update({name: torch.stack([stage[name] for stage in stages]) for name in stages[0]})
         if sync_rho is not None:
@@ -1065,6 +1098,8 @@ class receiver(transmitter):
             setattr(self, name, got.get(name))
         if plan.rate is not None:
             self.last_decode_report = decode_report(got["iters"], got["status"], plan.chain.outer(), got.get("crc_bad"))
+            if cancel is not None:                              # (under mimo_cancellation only)
+                self.last_decode_report.update(cancel)
         print("Number of received bits:            " + str(len(bits)))
         return bits, got["Hs0"], got["He0"]
 
@@ -1100,7 +1135,7 @@ class receiver(transmitter):
         llr = eng._new((F, cfg.D, cfg.C, cfg.mu), torch.float32)
         for lo, hi, Ys in self._data_spectra(eng, xs, moved, F):
             eng.stbc_detect(Ys, [H[lo:hi] for H in Hs], slope[lo:hi], out=llr[lo:hi], weights=None if w is None else w[:, lo:hi])
-        bits_t, rows = self._decode_llrs(eng, plan, llr.reshape(-1))
+        bits_t, rows, _ = self._decode_llrs(eng, plan, llr.reshape(-1))
         rows["last_stbc_slope"] = slope
         if w is not None:
             # the SNR after combining both speakers' paths of every recording under its weight

@@ -12,6 +12,7 @@ DT_F64, DT_F32, DT_I16, DT_U8 = 0, 1, 2, 3
 GF3_MAX_BRANCHES = 4                    # gf3_combine_branches: branches at most
 GF3_COMBINE_CSI, GF3_COMBINE_NOISE = 0, 1
 GF3_MIMO_STREAMS = 2                    # gf3_mimo_detect: streams sent at once
+GF3_LLR_KNOWN = 1e30                    # gf3_mimo_detect_known: magnitude of a known bit's LLR (float32)
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -157,6 +158,8 @@ _SIGS = {
                                      C.c_void_p]),
     "gf3_stbc_detect_nw": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p]),
+    "gf3_mimo_detect_known": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_void_p]),
     "gf3_track_phase": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gf3_feedback_equalise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -54,6 +54,7 @@ class CodedChain:
     feedback_min_known: int = 4             # known symbols a window needs before its gain is used
     loading: tuple = None                   # adaptive bit loading (loading.py): the validated order per data carrier; per_packet then counts its bits
     denoise: tuple = None                   # receive() under `channel_denoising`: (denoise_threshold as the façade holds it, no_pilots)
+    mimo_cancellation: int = 0              # receive_mimo(): extra passes at most, each detected again with the trusted codewords' bits known
 
     # ---- settings and their refusals -----------------------------------------------------------------------------------
     def rate(self):
@@ -155,6 +156,13 @@ class CodedChain:
         except (TypeError, ValueError):
             raise ValueError(f"feedback_window must be (half_symbols, half_bins), not {self.feedback_window!r}")
         return (int(n),) + Engine.check_feedback_window(hs, hb, self.feedback_min_known)
+
+    def cancellation(self):
+        """The passes of `mimo_cancellation`; ValueError for a count that is not an integer >= 0."""
+        n = self.mimo_cancellation
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"mimo_cancellation must be an integer >= 0 (the extra passes at most), not {n!r}")
+        return int(n)
 
     # ---- transmit side ---------------------------------------------------------------------------------------------------
     def encode(self, bits, rate, even=False):
@@ -338,43 +346,91 @@ class CodedChain:
         ORIGINAL tracked `eq` and divide it out, weighs the result again and decodes the untrusted codewords alone.
         Passes are not cumulative (each starts from the same `eq` with more known symbols).  The loop ends when nothing
         is untrusted or a pass trusts nothing new; every pass, and the first decode, costs one small read-back (the
-        numbers of the untrusted codewords).  The outer code then sees the final bits and erasures.
+        codewords' flags).  The loop itself is `decode_again`, which decode_cancel shares.  The outer code then sees the
+        final bits and erasures.
         -> (message bits, iters, group statuses, CRC flags or None, the host rows of `llrs`, {"feedback_passes",
         "feedback_recovered"})."""
         passes, hs, hb, min_known = self.feedback()
         o, rows = self.track(eng, o)
         llr, snr = self.weigh(eng, o, points)
-        n_llr = llr.numel()
-        n_cw = n_llr // code.n
+        last = {"snr": snr}
+
+        def again(full, trusted, untrusted):
+            bits, known = self.known_planes(eng, code, full, trusted, llr.numel() // self.per_packet)
+            fb = dict(o)
+            fb["eq"] = eng.feedback_equalise(o["eq"], bits, known, hs, hb, min_known)
+            new, last["snr"] = self.weigh(eng, fb, points)
+            return new
+        dec, iters, bad, erase, done, recovered = self.decode_again(code, llr, passes, again)
+        rows.update(last["snr"])
+        bits, iters, status, bad = self.outer_recover(dec, iters, bad, erase, llr.numel())
+        return bits, iters, status, bad, rows, {"feedback_passes": done, "feedback_recovered": recovered}
+
+    def decode_cancel(self, eng, code, llr, detect):
+        """receive_mimo() under `mimo_cancellation`: the first decode of the joint detector's `llr` as without it; then up
+        to `mimo_cancellation` passes of successive interference cancellation.  The bookkeeping is decode_feedback's
+        (`decode_again`): a pass re-encodes the TRUSTED codewords and lays their coded bits and a per-bit mask out over the
+        packets in transmitted order, which is the layout of the detector's LLRs.  `detect(pairs, bits, known)` -- the
+        façade's: the data symbols' spectra of those packet pairs again, Engine.mimo_detect_known on them under the call's
+        weights -- is asked for the LLRs [len(pairs), 2 per_packet] of the packet pairs (ascending, a host array) that hold
+        a bit of an untrusted codeword, given those pairs' rows of the two planes; the untrusted codewords alone are
+        decoded from them.  Passes are cumulative only in what is known: each detects from the same spectra.  One small
+        read-back per pass.  -> (message bits, iters, group statuses, CRC flags or None, {"cancel_passes",
+        "cancel_recovered"})."""
+        llr = llr.reshape(-1)                                   # (the façade's own buffer: the passes overwrite their pairs' rows)
+        n, pair = code.n, 2 * self.per_packet
+
+        def again(full, trusted, untrusted):
+            bits, known = self.known_planes(eng, code, full, trusted, llr.numel() // self.per_packet)
+            lo, hi = untrusted * n // pair, ((untrusted + 1) * n - 1) // pair     # (first and last pair of each codeword)
+            pairs = np.unique(np.concatenate([np.arange(a, b + 1) for a, b in zip(lo, hi)]))
+            at = torch.from_numpy(pairs).to(llr.device)
+            llr.view(-1, pair)[at] = detect(pairs, bits.view(-1, pair)[at], known.view(-1, pair)[at]).reshape(len(pairs), pair)
+            return llr
+        dec, iters, bad, erase, done, recovered = self.decode_again(code, llr, self.cancellation(), again)
+        bits, iters, status, bad = self.outer_recover(dec, iters, bad, erase, llr.numel())
+        return bits, iters, status, bad, {"cancel_passes": done, "cancel_recovered": recovered}
+
+    def known_planes(self, eng, code, full, trusted, F):
+        """The message rows `full` [n_cw, code.k] and the 0 / 1 flags `trusted` [n_cw] -> (bits, known): uint8 [F, per_packet]
+        in transmitted order, the trusted codewords re-encoded (every row goes through the encoder, the untrusted ones
+        zeroed and masked rather than compacted) and one mask byte per coded bit."""
+        n_cw = full.shape[0]
+        planes = []
+        for rows_u8 in (code.encode(full * trusted[:, None]), trusted[:, None].expand(n_cw, code.n)):
+            plane = torch.zeros((F, self.per_packet), dtype=torch.uint8, device=full.device)
+            plane.view(-1)[: n_cw * code.n] = rows_u8.reshape(-1)
+            planes.append(eng.interleave(plane, inverse=False) if self.interleave else plane)
+        return planes
+
+    def decode_again(self, code, llr, passes, again):
+        """What decode_feedback and decode_cancel share: the first decode of the whole codewords of `llr` (coded order), then
+        up to `passes` more.  A codeword is TRUSTED once it converged and, under `codeword_crc`, its CRC matches; its
+        message row is frozen from then on.  A pass asks `again(message rows [n_cw, code.k], trusted flags uint8 [n_cw],
+        the untrusted codewords' numbers (host, ascending))` for new LLRs in coded order and decodes the untrusted
+        codewords alone.  The loop ends when nothing is untrusted or a pass trusts nothing new; every pass, and the first
+        decode, costs one small read-back (the flags).  -> (the message bits per codeword, iters, CRC flags or None, the
+        counts the outer code erases by, the passes run, the codewords they came to trust)."""
+        n_cw = llr.numel() // code.n
         full, dec, iters, bad, erase = self.inner(code, llr[: n_cw * code.n])
-        F = n_llr // self.per_packet
         first = None
         done = 0
         while True:
-            untrusted = torch.nonzero(erase <= 0).reshape(-1)   # (the read-back: a codeword is trusted once erase > 0)
-            left = int(untrusted.numel())
+            untrusted = np.flatnonzero(erase.cpu().numpy() <= 0)    # (the read-back: a codeword is trusted once erase > 0)
+            left = len(untrusted)
             first = left if first is None else first
             if done and left == last:
                 break
             last = left
             if done == passes or left == 0:
                 break
-            trusted = (erase > 0).to(torch.uint8)
-            planes = []
-            for rows_u8 in (code.encode(full * trusted[:, None]), trusted[:, None].expand(n_cw, code.n)):
-                plane = torch.zeros((F, self.per_packet), dtype=torch.uint8, device=full.device)
-                plane.view(-1)[: n_cw * code.n] = rows_u8.reshape(-1)
-                planes.append(eng.interleave(plane, inverse=False) if self.interleave else plane)
-            fb = dict(o)
-            fb["eq"] = eng.feedback_equalise(o["eq"], planes[0], planes[1], hs, hb, min_known)
-            llr, snr = self.weigh(eng, fb, points)
-            sub = llr[: n_cw * code.n].reshape(n_cw, code.n)[untrusted]
+            llr = again(full, (erase > 0).to(torch.uint8), untrusted)
+            at = torch.from_numpy(untrusted).to(full.device)
+            sub = llr[: n_cw * code.n].reshape(n_cw, code.n)[at]
             full_u, dec_u, iters_u, bad_u, erase_u = self.inner(code, sub)
-            full[untrusted] = full_u
-            iters[untrusted] = iters_u
+            full[at] = full_u
+            iters[at] = iters_u
             if self.codeword_crc:
-                dec[untrusted], bad[untrusted], erase[untrusted] = dec_u, bad_u, erase_u
+                dec[at], bad[at], erase[at] = dec_u, bad_u, erase_u
             done += 1
-        rows.update(snr)
-        bits, iters, status, bad = self.outer_recover(dec, iters, bad, erase, n_llr)
-        return bits, iters, status, bad, rows, {"feedback_passes": done, "feedback_recovered": first - last}
+        return dec, iters, bad, erase, done, first - last

@@ -22,7 +22,8 @@
 //                            gf3_soft_demap_loaded (adaptive bit loading: a QAM order per carrier, the noise pair for such a packet)
 //   gf3rx_combine.hip        combine_kernel + gf3_combine_branches (receive diversity: maximal-ratio combining of B branches' symbols)
 //   gf3rx_mimo.hip           mimo_pilots_kernel, mimo_detect_kernel + gf3_mimo_pilots, gf3_mimo_detect (2 x 2 spatial multiplexing: both
-//                            columns of the channel from the covered pilots; joint max-log ML detection of the two streams)
+//                            columns of the channel from the covered pilots; joint max-log ML detection of the two streams;
+//                            gf3_mimo_detect_known: the same detector told which coded bits are already known)
 //   gf3rx_stbc.hip           stbc_slope_kernel, stbc_detect_kernel + gf3_stbc_slope, gf3_stbc_detect (transmit diversity: the Alamouti code over
 //                            pairs of data symbols; one phase slope from all paths, joint max-log ML detection of a pair)
 //   gf3rx_track.hip          track_phase_kernel + gf3_track_phase (per-symbol phase and timing tracking inside a packet)

@@ -1,5 +1,6 @@
 // libgf3rx -- 2 x 2 spatial multiplexing: the two-column pilot estimate (gf3_mimo_pilots) and the joint max-log ML
-// detector of the two streams (gf3_mimo_detect).  Not in the reference; see include/gf3rx.h and DESIGN.md §12.
+// detector of the two streams (gf3_mimo_detect, gf3_mimo_detect_nw with weights, gf3_mimo_detect_known with known bits).
+// Not in the reference; see include/gf3rx.h and DESIGN.md §12.
 //
 // Wire format: speaker 0 sends chirps and pilots as ever, speaker 1 is silent during the chirps and negates its pilot
 // symbols of odd index, so at microphone b   Y_p[k] = (H_b0[k] + (-1)^p H_b1[k]) X[k]   and, P being even,
@@ -14,7 +15,11 @@
 //   bin data_bins[c]: B x 16 bytes per cell, 16 bytes written.  Every sum runs in a fixed order, no atomics: two runs
 //   give identical bytes.  NW (gf3_mimo_detect_nw): one weight per branch and carrier, read into a register ahead of the
 //   symbol loop, multiplies that branch's term of every sum; a weight that is 0 or not finite takes the branch out at that
-//   carrier.  The NW = false instantiations are the arithmetic they were.
+//   carrier.  The NW = false instantiations are the arithmetic they were.  KN (gf3_mimo_detect_known): one byte per coded
+//   bit says whether the bit is known and one which it is, in the layout of the LLRs; a thread reads its 2 x 2 + 2 x 2 bytes
+//   of a cell as four 2-byte loads and forms one 4-bit mask of admissible points per stream; a pair with an inadmissible
+//   point enters the two reductions as INFINITY, a known bit leaves as -+GF3_LLR_KNOWN.  Selects and minima round nothing:
+//   with nothing known the bytes are those of the KN = false instantiations, which are the code they were.
 #include "gf3rx_demap.h"
 
 namespace {
@@ -101,9 +106,18 @@ struct MimoDetectArgs {
     int D, C, K, NB, P, Dc, ntile;
     const double* cre; const double* cim; const int* clab;      // the 4 points and their labels
     const double* wgt;                      // NW: [B][F][C] the branches' weights (gf3_joint_noise_weights)
+    const uint8_t* bits; const uint8_t* known;                  // KN: [F][2][D][C][2] a bit's value, whether it is known
 };
 
-template <int B, bool NW>
+// the two bytes of one stream's symbol at a cell (any alignment: the planes are byte arrays)
+struct BytePair { uint8_t v[2]; };
+GF3_DEV BytePair byte_pair(const uint8_t* p, int64_t cell) {
+    BytePair r;
+    __builtin_memcpy(&r, p + 2 * cell, 2);
+    return r;
+}
+
+template <int B, bool NW, bool KN>
 __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs a) {
     const int t = threadIdx.x;
     const int tile = blockIdx.x % a.ntile, chunk = blockIdx.x / a.ntile;
@@ -146,6 +160,13 @@ __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs 
     int lab[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { px[i] = a.cre[i]; py[i] = a.cim[i]; lab[i] = a.clab[i]; }
+    unsigned ones[2] = {0u, 0u};                            // KN: bit i of ones[k] <=> point i carries bit k as 1
+    if constexpr (KN) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) ones[k] |= (unsigned)((lab[i] >> (1 - k)) & 1) << i;
+    }
 
     for (int l = l0; l < l1; ++l) {
         const int64_t sym = f * D + l;
@@ -181,15 +202,33 @@ __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs 
         // over x1 with x0 = point i, best[1][j] the minimum over x0 with x1 = point j.  A bit of stream s then needs the
         // minimum of best[s] over the points that carry it as 1, and as 0 -- 8 selects per bit where the plain scan of the
         // pairs has 64.  (Minima round nothing: the numbers are those of the plain scan.)
+        // KN: adm[s] bit i set <=> point i agrees with every known bit of stream s at this cell (never empty: 4 labels).  An
+        // inadmissible point's own term A or Bj is INFINITY, and with it every pair's metric that holds the point; the
+        // admissible pairs' metrics are the sums they were.
+        BytePair kb[2], kk[2];
+        unsigned adm[2] = {15u, 15u};
+        if constexpr (KN) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int64_t cell = ((f * 2 + s) * D + l) * (int64_t)a.C + c;
+                kb[s] = byte_pair(a.bits, cell);
+                kk[s] = byte_pair(a.known, cell);
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+                    if (kk[s].v[k] != 0) adm[s] &= kb[s].v[k] != 0 ? ones[k] : ~ones[k];
+            }
+        }
         double A[4], best[2][4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             A[i] = G00 * (px[i] * px[i] + py[i] * py[i]) - 2.0 * (px[i] * m0.x + py[i] * m0.y);
+            if constexpr (KN) A[i] = (adm[0] >> i) & 1u ? A[i] : INFINITY;
             best[0][i] = INFINITY;
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const double Bj = G11 * (px[j] * px[j] + py[j] * py[j]) - 2.0 * (px[j] * m1.x + py[j] * m1.y);
+            double Bj = G11 * (px[j] * px[j] + py[j] * py[j]) - 2.0 * (px[j] * m1.x + py[j] * m1.y);
+            if constexpr (KN) Bj = (adm[1] >> j) & 1u ? Bj : INFINITY;
             const cplx q = cmul(G01, cmk(px[j], py[j]));
             best[1][j] = INFINITY;
 #pragma unroll
@@ -212,6 +251,8 @@ __global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs 
                     zero = fmin(zero, bit ? INFINITY : best[s][i]);
                 }
                 out[k] = any ? (float)(one - zero) : 0.0f;
+                if constexpr (KN)
+                    if (kk[s].v[k] != 0) out[k] = kb[s].v[k] != 0 ? -GF3_LLR_KNOWN : GF3_LLR_KNOWN;
             }
             store_llr<2>(a.llr, ((f * 2 + s) * D + l) * (int64_t)a.C + c, out);
         }
@@ -237,21 +278,33 @@ extern "C" int gf3_mimo_pilots(gf3_ctx* c, const void* d_in, int64_t n_in, const
     return GF3_OK;
 }
 
-// both entries of the detector: `who` names the caller in a refusal, d_w is null for the unweighted one
-template <bool NW>
+// the entries of the detector: `who` names the caller in a refusal, d_w is null for the unweighted ones, KN takes the planes
+template <bool NW, bool KN>
+static void mimo_detect_launch(int B, dim3 grid, hipStream_t st, const MimoDetectArgs& a) {
+    switch (B) {
+        case 1: hipLaunchKernelGGL((mimo_detect_kernel<1, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((mimo_detect_kernel<2, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((mimo_detect_kernel<3, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
+        default: hipLaunchKernelGGL((mimo_detect_kernel<4, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
+    }
+}
+
+template <bool NW, bool KN>
 static int mimo_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* const* d_Y, const void* const* d_H,
-                            const double* const* d_slope, const double* d_w, int64_t F, float* d_llr, void* stream) {
+                            const double* const* d_slope, const double* d_w, const uint8_t* d_bits, const uint8_t* d_known,
+                            int64_t F, float* d_llr, void* stream) {
     DeviceGuard dg(c);
     if (!c) return fail(c, GF3_EINVAL, "%s: null context", who);
     if (c->cfg.mu != 2 || c->cfg.M != 4)
         return fail(c, GF3_EINVAL, "%s: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)", who,
                     c->cfg.M, c->cfg.mu);
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w);
+    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w) && (!KN || (d_bits && d_known));
     for (int b = 0; ok && b < B; ++b) ok = d_Y[b] && d_H[b] && d_slope[b];
     if (!ok)
-        return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra, estimates and slopes; %s"
-                                   "an output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "");
+        return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra, estimates and slopes; %s%s"
+                                   "an output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "",
+                    KN ? "the planes of the bits and of what is known; " : "");
     if (const int rc = too_many_packets(c, F, who)) return rc;
     MimoDetectArgs a{};
     for (int b = 0; b < B; ++b) { a.Y[b] = (const cplx*)d_Y[b]; a.H[b] = (const cplx*)d_H[b]; a.slope[b] = d_slope[b]; }
@@ -262,24 +315,27 @@ static int mimo_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* 
     a.Dc = symbols_per_group(c, F * a.ntile, a.D);
     a.cre = c->d_cre; a.cim = c->d_cim; a.clab = c->d_clab;
     a.wgt = d_w;
+    a.bits = d_bits; a.known = d_known;
     const dim3 grid((unsigned)(a.ntile * ((a.D + a.Dc - 1) / a.Dc)), (unsigned)F);
-    const hipStream_t st = (hipStream_t)stream;
-    switch (B) {
-        case 1: hipLaunchKernelGGL((mimo_detect_kernel<1, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((mimo_detect_kernel<2, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((mimo_detect_kernel<3, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((mimo_detect_kernel<4, NW>), grid, dim3(MD_THREADS), 0, st, a); break;
-    }
+    mimo_detect_launch<NW, KN>(B, grid, (hipStream_t)stream, a);
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }
 
 extern "C" int gf3_mimo_detect(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* const* d_slope,
                                int64_t F, float* d_llr, void* stream) {
-    return mimo_detect_call<false>(c, "gf3_mimo_detect", B, d_Y, d_H, d_slope, nullptr, F, d_llr, stream);
+    return mimo_detect_call<false, false>(c, "gf3_mimo_detect", B, d_Y, d_H, d_slope, nullptr, nullptr, nullptr, F, d_llr, stream);
 }
 
 extern "C" int gf3_mimo_detect_nw(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H, const double* const* d_slope,
                                   const double* d_w, int64_t F, float* d_llr, void* stream) {
-    return mimo_detect_call<true>(c, "gf3_mimo_detect_nw", B, d_Y, d_H, d_slope, d_w, F, d_llr, stream);
+    return mimo_detect_call<true, false>(c, "gf3_mimo_detect_nw", B, d_Y, d_H, d_slope, d_w, nullptr, nullptr, F, d_llr, stream);
+}
+
+extern "C" int gf3_mimo_detect_known(gf3_ctx* c, int32_t B, const void* const* d_Y, const void* const* d_H,
+                                     const double* const* d_slope, const double* d_w, const uint8_t* d_bits, const uint8_t* d_known,
+                                     int64_t F, float* d_llr, void* stream) {
+    const char* who = "gf3_mimo_detect_known";
+    return d_w ? mimo_detect_call<true, true>(c, who, B, d_Y, d_H, d_slope, d_w, d_bits, d_known, F, d_llr, stream)
+               : mimo_detect_call<false, true>(c, who, B, d_Y, d_H, d_slope, nullptr, d_bits, d_known, F, d_llr, stream);
 }

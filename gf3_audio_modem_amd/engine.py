@@ -921,31 +921,7 @@ class Engine:
         (gf3_mimo_detect_nw): branch b's term of the metric at carrier c is multiplied by w[b, f, c] -- maximum likelihood
         for noise of variance 1 / w --, and a branch whose weight is 0 drops out there as a non-finite estimate does.
         Needs a table of 4 points with mu = 2 (ValueError)."""
-        cfg = self.cfg
-        Ys, Hs, slopes = list(Ys), list(Hs), list(slopes)
-        B = len(Ys)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"mimo_detect: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
-        if len(Hs) != B or len(slopes) != B:
-            raise ValueError(f"mimo_detect: Hs holds {len(Hs)} branches and slopes {len(slopes)}, Ys {B}")
-        if cfg.mu != 2 or len(self._re) != 4:
-            raise ValueError(f"mimo_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
-                             f"points with mu = {cfg.mu}")
-        Ys = [self._dev(y) for y in Ys]
-        Hs = [self._dev(h) for h in Hs]
-        slopes = [self._dev(s, torch.float64) for s in slopes]
-        NB = cfg.N // 2 + 1
-        if Ys[0].numel() % (cfg.D * NB):
-            raise ValueError("mimo_detect: Ys must be [F*D, N/2+1] for whole packets")
-        F = Ys[0].numel() // (cfg.D * NB)
-        if any(y.numel() != F * cfg.D * NB for y in Ys):
-            raise ValueError("mimo_detect: every branch needs Y [F*D, N/2+1] of the same F")
-        if any(h.numel() != F * 4 * cfg.K for h in Hs):
-            raise ValueError("mimo_detect: every H must be [F, 2, 2, K] for Y [F*D, N/2+1]")
-        if any(s.numel() != F for s in slopes):
-            raise ValueError("mimo_detect: every slope must be [F] for Y [F*D, N/2+1]")
-        shape = (F, _lib.GF3_MIMO_STREAMS, cfg.D, cfg.C, cfg.mu)
-        llr = self._out(out, shape, torch.float32, "F*2*D*C*mu", name="mimo_detect: out")
+        B, F, Ys, Hs, slopes, llr = self._mimo_detect_args("mimo_detect", Ys, Hs, slopes, out)
 
         def table(xs):
             return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
@@ -955,6 +931,57 @@ class Engine:
             w = self._joint_weights(weights, B, F, "mimo_detect")
             self._check(self.lib.gf3_mimo_detect_nw(self._h, B, table(Ys), table(Hs), table(slopes), _ptr(w), F, _ptr(llr),
                                                     self._stream()))
+        return llr
+
+    def _mimo_detect_args(self, who, Ys, Hs, slopes, out):
+        """What mimo_detect and mimo_detect_known check of their common arguments -> (B, F, the branches' tensors on the
+        device, the output [F, 2, D, C, mu])"""
+        cfg = self.cfg
+        Ys, Hs, slopes = list(Ys), list(Hs), list(slopes)
+        B = len(Ys)
+        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"{who}: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        if len(Hs) != B or len(slopes) != B:
+            raise ValueError(f"{who}: Hs holds {len(Hs)} branches and slopes {len(slopes)}, Ys {B}")
+        if cfg.mu != 2 or len(self._re) != 4:
+            raise ValueError(f"{who}: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
+                             f"points with mu = {cfg.mu}")
+        Ys = [self._dev(y) for y in Ys]
+        Hs = [self._dev(h) for h in Hs]
+        slopes = [self._dev(s, torch.float64) for s in slopes]
+        NB = cfg.N // 2 + 1
+        if Ys[0].numel() % (cfg.D * NB):
+            raise ValueError(f"{who}: Ys must be [F*D, N/2+1] for whole packets")
+        F = Ys[0].numel() // (cfg.D * NB)
+        if any(y.numel() != F * cfg.D * NB for y in Ys):
+            raise ValueError(f"{who}: every branch needs Y [F*D, N/2+1] of the same F")
+        if any(h.numel() != F * 4 * cfg.K for h in Hs):
+            raise ValueError(f"{who}: every H must be [F, 2, 2, K] for Y [F*D, N/2+1]")
+        if any(s.numel() != F for s in slopes):
+            raise ValueError(f"{who}: every slope must be [F] for Y [F*D, N/2+1]")
+        shape = (F, _lib.GF3_MIMO_STREAMS, cfg.D, cfg.C, cfg.mu)
+        return B, F, Ys, Hs, slopes, self._out(out, shape, torch.float32, "F*2*D*C*mu", name=f"{who}: out")
+
+    def mimo_detect_known(self, Ys, Hs, slopes, bits, known, out=None, weights=None):
+        """mimo_detect told what is already known (gf3_mimo_detect_known): `bits` and `known` are uint8 tensors of F*2*D*C*mu
+        elements on the engine's device, one byte per coded bit in the layout of the LLRs -- the transmitted order of packets
+        2f, 2f + 1.  A non-zero `known` byte: the bit is known, and is 1 where its `bits` byte is non-zero.  The metric,
+        the branches' rules and `weights` are mimo_detect's; a pair of points that contradicts a known bit of either
+        stream is left out of every minimum.  An unknown bit gets min over the pairs left with it 1 - min with it 0 (+0 where
+        no branch is left), a known bit -+GF3_LLR_KNOWN (1e30: finite).  With `known` all zero the bytes are mimo_detect's.
+        Everything else -- arguments, output, ValueError -- as mimo_detect."""
+        who = "mimo_detect_known"
+        B, F, Ys, Hs, slopes, llr = self._mimo_detect_args(who, Ys, Hs, slopes, out)
+        for name, plane in (("bits", bits), ("known", known)):
+            if (not isinstance(plane, torch.Tensor) or plane.dtype != torch.uint8 or plane.device.type != self.device.type
+                    or not plane.is_contiguous() or plane.numel() != llr.numel()):
+                raise ValueError(f"{who}: {name} must be a contiguous uint8 tensor of F*2*D*C*mu = {llr.numel()} elements on {self.device}")
+        w = None if weights is None else self._joint_weights(weights, B, F, who)
+
+        def table(xs):
+            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
+        self._check(self.lib.gf3_mimo_detect_known(self._h, B, table(Ys), table(Hs), table(slopes), _ptr(w), _ptr(bits), _ptr(known),
+                                                   F, _ptr(llr), self._stream()))
         return llr
 
     def _stbc_geometry(self, who):

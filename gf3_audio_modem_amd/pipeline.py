@@ -122,6 +122,7 @@ class ReceivePlan(NamedTuple):
     rates: object = None                    # check_input_rates' answer: per recording None or (input rate, half_taps), or None
     advance: int = 0                        # receive_mimo: samples every packet start is moved back by (`mimo_advance`)
     joint_noise: bool = False               # receive_mimo, receive_stbc: pilot-measured weights (`joint_weighting` = "noise")
+    cancel: int = 0                         # receive_mimo: passes of decoder-driven cancellation at most (`mimo_cancellation`)
 
 
 def check_mimo_pilots(no_pilots):
@@ -150,11 +151,24 @@ def check_joint_weighting(joint_weighting, no_pilots, who):
     return joint_weighting == "noise"
 
 
-def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams", verb="separates"):
+def check_cancellation(chain, rate, who, cancels):
+    """`mimo_cancellation` -> the passes as an int.  ValueError for a value that is not an integer >= 0, for a value > 0
+    under an encoding without codewords to trust, and (cancels False: the space-time code) for any value > 0."""
+    passes = chain.cancellation()
+    if passes and not cancels:
+        raise ValueError(f"{who}: mimo_cancellation cancels one stream of two out of the other; the pair of the space-time code "
+                         "decouples and there is nothing to cancel; leave it at 0")
+    if passes and rate is None:
+        raise ValueError(f"{who}: mimo_cancellation needs a 'QCLDPC-*' encoding, not {chain.encoding!r}: the decoded codewords "
+                         "are what is cancelled")
+    return passes
+
+
+def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams", verb="separates", cancels=True):
     """The plan of receive_mimo() on recordings of `lengths` samples, in plan_receive's manner and order: the pilot cover's
     and the coded chain's own refusals (CodedChain.check_mimo), the values of the joint weighting, the advance, the clock
     correction, the sync rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work.
-    (plan_stbc names itself in `who`.)"""
+    (plan_stbc names itself in `who` and, with cancels = False, refuses `mimo_cancellation`.)"""
     check_mimo_pilots(rx.no_pilots)
     rate = chain.check_mimo(who, what)
     joint_noise = check_joint_weighting(rx.joint_weighting, rx.no_pilots, who)
@@ -162,6 +176,7 @@ def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams",
     clock = check_clock(rx.clock_correction, rx.clock_taps)
     detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
     rates = check_input_rates(rx, len(lengths), True)
+    cancel = check_cancellation(chain, rate, who, cancels)
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
     no_path = ((rx.impulse_blanking, f"{who}: impulse_blanking is not applied; blank each recording's samples with "
@@ -174,7 +189,7 @@ def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams",
         if on:
             raise NotImplementedError(why.format(host=_HOST))
     return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance,
-                       joint_noise)
+                       joint_noise, cancel)
 
 
 def check_stbc_length(packet_length):
@@ -185,8 +200,9 @@ def check_stbc_length(packet_length):
 
 
 def plan_stbc(rx, chain, lengths, plots):
-    """The plan of receive_stbc(): plan_mimo's checks under its own name, and the pairing of the data symbols."""
-    plan = plan_mimo(rx, chain, lengths, plots, "receive_stbc", "the space-time code", "decodes")
+    """The plan of receive_stbc(): plan_mimo's checks under its own name (a `mimo_cancellation` > 0 refused: nothing to
+    cancel), and the pairing of the data symbols."""
+    plan = plan_mimo(rx, chain, lengths, plots, "receive_stbc", "the space-time code", "decodes", cancels=False)
     check_stbc_length(rx.packet_length)
     return plan
 

@@ -810,6 +810,32 @@ int gf3_stbc_detect_nw(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, con
                        const double *d_slope_f64, const double *d_w_f64, int64_t F, float *d_llr_f32, void *stream);
 
 /*
+ * Spatial multiplexing with known bits (not in the reference): the joint detector told what a decoder has already settled,
+ * for successive interference cancellation driven by the code.  The two packets of a pair share every cell and their
+ * codewords are different codewords; once one stream's bit at a cell is known, the pairs that contradict it are out, and
+ * with x0 wholly known stream 1 sees y - h0 x0 through h1 alone: gain G11 instead of G11 (1 - |G01|^2 / (G00 G11)).
+ *   - gf3_mimo_detect_known: gf3_mimo_detect (d_w_f64 null) or gf3_mimo_detect_nw (d_w_f64 [B][F][C]) with two more inputs,
+ *     d_bits_u8 and d_known_u8 [F][GF3_MIMO_STREAMS][D][C][mu] uint8, one byte per coded bit in the layout and order of the
+ *     LLRs (the transmitted order of packets 2f and 2f + 1): a non-zero d_known_u8 byte says the bit is known, a non-zero
+ *     d_bits_u8 byte that it is 1 (read where the bit is known only).  G00, G11, G01, m0, m1, the rule that leaves a branch
+ *     out and the order of every sum are those calls'.  A pair (x0 = point i, x1 = point j) is ADMISSIBLE when for both
+ *     streams every known bit of the cell equals that bit of the stream's point's label.  Then
+ *       an unknown bit: LLR = min over the admissible pairs with that bit 1 - min over the admissible pairs with that bit 0
+ *                       (neither set is empty: 4 points, 4 labels); +0 where no branch is left
+ *       a known bit:    -GF3_LLR_KNOWN if it is 1, +GF3_LLR_KNOWN if it is 0, also where no branch is left
+ *     GF3_LLR_KNOWN is finite, so nothing downstream forms inf - inf.  Minima round nothing: with d_known_u8 all zero the
+ *     output is byte for byte gf3_mimo_detect's (d_w_f64 null) or gf3_mimo_detect_nw's.
+ *     GF3_EINVAL for a null context, a context whose table is not mu = 2 with 4 points, B out of range, a null pointer (a
+ *     null d_w_f64 selects the unweighted metric), F < 0, more than 65535 packets.  F == 0 is a no-op.
+ *   One launch, no allocation, no host synchronisation, asynchronous on `stream`; every sum in a fixed order, no atomics:
+ *   two calls give identical bytes.  The text of a refusal names the function.
+ */
+#define GF3_LLR_KNOWN 1e30f
+int gf3_mimo_detect_known(gf3_ctx *ctx, int32_t B, const void *const *d_Y_c128, const void *const *d_H_c128,
+                          const double *const *d_slope_f64, const double *d_w_f64, const uint8_t *d_bits_u8,
+                          const uint8_t *d_known_u8, int64_t F, float *d_llr_f32, void *stream);
+
+/*
  * Per-symbol phase and timing tracking inside a packet (not in the reference, whose channel model is fixed at the two
  * pilot blocks and interpolated linearly between them).  Opt-in; a stage of its own on the equalised symbols, before
  * any of the weights above.  Per packet, sequentially over the data symbols l = 0 .. D-1, two numbers are followed by a
