@@ -245,7 +245,9 @@ int gf3_demod_frames_dn(gf3_ctx *ctx, const void *d_in, int64_t n_in,
 /* tests: the screening pass alone.  d_ep32 [F][D][C] complex64: the rotated fp32 symbols (2 X conj(g)) of the data carriers
  * in data_bins order; d_E [F][D] float32: the bound of each symbol; d_cls [F] int32: 0 decided, 1 listed; d_list: AT LEAST
  * gf3_demod_screen_workspace_bytes(ctx, F) bytes, [count | pad to 64 bytes | listed packet numbers]; d_bits_packed gets the
- * screen's own rows.  Fails where the screen does not apply. */
+ * screen's own rows.  Fails where the screen does not apply.  A packet whose samples fall outside [0, n_in) gets a zero row
+ * of d_bits_packed and d_cls 0 and is not listed; its rows of d_ep32 and d_E are NOT written.  Of d_list the count word is
+ * defined; the pad and the order of the entries behind it are not. */
 int64_t gf3_demod_screen_workspace_bytes(const gf3_ctx *ctx, int64_t F);
 /* tests: the fp32 transform of the screened demodulation alone (the same passes on single-precision points, the context's
  * twiddles rounded once): d_out_c64 [n_sym, N/2+1] complex64 spectra of the N samples at each offset, as gf3_rfft_batch
@@ -477,6 +479,9 @@ int gf3_demap_hard(gf3_ctx *ctx, const void *d_sym_c128, int64_t n,
  *                      indexed by carrier (entries of data carriers are ignored)
  *   d_gaps        [F] int64 leading zeros per row, or NULL
  *   out_dtype     GF3_F32 or GF3_F64
+ * Every sample of every row is written, the zeros included.  GF3_EINVAL, and nothing written, for a stride shorter than
+ * one packet, Lc + (2P + D)(N + CP).  The gaps live in device memory and are not checked: 0 <= d_gaps[f] <= stride - that
+ * length is the caller's to keep (a longer gap would carry the packet beyond its row).
  */
 int gf3_tx_frames(gf3_ctx *ctx, const uint8_t *d_bits_packed, const void *d_filler_c128,
                   const int64_t *d_gaps, int64_t F, void *d_out, int64_t stride,
@@ -532,6 +537,7 @@ int gf3_equalise_known_h(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int
  *   out_i64       [F * D*C*mu] int64: DEVICE memory, or PINNED host memory (hipHostMalloc / hipHostRegister -- e.g. a
  *                 torch tensor with pin_memory=True): the kernel then writes the array the reference returns straight
  *                 into host memory, 16 bytes per lane, and no separate copy is needed.  Pageable host memory is refused.
+ *                 out_i64 must be 16-BYTE ALIGNED, wherever it lives (GF3_EINVAL otherwise).
  */
 int gf3_unpack_bits(gf3_ctx *ctx, const uint8_t *d_bits_packed, int64_t F, const uint8_t *d_mask_u8, int32_t n_mask,
                     void *out_i64, void *stream);
@@ -644,7 +650,8 @@ int gf3_interleave(gf3_ctx *ctx, const void *d_in, void *d_out, int64_t F, int32
  *     gf3_soft_demap_csi's weight (|Hs| + (|He| - |Hs|) (l + P/2) / (D + P))^2 at the carrier's bin.  None: w = 1.
  *     d_var together with d_Hs / d_He, or only one of d_Hs / d_He: GF3_EINVAL.
  *   d_eq_c128 [F*D, C]   d_var_f64 [F, C]   d_Hs / d_He [F, K]   d_llr_f32 [F*D*Bs].  F == 0 is a no-op; at most 65535
- *   packets per call.
+ *   packets per call.  d_llr_f32 must be 8-BYTE ALIGNED (every off[c] and Bs are even, so each carrier's LLRs are stored
+ *   two at a time): GF3_EINVAL otherwise.  Every element of d_llr_f32 is written (a carrier of order 0 owns none).
  */
 typedef struct gf3_loading gf3_loading;
 int gf3_loading_create(const gf3_ctx *ctx, const uint8_t *h_order, int32_t C, gf3_loading **out);

@@ -3,7 +3,11 @@ read into a result or written, every promised element is written, every document
 
 One table row (a key of CASES) per entry that reads samples through (d_in, n_in, offsets) or (d_in, n_in, stride, window);
 the coding entries are in tests/test_bounds_coding_gpu.py, and tests/test_guarded_cpu.py holds the two tables, its EXEMPT
-list and its WITHHELD list (the entries still owed a row, with the reason) to cover `_lib._SIGS`.  Calls go through
+list and its WITHHELD list (the entries still owed a row, with the reason) to cover `_lib._SIGS`.  Sibling files enter
+their rows in THIS table through `case` and run them themselves (their ENTRIES): test_bounds_mimo_gpu.py,
+test_bounds_mimo_known_gpu.py, test_bounds_stbc_gpu.py and test_bounds_joint_noise_gpu.py (the two-speaker entries),
+test_bounds_symbols_gpu.py (everything that takes equalised symbols, spectra or bits), test_bounds_tx_gpu.py (the transmit
+side) and test_bounds_samples_gpu.py (gf3_schmidl_cox, gf3_resample_stream, gf3_debug_demod_screen).  Calls go through
 `eng.lib.<name>(eng._h, ...)`, the explicit-workspace forms wherever they exist.
 
 Geometry: N = 1024, CP = 32, P = 1 (2 where the denoiser needs pilot repeats), D = 3 (odd: the symbol-pair kernels end on a

@@ -5,7 +5,11 @@ written behind it, a promised element left unwritten, an input changed, an eleme
 output -- and every one is reported with the array's name and the byte offset.  A well-behaved stand-in passes, at both
 skews.  The census at the end holds every name of `_lib._SIGS` to be a row of a case table, a key of EXEMPT, or one of the
 entries listed in WITHHELD as still owed a row: a new ABI entry fails it until it has a case."""
+import collections
 import ctypes
+import glob
+import importlib
+import os
 
 import numpy as np
 import pytest
@@ -131,17 +135,20 @@ FAULTED = "a guarded call of its kernels faulted on the GPU with a workspace off
 NO_ROW = "no guarded case yet"
 WITHHELD = {name: FAULTED for name in ("gf3_sync_stream", "gf3_sync_stream_ex", "gf3_sync_chunk", "gf3_sync_decide",
                                        "gf3_detect_chunk", "gf3_detect_decide")}
-WITHHELD.update({name: NO_ROW for name in (
-    "gf3_debug_stream_screen", "gf3_schmidl_cox", "gf3_resample_stream", "gf3_debug_demod_screen", "gf3_equalise",
-    "gf3_demap_hard", "gf3_soft_demap", "gf3_soft_demap_csi", "gf3_noise_estimate", "gf3_soft_demap_nw",
-    "gf3_noise_estimate_cs", "gf3_soft_demap_nw_cs", "gf3_interleave", "gf3_noise_estimate_loaded", "gf3_soft_demap_loaded",
-    "gf3_combine_branches", "gf3_track_phase", "gf3_feedback_equalise", "gf3_unpack_bits", "gf3_tx_frames",
-    "gf3_tx_frames_ex", "gf3_tone_reserve")})
+WITHHELD.update({name: NO_ROW for name in ("gf3_debug_stream_screen",)})      # (with the stream-sync family: its rows wait)
+
+
+def bounds_modules():
+    """Every tests/test_bounds_*_gpu.py, imported in sorted order: the siblings enter their rows in the two tables on import."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    names = sorted(os.path.basename(f)[:-3] for f in glob.glob(os.path.join(here, "test_bounds_*_gpu.py")))
+    return {name: importlib.import_module("tests." + name) for name in names}
+
 
 def test_every_abi_entry_has_a_case_or_an_accepted_exemption():
     from gf3_audio_modem_amd import _lib
-    from tests import test_bounds_coding_gpu as BC
-    from tests import test_bounds_signal_gpu as BS
+    mods = bounds_modules()
+    BC, BS = mods["test_bounds_coding_gpu"], mods["test_bounds_signal_gpu"]
     rows = set(BS.CASES) | set(BC.CASES)
     assert not set(BS.CASES) & set(BC.CASES)
     assert set(EXEMPT.values()) == {NO_DEVICE_MEMORY, HOST_ONLY}
@@ -153,3 +160,17 @@ def test_every_abi_entry_has_a_case_or_an_accepted_exemption():
     assert not known - set(_lib._SIGS), sorted(known - set(_lib._SIGS))
     for name, cases in {**BS.CASES, **BC.CASES}.items():
         assert cases, name
+
+
+def test_every_registered_row_is_run_by_exactly_one_module():
+    """A sibling module enters rows with `BS.case` and runs the names of its own ENTRIES: a name registered and left out of
+    ENTRIES would satisfy the census above and never run.  The union of the modules' ROWS is every (name, i) of both tables,
+    and no pair is in two modules."""
+    mods = bounds_modules()
+    BC, BS = mods["test_bounds_coding_gpu"], mods["test_bounds_signal_gpu"]
+    registered = {(name, i) for table in (BS.CASES, BC.CASES) for name, cases in table.items() for i in range(len(cases))}
+    run = collections.Counter(pair for m in mods.values() for pair in m.ROWS)
+    twice = sorted(pair for pair, n in run.items() if n > 1)
+    assert not twice, f"rows run by two modules: {twice[:5]}"
+    assert set(run) == registered, (sorted(registered - set(run))[:5], sorted(set(run) - registered)[:5])
+    assert WITHHELD["gf3_debug_stream_screen"] == NO_ROW and sum(v == FAULTED for v in WITHHELD.values()) == 6
