@@ -29,8 +29,6 @@ struct CombineArgs {
     DemapTab t;
 };
 
-GF3_DEV bool is_fin(double x) { return fabs(x) < INFINITY; }
-
 template <int B, bool NOISE, int HI>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     __shared__ double red[CB_THREADS];
@@ -95,16 +93,6 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a) {
     }
 }
 
-template <bool NOISE, int HI>
-void launch_combine(int B, dim3 grid, hipStream_t st, const CombineArgs& a) {
-    switch (B) {
-        case 1: hipLaunchKernelGGL((combine_kernel<1, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((combine_kernel<2, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((combine_kernel<3, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((combine_kernel<4, NOISE, HI>), grid, dim3(CB_THREADS), 0, st, a); break;
-    }
-}
-
 }  // namespace
 
 extern "C" int gf3_combine_branches(gf3_ctx* c, int32_t B, const void* const* d_eq, int32_t mode, const void* const* d_Hs,
@@ -130,14 +118,15 @@ extern "C" int gf3_combine_branches(gf3_ctx* c, int32_t B, const void* const* d_
     a.eq_out = (cplx*)d_eq_out; a.wsum = d_wsum; a.llr = d_llr;
     a.bins = c->d_bins;
     a.D = c->cfg.D; a.C = c->cfg.C; a.K = c->K; a.P = c->cfg.P;
-    a.ntile = (a.C + CB_THREADS - 1) / CB_THREADS;
     a.t = demap_tab(c);
-    a.Dc = symbols_per_group(c, F * a.ntile, a.D);
-    const dim3 grid((unsigned)(a.ntile * ((a.D + a.Dc - 1) / a.Dc)), (unsigned)F);
+    const TileGrid g = tile_grid(c, F, a.D, CB_THREADS);
+    a.ntile = g.ntile; a.Dc = g.run;
     with_grid_bits(c, [&](auto hi) {
-        constexpr int HI = decltype(hi)::value;
-        if (noise) launch_combine<true, HI>(B, grid, (hipStream_t)stream, a);
-        else launch_combine<false, HI>(B, grid, (hipStream_t)stream, a);
+        with_branches(B, [&](auto nb) {
+            constexpr int HI = decltype(hi)::value, NB = decltype(nb)::value;
+            if (noise) hipLaunchKernelGGL((combine_kernel<NB, true, HI>), g.grid, dim3(CB_THREADS), 0, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL((combine_kernel<NB, false, HI>), g.grid, dim3(CB_THREADS), 0, (hipStream_t)stream, a);
+        });
     });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;

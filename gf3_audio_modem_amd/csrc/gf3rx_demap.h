@@ -207,6 +207,9 @@ GF3_DEV double csi_weight(cplx hs, cplx he, int l, int P, int D) {
     return csi_weight_mag(hypot(hs.x, hs.y), hypot(he.x, he.y), l, P, D);
 }
 
+// neither NaN nor infinite: what lets a value into a weighted sum (combining, the joint detectors of gf3rx_joint.h)
+GF3_DEV bool is_fin(double x) { return fabs(x) < INFINITY; }
+
 // ---- noise weights ---------------------------------------------------------------------------------------------------
 // A packet's mean variance from the 256 threads' partial sums: a binary tree in LDS (red[256], barriers included), the
 // same number in every workgroup that adds the same partials.  What a thread's partial holds is the caller's matter

@@ -179,7 +179,7 @@ int launch_denoise(const gf3_ctx* c, const void* d_in, int64_t n_in, const int64
                    double* d_psum, double* d_report, hipStream_t st) {
     if (c->cfg.P < 2) return fail(c, GF3_EINVAL, "pilot denoising measures the noise from the pilot repeats: P >= 2 (P=%d)", c->cfg.P);
     if (bad_threshold(threshold)) return fail(c, GF3_EINVAL, "pilot denoising: the threshold must be a finite number > 0");
-    if (F > 0x3fffffff) return fail(c, GF3_EINVAL, "pilot denoising: more than 2^30 - 1 packets in one call");
+    if (const int rc = too_many_packets_i32(c, F, "pilot denoising")) return rc;
     DenoiseArgs a{FftTables{c->d_tw, c->d_twn}, d_in, n_in, d_off, c->cfg.CP, c->S, c->cfg.P, c->cfg.D, c->d_known, threshold,
                   d_psum, d_report};
     hipError_t e = hipSuccess;

@@ -50,6 +50,7 @@
 #include <atomic>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "gf3rx.h"
@@ -317,6 +318,30 @@ static hipError_t launch(Kern k, int64_t grid, int threads, size_t lds, hipStrea
 inline int too_many_packets(const gf3_ctx* c, int64_t F, const char* who) {
     return F > 65535 ? fail(c, GF3_EINVAL, "%s: at most 65535 packets per call", who) : GF3_OK;
 }
+// Kernels whose grid carries the packet in x (two workgroups per packet at the most): at most 2^30 - 1 packets, so that
+// the workgroup count stays a positive 32-bit number.
+inline int too_many_packets_i32(const gf3_ctx* c, int64_t F, const char* who) {
+    return F > 0x3fffffff ? fail(c, GF3_EINVAL, "%s: more than 2^30 - 1 packets in one call", who) : GF3_OK;
+}
+// 1 <= B <= GF3_MAX_BRANCHES, and every table given is there and holds B entries that are not null
+template <typename... Tab>
+inline bool branches_ok(int B, Tab... tabs) {
+    if (B < 1 || B > GF3_MAX_BRANCHES || !(... && (tabs != nullptr))) return false;
+    for (int b = 0; b < B; ++b)
+        if (!(... && (tabs[b] != nullptr))) return false;
+    return true;
+}
+// The one place where a branch count becomes a template argument: fn(std::integral_constant<int, B>) for a checked B, its
+// result handed back (with_grid_bits' idiom, gf3rx_demap.h).
+template <typename Fn>
+inline auto with_branches(int B, Fn&& fn) {
+    switch (B) {
+        case 1: return fn(std::integral_constant<int, 1>{});
+        case 2: return fn(std::integral_constant<int, 2>{});
+        case 3: return fn(std::integral_constant<int, 3>{});
+        default: return fn(std::integral_constant<int, 4>{});
+    }
+}
 // Data symbols per workgroup of a kernel that streams a packet's D symbols, `per` workgroups per chunk of symbols (the
 // packets, times the carrier tiles where a packet has several): about 8 workgroups per compute unit when there are
 // packets enough; a handful of long packets is cut down to single symbols.
@@ -325,6 +350,14 @@ inline int symbols_per_group(const gf3_ctx* c, int64_t per, int D) {
     if (nchunk > D) nchunk = D;
     if (nchunk < 1) nchunk = 1;
     return (int)((D + nchunk - 1) / nchunk);
+}
+// The grid of such a kernel whose threads are carriers: ntile tiles of `threads` data carriers x chunks of `run` of the
+// packet's `units` streamed units (symbols, or pairs of them) in x, the packet in y.
+struct TileGrid { int ntile, run; dim3 grid; };
+inline TileGrid tile_grid(const gf3_ctx* c, int64_t F, int units, int threads) {
+    const int ntile = (c->cfg.C + threads - 1) / threads;
+    const int run = symbols_per_group(c, F * ntile, units);
+    return TileGrid{ntile, run, dim3((unsigned)(ntile * ((units + run - 1) / run)), (unsigned)F)};
 }
 
 #ifdef GF3_DEV_BUILD   /* developer iteration: only N=4096 with f32/f64 samples */

@@ -19,8 +19,6 @@
 
 namespace {
 
-GF3_DEV bool is_fin(double x) { return fabs(x) < INFINITY; }
-
 // ------------------------------------------------------------------------------------------------------------ estimate
 struct PilotNoiseArgs {
     FftTables t;
@@ -142,7 +140,7 @@ extern "C" int gf3_mimo_pilot_noise(gf3_ctx* c, const void* d_in, int64_t n_in, 
     if (F == 0) return GF3_OK;
     if (!d_in || !d_off || !d_H || !d_var || !d_status || F < 0 || n_in < 0)
         return fail(c, GF3_EINVAL, "gf3_mimo_pilot_noise: bad argument");
-    if (F > 0x3fffffff) return fail(c, GF3_EINVAL, "gf3_mimo_pilot_noise: more than 2^30 - 1 packets in one call");
+    if (const int rc = too_many_packets_i32(c, F, "gf3_mimo_pilot_noise")) return rc;
     PilotNoiseArgs a{FftTables{c->d_tw, c->d_twn}, d_in, n_in, d_off, c->cfg.CP, c->S, c->cfg.P, c->cfg.D, c->d_known,
                      (const cplx*)d_H, d_var, d_status};
     hipError_t e = hipSuccess;
@@ -155,25 +153,18 @@ extern "C" int gf3_joint_noise_weights(gf3_ctx* c, int32_t B, const double* cons
     DeviceGuard dg(c);
     if (!c) return fail(c, GF3_EINVAL, "gf3_joint_noise_weights: null context");
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_var && d_w && F >= 0;
-    for (int b = 0; ok && b < B; ++b) ok = d_var[b] != nullptr;
-    if (!ok)
+    if (!(branches_ok(B, d_var) && d_w && F >= 0))
         return fail(c, GF3_EINVAL, "gf3_joint_noise_weights: bad argument (1 <= B <= %d branches of variances; an output; F >= 0)",
                     GF3_MAX_BRANCHES);
-    if (F > 0x3fffffff) return fail(c, GF3_EINVAL, "gf3_joint_noise_weights: more than 2^30 - 1 packets in one call");
+    if (const int rc = too_many_packets_i32(c, F, "gf3_joint_noise_weights")) return rc;
     JointWeightArgs a{};
     for (int b = 0; b < B; ++b) a.var[b] = d_var[b];
     a.w = d_w;
     a.bins = c->d_bins;
     a.C = c->cfg.C; a.K = c->K;
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (B) {
-        case 1: e = launch((joint_weights_kernel<1>), F, VBAR_THREADS, 0, st, a); break;
-        case 2: e = launch((joint_weights_kernel<2>), F, VBAR_THREADS, 0, st, a); break;
-        case 3: e = launch((joint_weights_kernel<3>), F, VBAR_THREADS, 0, st, a); break;
-        default: e = launch((joint_weights_kernel<4>), F, VBAR_THREADS, 0, st, a); break;
-    }
+    const hipError_t e = with_branches(B, [&](auto nb) {
+        return launch((joint_weights_kernel<decltype(nb)::value>), F, VBAR_THREADS, 0, (hipStream_t)stream, a);
+    });
     HIPCHK(c, e);
     return GF3_OK;
 }

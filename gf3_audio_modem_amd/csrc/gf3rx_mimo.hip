@@ -20,11 +20,9 @@
 //   of a cell as four 2-byte loads and forms one 4-bit mask of admissible points per stream; a pair with an inadmissible
 //   point enters the two reductions as INFINITY, a known bit leaves as -+GF3_LLR_KNOWN.  Selects and minima round nothing:
 //   with nothing known the bytes are those of the KN = false instantiations, which are the code they were.
-#include "gf3rx_demap.h"
+#include "gf3rx_joint.h"
 
 namespace {
-
-GF3_DEV bool is_fin(double x) { return fabs(x) < INFINITY; }
 
 // ---------------------------------------------------------------------------------------------------------- pilots
 struct MimoPilotArgs {
@@ -95,8 +93,6 @@ __global__ __launch_bounds__(NC / 8) void mimo_pilots_kernel(MimoPilotArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- detector
-constexpr int MD_THREADS = 256;
-
 struct MimoDetectArgs {
     const cplx* Y[GF3_MAX_BRANCHES];        // [F*D][NB]
     const cplx* H[GF3_MAX_BRANCHES];        // [F][2][2][K]
@@ -118,11 +114,11 @@ GF3_DEV BytePair byte_pair(const uint8_t* p, int64_t cell) {
 }
 
 template <int B, bool NW, bool KN>
-__global__ __launch_bounds__(MD_THREADS) void mimo_detect_kernel(MimoDetectArgs a) {
+__global__ __launch_bounds__(JOINT_THREADS) void mimo_detect_kernel(MimoDetectArgs a) {
     const int t = threadIdx.x;
     const int tile = blockIdx.x % a.ntile, chunk = blockIdx.x / a.ntile;
     const int64_t f = blockIdx.y;
-    const int c = tile * MD_THREADS + t;
+    const int c = tile * JOINT_THREADS + t;
     if (c >= a.C) return;
     const int bin = a.bins[c];
     const int D = a.D, P = a.P;
@@ -265,11 +261,10 @@ extern "C" int gf3_mimo_pilots(gf3_ctx* c, const void* d_in, int64_t n_in, const
                                int32_t* d_status, void* stream) {
     DeviceGuard dg(c);
     if (!c) return fail(c, GF3_EINVAL, "gf3_mimo_pilots: null context");
-    if (c->cfg.P < 2 || (c->cfg.P & 1))
-        return fail(c, GF3_EINVAL, "gf3_mimo_pilots: the two covers need an even number of pilot symbols, P >= 2 (P=%d)", c->cfg.P);
+    if (const int rc = needs_even_cover(c, "gf3_mimo_pilots")) return rc;
     if (F == 0) return GF3_OK;
     if (!d_in || !d_off || !d_H_out || !d_status || F < 0 || n_in < 0) return fail(c, GF3_EINVAL, "gf3_mimo_pilots: bad argument");
-    if (F > 0x3fffffff) return fail(c, GF3_EINVAL, "gf3_mimo_pilots: more than 2^30 - 1 packets in one call");
+    if (const int rc = too_many_packets_i32(c, F, "gf3_mimo_pilots")) return rc;
     MimoPilotArgs a{FftTables{c->d_tw, c->d_twn}, d_in, n_in, d_off, c->cfg.CP, c->S, c->cfg.P, c->cfg.D, c->d_known,
                     (cplx*)d_H_out, d_status};
     hipError_t e = hipSuccess;
@@ -280,28 +275,14 @@ extern "C" int gf3_mimo_pilots(gf3_ctx* c, const void* d_in, int64_t n_in, const
 
 // the entries of the detector: `who` names the caller in a refusal, d_w is null for the unweighted ones, KN takes the planes
 template <bool NW, bool KN>
-static void mimo_detect_launch(int B, dim3 grid, hipStream_t st, const MimoDetectArgs& a) {
-    switch (B) {
-        case 1: hipLaunchKernelGGL((mimo_detect_kernel<1, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((mimo_detect_kernel<2, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((mimo_detect_kernel<3, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((mimo_detect_kernel<4, NW, KN>), grid, dim3(MD_THREADS), 0, st, a); break;
-    }
-}
-
-template <bool NW, bool KN>
 static int mimo_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* const* d_Y, const void* const* d_H,
                             const double* const* d_slope, const double* d_w, const uint8_t* d_bits, const uint8_t* d_known,
                             int64_t F, float* d_llr, void* stream) {
     DeviceGuard dg(c);
     if (!c) return fail(c, GF3_EINVAL, "%s: null context", who);
-    if (c->cfg.mu != 2 || c->cfg.M != 4)
-        return fail(c, GF3_EINVAL, "%s: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)", who,
-                    c->cfg.M, c->cfg.mu);
+    if (const int rc = needs_4_points(c, who)) return rc;
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w) && (!KN || (d_bits && d_known));
-    for (int b = 0; ok && b < B; ++b) ok = d_Y[b] && d_H[b] && d_slope[b];
-    if (!ok)
+    if (!(branches_ok(B, d_Y, d_H, d_slope) && d_llr && F >= 0 && (!NW || d_w) && (!KN || (d_bits && d_known))))
         return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra, estimates and slopes; %s%s"
                                    "an output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "",
                     KN ? "the planes of the bits and of what is known; " : "");
@@ -311,13 +292,14 @@ static int mimo_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* 
     a.llr = d_llr;
     a.bins = c->d_bins;
     a.D = c->cfg.D; a.C = c->cfg.C; a.K = c->K; a.NB = c->NC + 1; a.P = c->cfg.P;
-    a.ntile = (a.C + MD_THREADS - 1) / MD_THREADS;
-    a.Dc = symbols_per_group(c, F * a.ntile, a.D);
+    const TileGrid g = tile_grid(c, F, a.D, JOINT_THREADS);
+    a.ntile = g.ntile; a.Dc = g.run;
     a.cre = c->d_cre; a.cim = c->d_cim; a.clab = c->d_clab;
     a.wgt = d_w;
     a.bits = d_bits; a.known = d_known;
-    const dim3 grid((unsigned)(a.ntile * ((a.D + a.Dc - 1) / a.Dc)), (unsigned)F);
-    mimo_detect_launch<NW, KN>(B, grid, (hipStream_t)stream, a);
+    with_branches(B, [&](auto nb) {
+        hipLaunchKernelGGL((mimo_detect_kernel<decltype(nb)::value, NW, KN>), g.grid, dim3(JOINT_THREADS), 0, (hipStream_t)stream, a);
+    });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }

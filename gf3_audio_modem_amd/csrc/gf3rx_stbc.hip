@@ -17,11 +17,9 @@
 //   Per pair a thread reads B x 32 bytes of Y and writes 16.  Every sum runs in a fixed order, no atomics: two runs give
 //   identical bytes.  NW (gf3_stbc_detect_nw): mimo_detect_kernel's weights -- one per branch and carrier, in a register
 //   ahead of the pair loop, on that branch's term of every sum at both slots; 0 or not finite takes the branch out.
-#include "gf3rx_demap.h"
+#include "gf3rx_joint.h"
 
 namespace {
-
-GF3_DEV bool is_fin(double x) { return fabs(x) < INFINITY; }
 
 // ------------------------------------------------------------------------------------------------------------ slope
 constexpr int ST_THREADS = 256;
@@ -68,8 +66,6 @@ __global__ __launch_bounds__(ST_THREADS) void stbc_slope_kernel(StbcSlopeArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------------------ detector
-constexpr int SD_THREADS = 256;
-
 struct StbcDetectArgs {
     const cplx* Y[GF3_MAX_BRANCHES];        // [F*D][NB]
     const cplx* H[GF3_MAX_BRANCHES];        // [F][2][2][K]
@@ -82,11 +78,11 @@ struct StbcDetectArgs {
 };
 
 template <int B, bool NW>
-__global__ __launch_bounds__(SD_THREADS) void stbc_detect_kernel(StbcDetectArgs a) {
+__global__ __launch_bounds__(JOINT_THREADS) void stbc_detect_kernel(StbcDetectArgs a) {
     const int t = threadIdx.x;
     const int tile = blockIdx.x % a.ntile, chunk = blockIdx.x / a.ntile;
     const int64_t f = blockIdx.y;
-    const int c = tile * SD_THREADS + t;
+    const int c = tile * JOINT_THREADS + t;
     if (c >= a.C) return;
     const int bin = a.bins[c];
     const int D = a.D, P = a.P;
@@ -209,8 +205,7 @@ __global__ __launch_bounds__(SD_THREADS) void stbc_detect_kernel(StbcDetectArgs 
 
 // what both entries refuse of a context: the cover and the pairing
 int stbc_geometry(const gf3_ctx* c, const char* who) {
-    if (c->cfg.P < 2 || (c->cfg.P & 1))
-        return fail(c, GF3_EINVAL, "%s: the two covers need an even number of pilot symbols, P >= 2 (P=%d)", who, c->cfg.P);
+    if (const int rc = needs_even_cover(c, who)) return rc;
     if (c->cfg.D & 1)
         return fail(c, GF3_EINVAL, "%s: the code pairs the data symbols: an even D (D=%d)", who, c->cfg.D);
     return GF3_OK;
@@ -223,11 +218,9 @@ extern "C" int gf3_stbc_slope(gf3_ctx* c, int32_t B, const void* const* d_H, int
     if (!c) return fail(c, GF3_EINVAL, "gf3_stbc_slope: null context");
     if (const int rc = stbc_geometry(c, "gf3_stbc_slope")) return rc;
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_H && d_slope && F >= 0;
-    for (int b = 0; ok && b < B; ++b) ok = d_H[b] != nullptr;
-    if (!ok)
+    if (!(branches_ok(B, d_H) && d_slope && F >= 0))
         return fail(c, GF3_EINVAL, "gf3_stbc_slope: bad argument (1 <= B <= %d branches of estimates; an output; F >= 0)", GF3_MAX_BRANCHES);
-    if (F > 0x3fffffff) return fail(c, GF3_EINVAL, "gf3_stbc_slope: more than 2^30 - 1 packets in one call");
+    if (const int rc = too_many_packets_i32(c, F, "gf3_stbc_slope")) return rc;
     const int L = c->fit_hi - c->fit_lo;
     if (L < 2 || c->fit_lo < 0 || c->fit_hi > c->K)
         return fail(c, GF3_EINVAL, "gf3_stbc_slope: the fit range [%d, %d) holds fewer than 2 carriers of %d", c->fit_lo, c->fit_hi, c->K);
@@ -236,14 +229,9 @@ extern "C" int gf3_stbc_slope(gf3_ctx* c, int32_t B, const void* const* d_H, int
     a.slope = d_slope;
     a.K = c->K; a.fit_lo = c->fit_lo; a.fit_hi = c->fit_hi; a.xbar = c->xbar; a.inv_sxx = c->inv_sxx;
     const size_t lds = (size_t)(8 + L) * sizeof(double);
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    switch (B) {
-        case 1: e = launch((stbc_slope_kernel<1>), F, ST_THREADS, lds, st, a); break;
-        case 2: e = launch((stbc_slope_kernel<2>), F, ST_THREADS, lds, st, a); break;
-        case 3: e = launch((stbc_slope_kernel<3>), F, ST_THREADS, lds, st, a); break;
-        default: e = launch((stbc_slope_kernel<4>), F, ST_THREADS, lds, st, a); break;
-    }
+    const hipError_t e = with_branches(B, [&](auto nb) {
+        return launch((stbc_slope_kernel<decltype(nb)::value>), F, ST_THREADS, lds, (hipStream_t)stream, a);
+    });
     HIPCHK(c, e);
     return GF3_OK;
 }
@@ -254,14 +242,10 @@ static int stbc_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* 
                             const double* d_slope, const double* d_w, int64_t F, float* d_llr, void* stream) {
     DeviceGuard dg(c);
     if (!c) return fail(c, GF3_EINVAL, "%s: null context", who);
-    if (c->cfg.mu != 2 || c->cfg.M != 4)
-        return fail(c, GF3_EINVAL, "%s: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2 (M=%d, mu=%d)", who,
-                    c->cfg.M, c->cfg.mu);
+    if (const int rc = needs_4_points(c, who)) return rc;
     if (const int rc = stbc_geometry(c, who)) return rc;
     if (F == 0) return GF3_OK;
-    bool ok = B >= 1 && B <= GF3_MAX_BRANCHES && d_Y && d_H && d_slope && d_llr && F >= 0 && (!NW || d_w);
-    for (int b = 0; ok && b < B; ++b) ok = d_Y[b] && d_H[b];
-    if (!ok)
+    if (!(branches_ok(B, d_Y, d_H) && d_slope && d_llr && F >= 0 && (!NW || d_w)))
         return fail(c, GF3_EINVAL, "%s: bad argument (1 <= B <= %d branches, each with spectra and estimates; one slope "
                                    "array; %san output; F >= 0)", who, GF3_MAX_BRANCHES, NW ? "the weights; " : "");
     if (const int rc = too_many_packets(c, F, who)) return rc;
@@ -271,19 +255,13 @@ static int stbc_detect_call(gf3_ctx* c, const char* who, int32_t B, const void* 
     a.llr = d_llr;
     a.bins = c->d_bins;
     a.D = c->cfg.D; a.C = c->cfg.C; a.K = c->K; a.NB = c->NC + 1; a.P = c->cfg.P;
-    a.ntile = (a.C + SD_THREADS - 1) / SD_THREADS;
-    a.Jc = symbols_per_group(c, F * a.ntile, a.D / 2);
+    const TileGrid g = tile_grid(c, F, a.D / 2, JOINT_THREADS);
+    a.ntile = g.ntile; a.Jc = g.run;
     a.cre = c->d_cre; a.cim = c->d_cim; a.clab = c->d_clab;
     a.wgt = d_w;
-    const int pairs = a.D / 2;
-    const dim3 grid((unsigned)(a.ntile * ((pairs + a.Jc - 1) / a.Jc)), (unsigned)F);
-    const hipStream_t st = (hipStream_t)stream;
-    switch (B) {
-        case 1: hipLaunchKernelGGL((stbc_detect_kernel<1, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((stbc_detect_kernel<2, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((stbc_detect_kernel<3, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
-        default: hipLaunchKernelGGL((stbc_detect_kernel<4, NW>), grid, dim3(SD_THREADS), 0, st, a); break;
-    }
+    with_branches(B, [&](auto nb) {
+        hipLaunchKernelGGL((stbc_detect_kernel<decltype(nb)::value, NW>), g.grid, dim3(JOINT_THREADS), 0, (hipStream_t)stream, a);
+    });
     HIPCHK(c, hipGetLastError());
     return GF3_OK;
 }

@@ -20,6 +20,11 @@ from . import _lib, ingest
 from ._lib import Gf3Error, ptr as _ptr  # noqa: F401  (Gf3Error is importable from here as before)
 from .ingest import DIRECT_PIECE_BYTES, host_pieces  # noqa: F401  (the cut of a host stream, importable from here as before)
 
+def _table(xs):
+    """The branches' device tensors -> the table of their addresses the library takes (None stays None)."""
+    return None if xs is None else (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+
+
 _TORCH_DT = {_lib.DT_F64: torch.float64, _lib.DT_F32: torch.float32,
              _lib.DT_I16: torch.int16, _lib.DT_U8: torch.uint8}
 _DT_OF = {v: k for k, v in _TORCH_DT.items()}
@@ -794,6 +799,14 @@ class Engine:
                                                    self._stream()))
         return llr
 
+    @staticmethod
+    def _branches(who, xs):
+        """One argument per branch -> (list, B): 1 to GF3_MAX_BRANCHES of them."""
+        xs = list(xs)
+        if not 1 <= len(xs) <= _lib.GF3_MAX_BRANCHES:
+            raise ValueError(f"{who}: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {len(xs)}")
+        return xs, len(xs)
+
     def combine_branches(self, eqs, Hs=None, He=None, var=None, out=None, want=("eq", "llr")):
         """Receive diversity (gf3_combine_branches): maximal-ratio combining of B = len(eqs) <= 4 branches' equalised
         symbols, eqs[b] = demod_frames' 'eq' [F*D, C] of recording b of ONE transmission (each synchronised and demodulated
@@ -810,10 +823,7 @@ class Engine:
             raise ValueError("combine_branches: Hs and He go together")
         if (Hs is None) == (var is None):
             raise ValueError("combine_branches: give either Hs and He (csi weights) or var (noise weights), not both or neither")
-        eqs = list(eqs)
-        B = len(eqs)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"combine_branches: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        eqs, B = self._branches("combine_branches", eqs)
         want = tuple(want)
         if not want or any(k not in ("eq", "w", "llr") for k in want):
             raise ValueError(f"combine_branches: want must name at least one of 'eq', 'w', 'llr', not {want!r}")
@@ -841,11 +851,8 @@ class Engine:
         o = {k: self._out(out.get(k), kinds[k][0], kinds[k][1], kinds[k][2], name=f"combine_branches: out[{k!r}]") for k in want}
         if F and "eq" in o and any(o["eq"].data_ptr() == e.data_ptr() for e in eqs):
             raise ValueError("combine_branches: out['eq'] must be none of eqs (the other branches' sums still read it)")
-
-        def table(xs):
-            return None if xs is None else (C.c_void_p * B)(*[x.data_ptr() for x in xs])
         mode = _lib.GF3_COMBINE_NOISE if var is not None else _lib.GF3_COMBINE_CSI
-        self._check(self.lib.gf3_combine_branches(self._h, B, table(eqs), mode, table(sides[0]), table(sides[1]), table(sides[2]), F,
+        self._check(self.lib.gf3_combine_branches(self._h, B, _table(eqs), mode, _table(sides[0]), _table(sides[1]), _table(sides[2]), F,
                                                   _ptr(o.get("eq")), _ptr(o.get("w")), _ptr(o.get("llr")), self._stream()))
         return o
 
@@ -889,18 +896,14 @@ class Engine:
         combine_branches' rule under `var` -- vbar[f] the mean over all branches and data carriers, w = 1 / max(v, 1e-6
         vbar); 1 for the whole packet where vbar is 0 or not finite; 0 where v is not finite.  -> float64 [B, F, C], what
         mimo_detect and stbc_detect take as `weights`.  Fixed summation order: two calls give identical bytes."""
-        vars = list(vars)
-        B = len(vars)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"joint_noise_weights: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        vars, B = self._branches("joint_noise_weights", vars)
         vars = [self._dev(v, torch.float64) for v in vars]
         per = 2 * self.cfg.K
         if vars[0].numel() % per or any(v.numel() != vars[0].numel() for v in vars):
             raise ValueError("joint_noise_weights: every branch needs var [F, 2, K] of the same F")
         F = vars[0].numel() // per
         w = self._new((B, F, self.cfg.C), torch.float64)
-        table = (C.c_void_p * B)(*[v.data_ptr() for v in vars])
-        self._check(self.lib.gf3_joint_noise_weights(self._h, B, table, F, _ptr(w), self._stream()))
+        self._check(self.lib.gf3_joint_noise_weights(self._h, B, _table(vars), F, _ptr(w), self._stream()))
         return w
 
     def _joint_weights(self, weights, B, F, who):
@@ -922,14 +925,11 @@ class Engine:
         for noise of variance 1 / w --, and a branch whose weight is 0 drops out there as a non-finite estimate does.
         Needs a table of 4 points with mu = 2 (ValueError)."""
         B, F, Ys, Hs, slopes, llr = self._mimo_detect_args("mimo_detect", Ys, Hs, slopes, out)
-
-        def table(xs):
-            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
         if weights is None:
-            self._check(self.lib.gf3_mimo_detect(self._h, B, table(Ys), table(Hs), table(slopes), F, _ptr(llr), self._stream()))
+            self._check(self.lib.gf3_mimo_detect(self._h, B, _table(Ys), _table(Hs), _table(slopes), F, _ptr(llr), self._stream()))
         else:
             w = self._joint_weights(weights, B, F, "mimo_detect")
-            self._check(self.lib.gf3_mimo_detect_nw(self._h, B, table(Ys), table(Hs), table(slopes), _ptr(w), F, _ptr(llr),
+            self._check(self.lib.gf3_mimo_detect_nw(self._h, B, _table(Ys), _table(Hs), _table(slopes), _ptr(w), F, _ptr(llr),
                                                     self._stream()))
         return llr
 
@@ -937,30 +937,37 @@ class Engine:
         """What mimo_detect and mimo_detect_known check of their common arguments -> (B, F, the branches' tensors on the
         device, the output [F, 2, D, C, mu])"""
         cfg = self.cfg
-        Ys, Hs, slopes = list(Ys), list(Hs), list(slopes)
-        B = len(Ys)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"{who}: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        Ys, B = self._branches(who, Ys)
+        Hs, slopes = list(Hs), list(slopes)
         if len(Hs) != B or len(slopes) != B:
             raise ValueError(f"{who}: Hs holds {len(Hs)} branches and slopes {len(slopes)}, Ys {B}")
-        if cfg.mu != 2 or len(self._re) != 4:
-            raise ValueError(f"{who}: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
-                             f"points with mu = {cfg.mu}")
-        Ys = [self._dev(y) for y in Ys]
-        Hs = [self._dev(h) for h in Hs]
+        F, Ys, Hs = self._joint_args(who, Ys, Hs)
         slopes = [self._dev(s, torch.float64) for s in slopes]
-        NB = cfg.N // 2 + 1
-        if Ys[0].numel() % (cfg.D * NB):
-            raise ValueError(f"{who}: Ys must be [F*D, N/2+1] for whole packets")
-        F = Ys[0].numel() // (cfg.D * NB)
-        if any(y.numel() != F * cfg.D * NB for y in Ys):
-            raise ValueError(f"{who}: every branch needs Y [F*D, N/2+1] of the same F")
-        if any(h.numel() != F * 4 * cfg.K for h in Hs):
-            raise ValueError(f"{who}: every H must be [F, 2, 2, K] for Y [F*D, N/2+1]")
         if any(s.numel() != F for s in slopes):
             raise ValueError(f"{who}: every slope must be [F] for Y [F*D, N/2+1]")
         shape = (F, _lib.GF3_MIMO_STREAMS, cfg.D, cfg.C, cfg.mu)
         return B, F, Ys, Hs, slopes, self._out(out, shape, torch.float32, "F*2*D*C*mu", name=f"{who}: out")
+
+    def _joint_args(self, who, Ys, Hs, pairs=False):
+        """What both joint detectors check of a context (pairs: the space-time code's geometry as well) and of as many
+        spectra as estimates -> (F, both on the device)"""
+        cfg = self.cfg
+        if cfg.mu != 2 or len(self._re) != 4:
+            raise ValueError(f"{who}: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
+                             f"points with mu = {cfg.mu}")
+        if pairs:
+            self._stbc_geometry(who)
+        Ys = [self._dev(y) for y in Ys]
+        per = cfg.D * (cfg.N // 2 + 1)
+        if Ys[0].numel() % per:
+            raise ValueError(f"{who}: Ys must be [F*D, N/2+1] for whole packets")
+        F = Ys[0].numel() // per
+        if any(y.numel() != F * per for y in Ys):
+            raise ValueError(f"{who}: every branch needs Y [F*D, N/2+1] of the same F")
+        Hs = [self._dev(h) for h in Hs]
+        if any(h.numel() != F * 4 * cfg.K for h in Hs):
+            raise ValueError(f"{who}: every H must be [F, 2, 2, K] " + ("of the same F" if pairs else "for Y [F*D, N/2+1]"))
+        return F, Ys, Hs
 
     def mimo_detect_known(self, Ys, Hs, slopes, bits, known, out=None, weights=None):
         """mimo_detect told what is already known (gf3_mimo_detect_known): `bits` and `known` are uint8 tensors of F*2*D*C*mu
@@ -977,10 +984,7 @@ class Engine:
                     or not plane.is_contiguous() or plane.numel() != llr.numel()):
                 raise ValueError(f"{who}: {name} must be a contiguous uint8 tensor of F*2*D*C*mu = {llr.numel()} elements on {self.device}")
         w = None if weights is None else self._joint_weights(weights, B, F, who)
-
-        def table(xs):
-            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
-        self._check(self.lib.gf3_mimo_detect_known(self._h, B, table(Ys), table(Hs), table(slopes), _ptr(w), _ptr(bits), _ptr(known),
+        self._check(self.lib.gf3_mimo_detect_known(self._h, B, _table(Ys), _table(Hs), _table(slopes), _ptr(w), _ptr(bits), _ptr(known),
                                                    F, _ptr(llr), self._stream()))
         return llr
 
@@ -992,22 +996,6 @@ class Engine:
         if cfg.D % 2:
             raise ValueError(f"{who}: the code pairs the data symbols: an even D, not {cfg.D}")
 
-    def _stbc_estimates(self, Hs, who, F=None):
-        """Hs -> (B tensors on the device, B, F): 1 to GF3_MAX_BRANCHES arrays [F, 2, 2, K] of one F."""
-        Hs = list(Hs)
-        B = len(Hs)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"{who}: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
-        Hs = [self._dev(h) for h in Hs]
-        per = 4 * self.cfg.K
-        if F is None:
-            if Hs[0].numel() % per:
-                raise ValueError(f"{who}: every H must be [F, 2, 2, K]")
-            F = Hs[0].numel() // per
-        if any(h.numel() != F * per for h in Hs):
-            raise ValueError(f"{who}: every H must be [F, 2, 2, K] of the same F")
-        return Hs, B, F
-
     def stbc_slope(self, Hs):
         """The joint phase slope of transmit diversity (gf3_stbc_slope) from B = len(Hs) <= 4 recordings' mimo_pilots output
         [F, 2, 2, K]: per packet d[k] = sum_b sum_t conj(H_b[f, 0, t, k]) H_b[f, 1, t, k], y = unwrap(angle d), the
@@ -1016,10 +1004,16 @@ class Engine:
         with a non-finite d in the fit range.  Needs an even P >= 2 and an even D (ValueError).  Fixed summation order: two
         calls give identical bytes."""
         self._stbc_geometry("stbc_slope")
-        Hs, B, F = self._stbc_estimates(Hs, "stbc_slope")
+        Hs, B = self._branches("stbc_slope", Hs)
+        Hs = [self._dev(h) for h in Hs]
+        per = 4 * self.cfg.K
+        if Hs[0].numel() % per:
+            raise ValueError("stbc_slope: every H must be [F, 2, 2, K]")
+        F = Hs[0].numel() // per
+        if any(h.numel() != F * per for h in Hs):
+            raise ValueError("stbc_slope: every H must be [F, 2, 2, K] of the same F")
         slope = self._new((F,), torch.float64)
-        table = (C.c_void_p * B)(*[h.data_ptr() for h in Hs])
-        self._check(self.lib.gf3_stbc_slope(self._h, B, table, F, _ptr(slope), self._stream()))
+        self._check(self.lib.gf3_stbc_slope(self._h, B, _table(Hs), F, _ptr(slope), self._stream()))
         return slope
 
     def stbc_detect(self, Ys, Hs, slope, out=None, weights=None):
@@ -1034,37 +1028,20 @@ class Engine:
         mimo_detect takes them; both slots of a pair carry the branch's one weight.  Needs a table of 4 points with mu = 2,
         an even P >= 2, an even D (ValueError)."""
         cfg = self.cfg
-        Ys = list(Ys)
-        B = len(Ys)
-        if not 1 <= B <= _lib.GF3_MAX_BRANCHES:
-            raise ValueError(f"stbc_detect: 1 to {_lib.GF3_MAX_BRANCHES} branches, not {B}")
+        Ys, B = self._branches("stbc_detect", Ys)
         Hs = list(Hs)
         if len(Hs) != B:
             raise ValueError(f"stbc_detect: Hs holds {len(Hs)} branches, Ys {B}")
-        if cfg.mu != 2 or len(self._re) != 4:
-            raise ValueError(f"stbc_detect: the joint detector scans 4 x 4 pairs: a table of 4 points with mu = 2, not {len(self._re)} "
-                             f"points with mu = {cfg.mu}")
-        self._stbc_geometry("stbc_detect")
-        Ys = [self._dev(y) for y in Ys]
-        NB = cfg.N // 2 + 1
-        if Ys[0].numel() % (cfg.D * NB):
-            raise ValueError("stbc_detect: Ys must be [F*D, N/2+1] for whole packets")
-        F = Ys[0].numel() // (cfg.D * NB)
-        if any(y.numel() != F * cfg.D * NB for y in Ys):
-            raise ValueError("stbc_detect: every branch needs Y [F*D, N/2+1] of the same F")
-        Hs, _, _ = self._stbc_estimates(Hs, "stbc_detect", F)
+        F, Ys, Hs = self._joint_args("stbc_detect", Ys, Hs, pairs=True)
         slope = self._dev(slope, torch.float64)
         if slope.numel() != F:
             raise ValueError("stbc_detect: the slope must be ONE array [F] for Y [F*D, N/2+1]")
         llr = self._out(out, (F, cfg.D, cfg.C, cfg.mu), torch.float32, "F*D*C*mu", name="stbc_detect: out")
-
-        def table(xs):
-            return (C.c_void_p * B)(*[x.data_ptr() for x in xs])
         if weights is None:
-            self._check(self.lib.gf3_stbc_detect(self._h, B, table(Ys), table(Hs), _ptr(slope), F, _ptr(llr), self._stream()))
+            self._check(self.lib.gf3_stbc_detect(self._h, B, _table(Ys), _table(Hs), _ptr(slope), F, _ptr(llr), self._stream()))
         else:
             w = self._joint_weights(weights, B, F, "stbc_detect")
-            self._check(self.lib.gf3_stbc_detect_nw(self._h, B, table(Ys), table(Hs), _ptr(slope), _ptr(w), F, _ptr(llr),
+            self._check(self.lib.gf3_stbc_detect_nw(self._h, B, _table(Ys), _table(Hs), _ptr(slope), _ptr(w), F, _ptr(llr),
                                                     self._stream()))
         return llr
 

@@ -18,6 +18,7 @@ from tests import joint_noise_ref as JR
 from tests import mimo_ref as MR
 from tests import stbc_ref as SR
 from tests import tables as T
+from tests.joint_checks import held_to_the_restatement as joint_held
 from tests.test_mimo_gpu import LEAD, TAIL, detect_inputs, engine_of, quiet, same_bytes, small_params
 
 pytestmark = pytest.mark.gpu
@@ -183,13 +184,7 @@ def check_weighted(code, p, eng, Ys, Hs, slopes, w, packets=None):
         slopes = [s[packets] for s in slopes] if code == "mimo" else slopes[packets]
         part = got[packets]
     ref, pair = restated(Ys, Hs, slopes, w, p)
-    assert part.shape == ref.shape
-    atol = 1e-9 * np.abs(ref).max()
-    np.testing.assert_allclose(part, ref, rtol=1e-6, atol=atol)
-    clear = np.abs(ref) > atol
-    assert clear.mean() > 0.95
-    lab = np.asarray(p.const_bits)[pair].astype(bool)
-    assert np.array_equal((part < 0)[clear], lab[clear])
+    joint_held(part, ref, pair, p.const_bits, clear_share=0.95)
     return got
 
 

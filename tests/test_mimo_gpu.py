@@ -18,6 +18,7 @@ import torch
 from oracle import gf3_oracle as orc
 from tests import mimo_ref as MR
 from tests import tables as T
+from tests.joint_checks import held_to_the_restatement
 from tests.test_mimo_cpu import LEVEL_DB
 
 pytestmark = pytest.mark.gpu
@@ -149,13 +150,7 @@ def check_detect(p, eng, Ys, Hs, slopes, packets=None):
         Ys, Hs, slopes = [y[rows] for y in Ys], [h[packets] for h in Hs], [s[packets] for s in slopes]
         part = got[packets]
     ref, pair = MR.detect(Ys, Hs, slopes, p)
-    assert part.shape == ref.shape
-    atol = 1e-9 * np.abs(ref).max()
-    np.testing.assert_allclose(part, ref, rtol=1e-6, atol=atol)
-    clear = np.abs(ref) > atol
-    assert clear.mean() > 0.99
-    lab = np.asarray(p.const_bits)[pair].astype(bool)         # [F, 2, D, C, mu]: the bits of the joint argmin
-    assert np.array_equal((part < 0)[clear], lab[clear])
+    held_to_the_restatement(part, ref, pair, p.const_bits)
     return got
 
 

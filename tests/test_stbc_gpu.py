@@ -14,6 +14,7 @@ from oracle import gf3_oracle as orc
 from tests import mimo_ref as MR
 from tests import stbc_ref as SR
 from tests import tables as T
+from tests.joint_checks import held_to_the_restatement
 from tests.test_mimo_gpu import LEAD, TAIL, detect_inputs, engine_of, facade, oracle_params, quiet, resampled, same_bytes, small_params
 from tests.test_stbc_cpu import LEVEL_DB, MIC
 
@@ -78,13 +79,7 @@ def check_detect(p, eng, Ys, Hs, slope, packets=None):
         Ys, Hs, slope = [y[rows] for y in Ys], [h[packets] for h in Hs], slope[packets]
         part = got[packets]
     ref, pair = SR.detect(Ys, Hs, slope, p)
-    assert part.shape == ref.shape
-    atol = 1e-9 * np.abs(ref).max()
-    np.testing.assert_allclose(part, ref, rtol=1e-6, atol=atol)
-    clear = np.abs(ref) > atol
-    assert clear.mean() > 0.99
-    lab = np.asarray(p.const_bits)[pair].astype(bool)         # [F, D, C, mu]: the bits of the joint argmin
-    assert np.array_equal((part < 0)[clear], lab[clear])
+    held_to_the_restatement(part, ref, pair, p.const_bits)
     return got
 
 
