@@ -24,7 +24,7 @@ from ._lib import GF3_MAX_BRANCHES
 from .engine import Engine, RxConfig, map_bits
 from .loading import map_loaded, validate_loading
 from .pipeline import check_clock, check_rate, convert_rate, correct_clock, demodulate, fetch, plan_receive  # noqa: F401  (importable from here as before)
-from .pipeline import check_mimo_pilots, check_stbc_length, plan_mimo, plan_stbc
+from .pipeline import check_mimo_pilots, check_stbc_length, plan_mimo, plan_stbc, window_report, window_stage
 
 __all__ = ["CamG", "transmitter", "receiver", "load_file", "save_file", "np"]
 
@@ -60,6 +60,7 @@ class CamG:
 
     last_tx_report = None                       # set by every transmit() (see papr_reduction below)
     last_input_rate = None                      # set by receive calls once one has run under input_rate (see input_rate below)
+    last_window_report = None                   # set by receive calls once one has run under receive_window (see receive_window below)
     sync_report = None                          # set by every receive call (see sync_rule below)
     last_mimo_separation = None                 # set by every receive_mimo() (see mimo_advance below)
     last_stbc_slope = None                      # set by every receive_stbc(): the joint phase slope per packet, float64 [F]
@@ -152,6 +153,23 @@ class CamG:
         self.blanking_guard = 8
         self.last_blanked = None
         self.last_sample_level = None
+        # every encoding: receive_window = L > 0 tapers, between sync (blanking, clock correction) and every demodulator call,
+        # the last L samples of each symbol by a raised cosine and folds in the L samples one period earlier, the end of its
+        # cyclic prefix (Engine.window_frames).  A transform cuts its N samples out with a rectangle, and what
+        # is not periodic in N -- a whistle, a fan or coil whine, another device's beep, the interference a residual clock
+        # offset leaves -- leaks into EVERY carrier with sidelobes that fall as 1 / distance; `llr_weighting` = "noise" can
+        # only mark carriers, and a steady tone is no impulse to blank.  Under the window the sidelobes fall as 1 / distance^3
+        # and the tone costs a narrow notch.  The wanted signal passes unchanged as long as the channel leaves the last L
+        # samples of the prefix clean: L is spent from the prefix, so it is for the modes with a prefix to spare (B, C) or
+        # short channels.  Choose L <= cp_length - the largest kept delay of `last_denoise_report`; every receive call leaves
+        # {"taper": L, "mismatch_db": 10 log10(the energy of the difference of the two stretches it blended / their energy)
+        # per packet [packets] ([B, packets] for several recordings)} in `last_window_report` -- about 3 dB below -SNR for a
+        # clean prefix, rising as the channel's tail reaches into the ramp -- and None with the stage off (the attribute stays
+        # on the class, like `last_input_rate`, until a call under receive_window first sets it).  receive_mimo and
+        # receive_stbc take `mimo_advance` from the same prefix: ValueError when mimo_advance + receive_window > cp_length.
+        # ValueError for a value that is not an integer in [0, cp_length]; NotImplementedError on the piece-wise host path.
+        # 0: everything as without it, bit for bit.
+        self.receive_window = 0
         # "QCLDPC-*", staged path: decoder_feedback = n > 0 lets receive() decode up to n more times.  The codewords that
         # decoded (and, under codeword_crc, whose CRC matches) are re-encoded; the residual channel measured on their symbols,
         # smoothed over +-feedback_window[0] symbols x +-feedback_window[1] bins wherever at least feedback_min_known known
@@ -1010,8 +1028,8 @@ class receiver(transmitter):
 
     # ---- the steps receive_mimo and receive_stbc share ------------------------------------------------------------------
     def _covered_estimates(self, eng, plan, xs, starts):
-        """Step 2 of both: every packet start moved back by the plan's advance; per recording the clock correction (xs[i] is
-        replaced by the corrected samples), the demodulator for the slope, the ragged flag and the returned Hs / He, and
+        """Step 2 of both: every packet start moved back by the plan's advance; per recording the clock correction and the
+        receive window (xs[i] is replaced by the rows they leave), the demodulator for the slope, the ragged flag and the returned Hs / He, and
         Engine.mimo_pilots for the two columns of the channel -> (slopes, Hs, ragged flags, clock stages, recording 0's
         demodulator outputs, the moved starts, under the plan's joint_noise every recording's Engine.mimo_pilot_noise
         [F, 2, K] -- else an empty list)."""
@@ -1023,7 +1041,11 @@ class receiver(transmitter):
             if plan.clock:
                 x, st, clock_status, stage = correct_clock(eng, x, st, plan.clock)
                 ragged.append(clock_status)
-                xs[i] = x
+            if plan.window:
+                x, st, window_status, window_rows = window_stage(eng, x, st, plan.window)
+                stage = {**stage, **window_rows}
+                ragged.append(window_status)
+            xs[i] = x
             o = eng.demod_frames(x, st, want=("Hs", "He", "slope", "status"))
             H, status = eng.mimo_pilots(x, st)
             first = o if first is None else first
@@ -1091,6 +1113,8 @@ class receiver(transmitter):
         print("Number of received OFDM symbols:    " + str(symbols))
         bits = bits_t.cpu().numpy().astype(np.int64)
         self._last_slope = got["slope"]
+        if plan.window or "last_window_report" in vars(self):             # (value or None, from the first call under receive_window on)
+            self.last_window_report = window_report(plan, got)
         self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
         if plan.rates is not None or "last_input_rate" in vars(self):
             self.last_input_rate = None if plan.rates is None else np.array([float(self.fs) if v is None else v[0] for v in plan.rates])
@@ -1169,7 +1193,7 @@ class receiver(transmitter):
         xs, starts, sync_rho = self._synchronise(eng, plan, rs, located)
         # 2. demodulate, every recording on its own: under impulse_blanking a copy of the samples with the clicks inside the
         # packets' bodies blanked, under clock_correction the packets' bodies at the corrected rate, packed (every recording
-        # has its own clock)
+        # has its own clock), under receive_window those bodies with every symbol tapered into its prefix, packed
         need_eq = diversity or plan.rate is not None or plan.chain.loading is not None
         outs, stages, ragged = [], [], []
         for x, st in zip(xs, starts):
@@ -1180,6 +1204,10 @@ class receiver(transmitter):
                 x, st, clock_status, clock_rows = correct_clock(eng, x, st, plan.clock)
                 stage.update(clock_rows)
                 ragged.append(clock_status)
+            if plan.window:
+                x, st, window_status, window_rows = window_stage(eng, x, st, plan.window)
+                stage.update(window_rows)
+                ragged.append(window_status)
             outs.append(demodulate(eng, plan, x, st, need_eq))
             if "denoise_report" in outs[-1]:                    # (under channel_denoising only)
                 stage["last_denoise_report"] = outs[-1]["denoise_report"]
@@ -1245,6 +1273,8 @@ class receiver(transmitter):
         """The attributes a receive call leaves, from the fetched rows.  Each call assigns its own list and touches nothing
         else (the table and the open point that follows from it: DESIGN §12, "The receive pipeline")."""
         self._last_slope = got["slope"]
+        if plan.window or "last_window_report" in vars(self):             # (value or None, from the first call under receive_window on)
+            self.last_window_report = window_report(plan, got)
         self.sync_report = {"rho": got["sync_rho"].tolist(), "threshold": plan.detect} if "sync_rho" in got else None
         if plan.rates is not None or "last_input_rate" in vars(self):      # (value or None, from the first call under input_rate on)
             applied = None if plan.rates is None else [float(self.fs) if v is None else v[0] for v in plan.rates]

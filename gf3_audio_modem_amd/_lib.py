@@ -169,6 +169,8 @@ _SIGS = {
     "gf3_resample_coefficients": (C.c_int, [C.c_int32, c_double_p]),
     "gf3_resample_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "gf3_window_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "gf3_resample_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int64,
                                       C.c_int64, C.c_void_p, C.c_void_p]),
     "gf3_ldpc_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -29,7 +29,7 @@ CSRC = os.path.join(HERE, "csrc")
 UNITS = ["gf3rx_demod_soft", "gf3rx_dsplit_soft",
          "gf3rx_demod_full", "gf3rx_dsplit_full", "gf3rx_demod_scan", "gf3rx_dsplit_scan", "gf3rx_demod_screen", "gf3rx_demod_qpsk", "gf3rx_dsplit_qpsk",
          "gf3rx_screen", "gf3rx_corr", "gf3rx_demod_split", "gf3rx_fscreen",
-         "gf3rx_fft", "gf3rx_sync", "gf3rx_detect", "gf3rx_ldpc", "gf3rx_outer", "gf3rx_crc", "gf3rx_track", "gf3rx_feedback", "gf3rx_blank", "gf3rx_resample", "gf3rx_denoise", "gf3rx_papr", "gf3rx_noise", "gf3rx_loading", "gf3rx_combine", "gf3rx_mimo", "gf3rx_stbc", "gf3rx_joint_noise", "gf3rx_demap", "gf3rx_ctx", "gf3rx_abi", "gf3rx_sync_frames"]
+         "gf3rx_fft", "gf3rx_sync", "gf3rx_detect", "gf3rx_ldpc", "gf3rx_outer", "gf3rx_crc", "gf3rx_track", "gf3rx_feedback", "gf3rx_blank", "gf3rx_resample", "gf3rx_window", "gf3rx_denoise", "gf3rx_papr", "gf3rx_noise", "gf3rx_loading", "gf3rx_combine", "gf3rx_mimo", "gf3rx_stbc", "gf3rx_joint_noise", "gf3rx_demap", "gf3rx_ctx", "gf3rx_abi", "gf3rx_sync_frames"]
 SRC = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 STAMP_SRC = os.path.join(CSRC, "gf3rx_stamp.cpp")
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "gf3rx.h")]

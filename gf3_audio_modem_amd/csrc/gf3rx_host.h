@@ -32,6 +32,8 @@
 //   gf3rx_resample.hip       resample_kernel + gf3_resample_frames, gf3_resample_coefficients (sampling-clock correction of the packet
 //                            bodies; the storage rounding it shares with gf3rx_blank.hip is gf3rx_storage.h);
 //                            resample_stream_kernel + gf3_resample_stream (whole-stream rate conversion in front of the sync)
+//   gf3rx_window.hip         window_kernel + gf3_window_frames (receive windowing: every symbol of the packet bodies tapered into
+//                            its cyclic prefix, between the clock correction and demodulation)
 //   gf3rx_denoise.hip        denoise_kernel + gf3_denoise_pilots (delay-domain denoising of the pilot sums ahead of the estimate stage)
 //   gf3rx_papr.hip           papr_kernel + gf3_tone_reserve (transmit side: per data symbol, values for the carriers outside the
 //                            data band that lower the symbol's peak; gf3_tx_frames_ex sends them in the filler's place)

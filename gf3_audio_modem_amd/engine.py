@@ -1186,6 +1186,44 @@ class Engine:
         return rows, torch.arange(F, dtype=torch.int64, device=self.device) * n, status
 
     @staticmethod
+    def check_window(taper, cp):
+        """ValueError unless `taper`, the samples of a receive window's ramp, is an integer (not a bool) in [0, cp] -> the int."""
+        if isinstance(taper, (bool, np.bool_)) or not isinstance(taper, (int, np.integer)) or not 0 <= taper <= cp:
+            raise ValueError(f"receive_window must be an integer number of samples in [0, cp_length = {cp}], not {taper!r}")
+        return int(taper)
+
+    @staticmethod
+    def window_ramp(taper):
+        """The raised-cosine ramp the receive window takes: r[i] = 0.5 - 0.5 cos(pi (i + 0.5) / L), so r[i] + r[L-1-i] = 1."""
+        return 0.5 - 0.5 * np.cos(np.pi * (np.arange(taper, dtype=np.float64) + 0.5) / taper)
+
+    def window_frames(self, x, frame_offsets, taper, out=None):
+        """Receive windowing of the packet bodies (gf3_window_frames): in every symbol of packet f, 2P + D symbols from
+        frame_offsets[f] on, the last `taper` = L samples fade out by a raised cosine while the L samples one period
+        earlier -- the end of the cyclic prefix -- fade in on top of them; every other sample is copied.  Where the prefix
+        outlasts the channel by L samples the wanted signal passes unchanged, and what is not periodic in N (a whistle, a
+        fan, a neighbour's beep) leaks into the carriers with sidelobes that fall as 1 / distance^3 instead of 1 / distance.
+        x may be resample_frames' rows with their offsets.  out: optional contiguous tensor of F * M * S samples in the
+        storage type, not x itself.  taper: an integer in [1, CP] (0 is refused: there is nothing to do).
+        -> (rows [F, M S] in the storage type, offsets int64 [F] = f M S -- what any demodulator call takes next to rows --,
+        status int32 [F]: bit 0 the body is not inside the samples (row of zeros, NaN report), report float64 [F, M, 2]: per
+        symbol the squared difference of the two stretches that are blended, summed, and the sum of their squares.)  Two
+        calls give identical bytes."""
+        taper = self.check_window(taper, self.cfg.CP)
+        if taper == 0:
+            raise ValueError("window_frames: a taper of 0 samples windows nothing; skip the call")
+        x = self._samples(x)
+        off = self._dev(frame_offsets, torch.int64)
+        F, n = off.numel(), self.cfg.M * self.cfg.S
+        ramp = self._dev(self.window_ramp(taper), torch.float64)
+        rows = self._out(out, (F, n), self.cfg.in_dtype, "F * M * S").reshape(F, n)
+        status = self._new((F,), torch.int32)
+        report = self._new((F, self.cfg.M, 2), torch.float64)
+        self._check(self.lib.gf3_window_frames(self._h, _ptr(x), x.numel(), _ptr(off), F, _ptr(ramp), taper, _ptr(rows), _ptr(report),
+                                               _ptr(status), self._stream()))
+        return rows, torch.arange(F, dtype=torch.int64, device=self.device) * n, status, report
+
+    @staticmethod
     def check_ratio(r, half_taps, who="resample_stream"):
         """ValueError unless r is a finite number in [0.25, 4] and half_taps 16 or 32 (what gf3_resample_stream refuses)
         -> (r as a float, half_taps as an int)."""

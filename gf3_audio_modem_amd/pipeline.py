@@ -123,6 +123,7 @@ class ReceivePlan(NamedTuple):
     advance: int = 0                        # receive_mimo: samples every packet start is moved back by (`mimo_advance`)
     joint_noise: bool = False               # receive_mimo, receive_stbc: pilot-measured weights (`joint_weighting` = "noise")
     cancel: int = 0                         # receive_mimo: passes of decoder-driven cancellation at most (`mimo_cancellation`)
+    window: int = 0                         # samples of the receive window's ramp (`receive_window`), 0: no windowing stage
 
 
 def check_mimo_pilots(no_pilots):
@@ -167,7 +168,8 @@ def check_cancellation(chain, rate, who, cancels):
 def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams", verb="separates", cancels=True):
     """The plan of receive_mimo() on recordings of `lengths` samples, in plan_receive's manner and order: the pilot cover's
     and the coded chain's own refusals (CodedChain.check_mimo), the values of the joint weighting, the advance, the clock
-    correction, the sync rule and the input rate (ValueError), then what has no path (NotImplementedError).  No GPU work.
+    correction, the sync rule, the input rate and the receive window (ValueError), then what has no path
+    (NotImplementedError).  No GPU work.
     (plan_stbc names itself in `who` and, with cancels = False, refuses `mimo_cancellation`.)"""
     check_mimo_pilots(rx.no_pilots)
     rate = chain.check_mimo(who, what)
@@ -177,6 +179,10 @@ def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams",
     detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
     rates = check_input_rates(rx, len(lengths), True)
     cancel = check_cancellation(chain, rate, who, cancels)
+    window = Engine.check_window(rx.receive_window, rx.cp_length)
+    if advance + window > rx.cp_length:
+        raise ValueError(f"{who}: mimo_advance + receive_window = {advance} + {window} samples exceed cp_length = {rx.cp_length}: "
+                         "nothing of the prefix would be left")
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
     no_path = ((rx.impulse_blanking, f"{who}: impulse_blanking is not applied; blank each recording's samples with "
@@ -189,7 +195,7 @@ def plan_mimo(rx, chain, lengths, plots, who="receive_mimo", what="two streams",
         if on:
             raise NotImplementedError(why.format(host=_HOST))
     return ReceivePlan(chain, rate, False, None, clock, None, False, False, int(chunk or PIECEWISE_CHUNK), detect, rates, advance,
-                       joint_noise, cancel)
+                       joint_noise, cancel, window)
 
 
 def check_stbc_length(packet_length):
@@ -211,7 +217,8 @@ def plan_receive(rx, chain, lengths, plots, diversity):
     """The plan of receive() (diversity False) or receive_diversity() on recordings of `lengths` samples, from the
     receiver's attributes as they are now and its CodedChain.  Every refusal of a receive call is raised here, in this order:
     the coded chain's own (CodedChain.check_receive / check_diversity: ValueError), the values of the blanking and the
-    clock correction, of the sync rule and of the input rate (ValueError), then what has no path (NotImplementedError)."""
+    clock correction, of the sync rule, of the input rate and of the receive window (ValueError), then what has no path
+    (NotImplementedError)."""
     chunk = getattr(rx, "host_chunk_samples", None)
     piecewise = not plots and bool(chunk or any(n > PIECEWISE_ABOVE for n in lengths))
     if diversity:
@@ -219,18 +226,21 @@ def plan_receive(rx, chain, lengths, plots, diversity):
         clock = check_clock(rx.clock_correction, rx.clock_taps)
         detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
         rates = check_input_rates(rx, len(lengths), True)
+        window = Engine.check_window(rx.receive_window, rx.cp_length)
         no_path = ((rx.impulse_blanking, "receive_diversity: impulse_blanking is not combined; blank each recording's samples "
                                          "with Engine.blank_impulses first"),
                    (plots, "receive_diversity: no plots; receive() one recording for them"),
                    (piecewise, "receive_diversity: {host} combines nothing; receive shorter recordings"),
                    (detect and piecewise, _LOCAL),
-                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"))
+                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"),
+                   (window and piecewise, "receive_window: {host} has no windowing pass; receive shorter recordings"))
     else:
         rate, fused = chain.check_receive()
         blanking = Engine.check_blanking(rx.blanking_threshold, rx.blanking_guard) if rx.impulse_blanking else None
         clock = check_clock(rx.clock_correction, rx.clock_taps)
         detect = check_sync_rule(rx.sync_rule, rx.detect_threshold)
         rates = check_input_rates(rx, len(lengths), False)
+        window = Engine.check_window(rx.receive_window, rx.cp_length)
         loaded = chain.loading is not None
         no_path = ((chain.denoise and piecewise, "channel_denoising: {host} has no denoising pass; receive shorter recordings"),
                    (loaded and plots, "bit_loading: the plots draw one constellation; receive with graph_output = False"),
@@ -240,13 +250,14 @@ def plan_receive(rx, chain, lengths, plots, diversity):
                    (rate is not None and piecewise, "encoding {encoding!r}: {host} has no soft-decision decoding; "
                                                     "receive shorter recordings"),
                    (detect and piecewise, _LOCAL),
-                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"))
+                   (rates and piecewise, "input_rate: {host} has no rate conversion; receive shorter recordings"),
+                   (window and piecewise, "receive_window: {host} has no windowing pass; receive shorter recordings"))
     for on, why in no_path:
         if on:
             raise NotImplementedError(why.format(host=_HOST, encoding=chain.encoding))
     denoise = None if chain.denoise is None else float(chain.denoise[0])       # (validated by the chain's checks above)
     return ReceivePlan(chain, rate, fused and not plots, blanking, clock, denoise, bool(plots), piecewise,
-                       int(chunk or PIECEWISE_CHUNK), detect, rates)
+                       int(chunk or PIECEWISE_CHUNK), detect, rates, window=window)
 
 
 def convert_rate(eng, r, rate, fs):
@@ -275,6 +286,25 @@ def correct_clock(eng, x, starts, clock):
         eps = rows["last_clock_ppm"] * 1e-6
     out, offsets, status = eng.resample_frames(x, starts, eps.expand(F).contiguous(), half_taps=half_taps)
     return out, offsets, status, rows
+
+
+def window_stage(eng, x, starts, taper):
+    """The receive window of one recording (taper = the plan's `window`, not 0), on the samples as blanking and the clock
+    correction left them -> (rows, offsets: what the demodulator takes in place of (x, starts), status int32 [F]: non-zero
+    for a packet that is not inside the samples, {"window_sums": per packet the two sums of Engine.window_frames' report over
+    its symbols, float64 [F, 2]; `window_report` turns them into `last_window_report`})."""
+    rows, offsets, status, report = eng.window_frames(x, starts, taper)
+    return rows, offsets, status, {"window_sums": report.sum(dim=1)}
+
+
+def window_report(plan, got):
+    """`last_window_report` of a receive call from its fetched rows: None with the stage off, else the taper and per packet
+    (per recording and packet for several recordings) 10 log10 of the prefix mismatch over the power it is measured against."""
+    if not plan.window:
+        return None
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sums = got["window_sums"]
+        return {"taper": plan.window, "mismatch_db": 10.0 * np.log10(sums[..., 0] / sums[..., 1])}
 
 
 def demodulate(eng, plan, x, starts, need_eq):

@@ -972,6 +972,36 @@ int gf3_resample_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int6
                         const double *d_eps_f64, int32_t half_taps, void *d_out, int32_t *d_status_i32, void *stream);
 
 /*
+ * Receive windowing, between sync (blanking, clock correction) and demodulation (not in the reference).  Opt-in.  Every
+ * transform cuts a symbol out with a rectangle of N samples, and whatever is not periodic in N -- a whistle, a fan, the
+ * interference a residual clock offset leaves -- leaks into every carrier with the rectangle's sidelobes, 1 / distance.
+ * gf3_window_frames tapers the last L samples of every symbol's body and folds in the L samples one period (N) earlier,
+ * the last L of its cyclic prefix.  Where the prefix outlasts the channel the two stretches carry the same signal, which
+ * therefore passes unchanged, and everything else is seen through a window whose edges follow the ramp.
+ *   Packet f: body [s_f, s_f + M S), s_f = d_frame_offsets[f], M = 2P + D, S = N + CP.  Symbol m with samples
+ *   s[0 .. S) = x[s_f + m S ..), ramp r = d_ramp_f64 [L], 1 <= L <= CP; all in fp64, i = 0 .. L - 1:
+ *       out[f, m S + S - L + i] = s[S - L + i] * (1 - r[i]) + s[CP - L + i] * r[i]
+ *   (four rounded operations, of which the compiler may contract one into a fused multiply-add); every other sample of
+ *   the body is copied.  The ramp is the caller's: any r with r[i] + r[L - 1 - i] = 1 keeps the window Nyquist.
+ *   d_out is a packed [F, M S] array in the context's storage type (gf3_resample_frames' conversion: fp64 as is, f32 by a
+ *   cast, i16 / u8 by rint, half to even, clamped); frame offsets f M S into it feed every demodulator entry point, and
+ *   gf3_resample_frames' rows with their offsets are a valid input here.
+ *   d_report_f64 [F, M, 2], per symbol: [0] = sum_i (s[S-L+i] - s[CP-L+i])^2, the prefix mismatch; [1] = sum_i
+ *   (s[S-L+i]^2 + s[CP-L+i]^2).  Their ratio grows when the channel's tail reaches into the ramp.  A sample among those
+ *   2L that is not finite makes that symbol's two sums NaN and no other's; in `out` it reaches the one or two outputs it
+ *   enters.  Every sum runs in a fixed order (a thread's elements ascending, the wave butterfly, the waves in order).
+ *   d_status_i32 [F]: bit 0 -- the body is not inside [0, n_in) (the rule of gf3_blank_impulses): the row is zeros and
+ *   the packet's report NaN.
+ *   GF3_EINVAL (the text names the function) for a null context, a null pointer with F > 0, d_out == d_in, F < 0,
+ *   n_in < 0, L outside [1, CP] and more than 65535 packets in one call.  F == 0 is a no-op.  One launch, no atomics (two
+ *   runs give identical bytes), no workspace, asynchronous on `stream`.  Samples are read and written at their element
+ *   alignment; 16-byte accesses are taken where the addresses allow them.
+ */
+int gf3_window_frames(gf3_ctx *ctx, const void *d_in, int64_t n_in, const int64_t *d_frame_offsets, int64_t F,
+                      const double *d_ramp_f64, int32_t L, void *d_out, double *d_report_f64, int32_t *d_status_i32,
+                      void *stream);
+
+/*
  * Whole-stream rate conversion, in front of the sync (not in the reference).  Opt-in.  Every kernel here assumes samples
  * taken at cfg.fs; a recording at 44.1, 88.2 or 96 kHz is 88 435 ppm and more away, far beyond what the per-packet
  * correction above can take.  gf3_resample_stream converts a stream by any ratio, in either direction, and can be cut
